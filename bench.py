@@ -2,16 +2,21 @@
 """bench.py -- k-mer count throughput of the MI355X FM-index engine (BASELINE.json's metric).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full   (the headline plus every other measurement and check below)
     python bench.py --in-process N                         (one process, N replicas: the path a Rust caller on a node uses)
 
 One "step" = one pass of the hot path (awry_dev_count_nt2: seeded backward search over packed 31-mers)
 over one batch of synthetic queries per GPU, queries already resident in HBM.  The index is replicated
 per GPU and the query batch is sharded by rank with no data-path collective -> weak scaling.
-Rank 0 prints ONE JSON line with the roofline object (algorithmic bytes from an in-kernel work census,
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the headline: `value`
+queries/s and `ms_per_step`.  `--dump-outputs DIR` writes what the last timed step computed (rank 0's counts, a
+fixed sample of them when the batch is large) as DIR/*.npy before the line is printed.
+With `--full` the line also carries the roofline object (algorithmic bytes from an in-kernel work census,
 HIP-event kernel time, HBM traffic from rocprofv3 counter passes of this very run) and, at N == 1, the CPU
 baseline (the oracle = C restatement of the reference's rayon/AVX2 path, timed on this host's cores on a
-bounded sample of the same batch).  At N == 1 the line also carries every other BASELINE config at its own size
-(`variants`, `locate` = configs[2] with 100 M reads, `amino` = configs[3]), each checked against the oracle in the run.
+bounded sample of the same batch).  At N == 1 the full line also carries every other BASELINE config at its own size
+(`variants`, `locate` = configs[2] with 100 M reads, `amino` = configs[3]), each checked against the oracle in the run;
+at N > 1 the parity checks across ranks and the host-boundary aggregate.
 
 HBM traffic: after its own measurements the run starts itself again under `rocprofv3 --pmc` (one child per counter
 set: FETCH_SIZE / WRITE_SIZE / TCC hit+miss, as MI355X_MICROARCH.md prescribes) on the index it saved; the child
@@ -80,6 +85,28 @@ def unpack_nt2(words, L):
     for j in range(L):
         out[:, j] = lut[((w >> np.uint64(2 * j)) & np.uint64(3)).astype(np.int64)]
     return out
+
+
+DUMP_SAMPLE = 1 << 21  # counts --dump-outputs writes when a batch is larger: 2 M float64 values + their positions = 32 MiB
+
+
+def dump_sample_index(n, seed=0xD0D0):
+    """positions of the results --dump-outputs writes: all n when n <= DUMP_SAMPLE, else a fixed seeded sample, ascending"""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, DUMP_SAMPLE, replace=False)).astype(np.int64)
+
+
+def dump_outputs(d, torch, counts):
+    """what the caller of the timed path receives from its last step: the occurrence count of every query (`counts.npy`),
+    with the queries' positions in the batch (`query_index.npy`).  float64 holds both exactly (a count is at most the text
+    length)."""
+    idx = dump_sample_index(counts.numel())
+    got = counts[torch.from_numpy(idx).to(counts.device)].cpu().numpy().copy().view(np.uint64)
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "counts.npy"), got.astype(np.float64))
+    np.save(os.path.join(d, "query_index.npy"), idx.astype(np.float64))
+    log("outputs of the last timed step: %d of %d counts -> %s" % (len(idx), counts.numel(), d))
 
 
 # Every host array this file takes from a device tensor is `.cpu().numpy().copy()`: numpy-owned memory, the torch CPU tensor
@@ -787,6 +814,9 @@ def main():
     ap.add_argument("--pmc-child", default="", help=argparse.SUPPRESS)
     ap.add_argument("--phase-file", default="", help=argparse.SUPPRESS)
     ap.add_argument("--in-process", type=int, default=0, help="one process, this many replicas (awry_set_devices): times the host batch entry points")
+    ap.add_argument("--full", action="store_true", help="besides the headline: roofline census, CPU baseline, every other config, oracle checks, "
+                                                        "counter passes (N = 1); parity checks and the host boundary (N > 1)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
     if args.pmc_child:
         return pmc_child(args)
@@ -845,7 +875,7 @@ def main():
         pass
     tmpdir = tempfile.mkdtemp(prefix="awry_bench_", dir=shm) if rank == 0 else None
     index_path = None
-    want_pmc = not args.no_pmc and world == 1
+    want_pmc = args.full and not args.no_pmc and world == 1
 
     # ---- index: built ONCE (rank 0, on its GPU) and handed to the other ranks as an .awry v1 file; every rank then
     #      replicates it into its own GPU's HBM and builds its seed table / accelerators there, concurrently
@@ -858,7 +888,7 @@ def main():
         ix = awry_amd.FmIndex.from_text(text, 0, 8, 0, starts, headers, build_device=local_rank)
         t2 = time.time()
         index_path = os.path.join(tmpdir, "index.awry")
-        if world > 1 or args.cpu_seconds > 0 or want_pmc:
+        if world > 1 or (args.full and args.cpu_seconds > 0) or want_pmc:
             ix.save(index_path)  # .awry v1 in the reference's own layout: 160-B blocks, packed SA, k-mer table
         log("text %.1fs (%s), index build %.1fs, save %.1fs" % (t1 - t0, json.dumps(text_info), t2 - t1, time.time() - t2))
     if world > 1:
@@ -923,25 +953,8 @@ def main():
     ix.dev_phase_marker(60000, stream, 0)
     kernel_ms = ev0.elapsed_time(ev1) / K  # HIP events on the stream the kernel runs on
 
-    # ---- the same K steps once more, each bracketed by its own pair of events: the median beside the mean
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(K)]
-    for i, (a, b) in enumerate(evs):
-        a.record()
-        step(W + i)
-        b.record()
-    torch.cuda.synchronize()
-    per_step = sorted(a.elapsed_time(b) for a, b in evs)
-    kernel_ms_median = per_step[len(per_step) // 2]
-
-    # ---- work census of the timed batches (same kernel, TALLY variant, untimed)
-    for i in range(K):
-        ix.dev_count_nt2_tally(batches[(W + i) % n_batches].data_ptr(), nq, L, counts.data_ptr(), tally.data_ptr(), True, stream, 0)
-    torch.cuda.synchronize()
-    tl = [int(x) / K for x in tally.cpu().tolist()]
-    probes, steps_exec, blocks, vsa, vtxt = tl[:5]
-    # probe 16 B, block 104 B, query 8 B, result 8 B; seed-and-verify (survivors only): 8 B per SA read
-    # and the <= 8 B text window of the remaining letters; left-context index: 32 B per node consulted, 8 B per entry read
-    alg_bytes = 16.0 * probes + 104.0 * blocks + nq * (8.0 + 8.0) + 8.0 * vsa + 8.0 * vtxt + lcx_price(tl)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, counts)
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
     if world > 1:
@@ -964,22 +977,43 @@ def main():
                    "seed_k": ix.seed_kmer_len(), "left_context_index": bool(ix.lcx_enabled()),
                    "sharding": "index replicated per GPU (built once, handed over as .awry v1), queries sharded by rank, no collective",
                    "ranks": world, "backend": ("rccl (torch.distributed nccl)" if backend == "nccl" else backend) if world > 1 else None},
-        "roofline": {"bound": "hbm", "kernel": ix.count_schedule(L), "achieved": alg_bytes / (kernel_ms * 1e-3) / 1e9,
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": alg_bytes / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "traffic": None, "kernel_ms": kernel_ms, "kernel_ms_median_of_%d" % K: kernel_ms_median,
-                     "queries_per_s_at_median": nq / (kernel_ms_median * 1e-3), "algorithmic_bytes_per_launch": alg_bytes,
-                     # the device's seed entry is 8 bytes, SURVEY 8(d) prices a probe at 16: the same fraction on the bytes actually needed
-                     "frac_at_8_byte_probe": (alg_bytes - 8.0 * probes) / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "census_per_launch": {"seed_probes": probes, "steps": steps_exec, "block_reads": blocks,
-                                           "verify_sa_reads": vsa, "verify_text_windows": vtxt, "lcx_nodes": tl[6], "lcx_entries": tl[7]}},
     }
-    # the ceiling that actually binds this access pattern: random 128-B line requests (profiles/r01_gather_calibration.txt)
-    lines = probes + blocks + vsa + vtxt + tl[6] + tl[7] + nq * (8.0 + 8.0) / 128.0
-    result["roofline"]["random_line_rate"] = {"achieved_Glines_s": lines / (kernel_ms * 1e-3) / 1e9, "measured_ceiling_Glines_s": 48.0,
-                                              "note": "seed probe + ranked blocks + verify SA reads and text windows + coalesced share of query/result words; ceiling = "
-                                                      "tools/calib_gather.hip: 8-B probes into a 34-137 GiB table (53 on 2 GiB; 44 when whole 128-B lines are consumed)"}
+    if args.full:
+        # ---- the same K steps once more, each bracketed by its own pair of events: the median beside the mean
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(K)]
+        for i, (a, b) in enumerate(evs):
+            a.record()
+            step(W + i)
+            b.record()
+        torch.cuda.synchronize()
+        per_step = sorted(a.elapsed_time(b) for a, b in evs)
+        kernel_ms_median = per_step[len(per_step) // 2]
 
-    if rank == 0:
+        # ---- work census of the timed batches (same kernel, TALLY variant, untimed)
+        for i in range(K):
+            ix.dev_count_nt2_tally(batches[(W + i) % n_batches].data_ptr(), nq, L, counts.data_ptr(), tally.data_ptr(), True, stream, 0)
+        torch.cuda.synchronize()
+        tl = [int(x) / K for x in tally.cpu().tolist()]
+        probes, steps_exec, blocks, vsa, vtxt = tl[:5]
+        # probe 16 B, block 104 B, query 8 B, result 8 B; seed-and-verify (survivors only): 8 B per SA read
+        # and the <= 8 B text window of the remaining letters; left-context index: 32 B per node consulted, 8 B per entry read
+        alg_bytes = 16.0 * probes + 104.0 * blocks + nq * (8.0 + 8.0) + 8.0 * vsa + 8.0 * vtxt + lcx_price(tl)
+
+        result["roofline"] = {"bound": "hbm", "kernel": ix.count_schedule(L), "achieved": alg_bytes / (kernel_ms * 1e-3) / 1e9,
+                              "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": alg_bytes / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                              "traffic": None, "kernel_ms": kernel_ms, "kernel_ms_median_of_%d" % K: kernel_ms_median,
+                              "queries_per_s_at_median": nq / (kernel_ms_median * 1e-3), "algorithmic_bytes_per_launch": alg_bytes,
+                              # the device's seed entry is 8 bytes, SURVEY 8(d) prices a probe at 16: the same fraction on the bytes actually needed
+                              "frac_at_8_byte_probe": (alg_bytes - 8.0 * probes) / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                              "census_per_launch": {"seed_probes": probes, "steps": steps_exec, "block_reads": blocks,
+                                                    "verify_sa_reads": vsa, "verify_text_windows": vtxt, "lcx_nodes": tl[6], "lcx_entries": tl[7]}}
+        # the ceiling that actually binds this access pattern: random 128-B line requests (profiles/r01_gather_calibration.txt)
+        lines = probes + blocks + vsa + vtxt + tl[6] + tl[7] + nq * (8.0 + 8.0) / 128.0
+        result["roofline"]["random_line_rate"] = {"achieved_Glines_s": lines / (kernel_ms * 1e-3) / 1e9, "measured_ceiling_Glines_s": 48.0,
+                                                  "note": "seed probe + ranked blocks + verify SA reads and text windows + coalesced share of query/result words; ceiling = "
+                                                          "tools/calib_gather.hip: 8-B probes into a 34-137 GiB table (53 on 2 GiB; 44 when whole 128-B lines are consumed)"}
+
+    if rank == 0 and args.full:
         # nominal peak next to a measured streaming figure: a HIP copy kernel, 16 B per lane per step, read + write bytes
         a = torch.empty(1 << 30, dtype=torch.uint8, device=dev)
         b = torch.empty_like(a)
@@ -993,7 +1027,7 @@ def main():
         result["roofline"]["peak_measured_stream_copy"] = 10 * 2 * a.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
         del a, b
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         oi, cores = None, 1
         if args.cpu_seconds > 0:
             from oracle import oracle_ffi
@@ -1123,8 +1157,10 @@ def main():
             if "amino" in result:
                 for name in ("random", "present"):
                     attach_traffic(result["amino"][name], result["amino"][name]["kernel_ms"], pmc, "amino_" + name)
+    elif world == 1:
+        ix.close()
 
-    if world > 1:
+    if world > 1 and args.full:
         # parity re-checked at every G, outside the timed region.  All ranks count one common batch (half
         # k-mers of the text, half random; made by rank 0, which holds the text, and broadcast) twice: with the default
         # schedule (seed table, context and position seeds, left-context index, text comparison) and by plain backward search
@@ -1206,7 +1242,7 @@ def main():
 
     if world > 1:
         dist.barrier()
-        if rank == 0 and default_config:  # every GPU runs the single-GPU kernel on its own replica: the committed single-GPU passes
+        if rank == 0 and default_config and args.full:  # every GPU runs the single-GPU kernel on its own replica: the committed single-GPU passes
             attach_traffic(result["roofline"], kernel_ms, committed_traffic(), "headline")
     if rank == 0:
         shutil.rmtree(tmpdir, ignore_errors=True)

@@ -1,4 +1,4 @@
-"""bench.py's host logic that needs no GPU: cutting a rocprofv3 counter pass into phases by the marker kernels."""
+"""bench.py's host logic that needs no GPU: cutting a rocprofv3 counter pass into phases by the marker kernels; the sample --dump-outputs writes."""
 import csv
 import os
 import sys
@@ -47,3 +47,13 @@ def test_attach_traffic_units():
     e = bench.attach_traffic({}, 2.0, pmc, "x")  # 8 GB in 2 ms = 4 TB/s = half of the 8 TB/s peak
     assert abs(e["traffic_GBs"] - 4000.0) < 1e-6 and abs(e["traffic_frac_of_peak"] - 0.5) < 1e-9 and e["l2_hit_rate"] == 0.25
     assert bench.attach_traffic({}, 2.0, pmc, "missing")["traffic"] is None
+
+
+def test_dump_sample_is_fixed_bounded_and_complete_for_small_batches():
+    import numpy as np
+    small = bench.dump_sample_index(1000)
+    assert np.array_equal(small, np.arange(1000))
+    a, b = bench.dump_sample_index(10_000_000), bench.dump_sample_index(10_000_000)
+    assert np.array_equal(a, b) and len(a) == bench.DUMP_SAMPLE
+    assert a[0] >= 0 and a[-1] < 10_000_000 and bool(np.all(np.diff(a) > 0))
+    assert 2 * 8 * len(a) <= 64 << 20  # counts and positions, float64 each

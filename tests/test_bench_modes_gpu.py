@@ -37,7 +37,7 @@ def test_one_process_per_gpu_mode_rehearsed_with_gloo():
     env.pop("AWRY_HOST_THREADS", None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "ecoli",
-                        "--steps", "5", "--warmup", "1"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "--steps", "5", "--warmup", "1", "--full"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     r = _json_line(p.stdout)
     assert r["n_gpus"] == 2 and r["scaling"] == "strong" and r["value"] > 0
@@ -57,8 +57,53 @@ def test_explicit_batch_size_keeps_weak_scaling_label():
     env = dict(os.environ, AWRY_BENCH_BACKEND="gloo", AWRY_SEED_K="11", MASTER_ADDR="127.0.0.1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29633", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "ecoli", "--queries", "500000",
-                        "--steps", "3", "--warmup", "1", "--cpu-seconds", "0"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--full"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     r = _json_line(p.stdout)
     assert r["n_gpus"] == 2 and r["scaling"] == "weak" and r["config"]["queries_per_gpu_per_step"] == 500_000
     assert r["parity_check"]["rank0_gpu_matches_oracle_on_the_common_batch"] is None  # --cpu-seconds 0: no oracle in the run
+
+
+def test_plain_run_dumps_the_last_timed_step(tmp_path):
+    """the plain line (no --full) holds the headline and nothing measured besides it; --dump-outputs writes the counts of the
+    last timed step, a fixed sample of them for a batch above DUMP_SAMPLE, identical from run to run and equal to the
+    oracle's counts of the same queries (12-mers on the E. coli-scale text: about a quarter of them occur)"""
+    import numpy as np
+    import torch
+
+    import bench
+    from oracle import oracle_ffi
+    from tests import synth
+    nq, L, K, W = 2_500_000, 12, 4, 2
+    outs = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "ecoli", "--queries", str(nq), "--qlen", str(L),
+                            "--steps", str(K), "--warmup", str(W), "--dump-outputs", str(d)],
+                           cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        r = _json_line(p.stdout)
+        assert r["steps"] == K and r["warmup"] == W and r["ms_per_step"] > 0 and r["value"] > 0
+        assert abs(r["value"] - nq / (r["ms_per_step"] * 1e-3)) <= 1e-6 * r["value"]
+        assert r["unit"] == "queries/s" and r["higher_is_better"] is True and r["dtype"] == "u64"
+        assert not {"roofline", "cpu_baseline", "variants", "locate", "amino", "pmc_phases"} & set(r)
+        files = sorted(os.listdir(d))
+        assert files == ["counts.npy", "query_index.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        c, ix = np.load(d / "counts.npy"), np.load(d / "query_index.npy")
+        assert c.dtype == np.float64 and ix.dtype == np.float64 and len(c) == len(ix) == bench.DUMP_SAMPLE
+        outs.append((c, ix))
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
+    # the same queries as the bench's last timed step (batch (W + K - 1) mod its batch count), counted by the oracle
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    n_batches = min(K + W, 8)
+    batches = [torch.randint(0, 1 << (2 * L), (nq,), dtype=torch.int64, device=dev, generator=gen) for _ in range(n_batches)]
+    c, ix = outs[0]
+    words = batches[(W + K - 1) % n_batches].cpu().numpy().view(np.uint64)[ix.astype(np.int64)]
+    text, starts, headers, _ = bench.workload_text(None, torch, dev, "ecoli")
+    oi = oracle_ffi.OracleIndex.from_text(text, oracle_ffi.NUCLEOTIDE, 8, 0, starts, headers)
+    want, _ = oi.parallel_count(*synth.fixed_to_csr(bench.unpack_nt2(words, L)), 8)
+    oi.close()
+    assert np.array_equal(c, want.astype(np.float64)) and int((c > 0).sum()) > len(c) // 10

@@ -6,7 +6,7 @@ TAG=${1:-r01}; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-ARGS="--steps 10 --warmup 2 --cpu-seconds 0 --no-variants $*"
+ARGS="--full --steps 10 --warmup 2 --cpu-seconds 0 --no-variants $*"
 cd "$GRAFT_REPO_ROOT"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py $ARGS > "$OUT/bench_trace.json" 2> "$OUT/bench_trace.log" || { echo "trace run failed"; tail -20 "$OUT/bench_trace.log"; exit 1; }
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -- python3 bench.py $ARGS > "$OUT/bench_fetch.json" 2> "$OUT/bench_fetch.log" || { echo "fetch pmc failed"; tail -20 "$OUT/bench_fetch.log"; exit 1; }
