@@ -236,6 +236,9 @@ struct Replica {
   std::map<hipStream_t, std::unique_ptr<SurvScratch>> scratch;
   int seed_k = 0;
   int num_cus = 256;
+  // blocks of count_nt2_probe_resume_kernel<TALLY, VERIFY> resident per CU, by [2 * TALLY + VERIFY] (the occupancy query of
+  // each instantiation, at replica creation): its grid, and the number of survivor lists two_phase_lists sizes
+  int probe_resume_per_cu[4] = {8, 8, 8, 8};
   DevIndex dev{};
   ~Replica() {
     if (device >= 0) {
@@ -285,7 +288,9 @@ int grid_for(const Replica& r, uint64_t work_items, int per_block, int blocks_pe
   return (int)std::max<uint64_t>(1, std::min(want, cap));
 }
 
-// which instantiation serves awry_dev_count_nt2: 0 strided quads, 1 LDS-staged chunks, 2 groups of four
+// which instantiation serves awry_dev_count_nt2: 0 strided quads, 1 LDS-staged chunks, 2 groups of four, 3 two-phase,
+// 4 two-phase with the k-mer probe and resume passes as two launches on num_cus * 8 blocks (the schedule before the one
+// launch), 5 the same two launches on the one launch's grid (for A/B of fusion and grid size; other paths treat 4, 5 as 3)
 std::atomic<int> g_count_kernel{-1};
 // -1: no explicit choice (env / policy)
 int count_kernel_override() {
@@ -652,6 +657,15 @@ std::unique_ptr<Replica> make_replica(awry_index* ix, int device) {
   hipDeviceProp_t prop;
   HIP_CHECK(hipGetDeviceProperties(&prop, device));
   r->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  {
+    const void* fused[4] = {(const void*)count_nt2_probe_resume_kernel<false, false>, (const void*)count_nt2_probe_resume_kernel<false, true>,
+                            (const void*)count_nt2_probe_resume_kernel<true, false>, (const void*)count_nt2_probe_resume_kernel<true, true>};
+    for (int i = 0; i < 4; i++) {
+      int per_cu = 0;
+      HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused[i], 256, 0));
+      r->probe_resume_per_cu[i] = std::max(1, std::min(per_cu, 8));
+    }
+  }
   HIP_CHECK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
   for (auto& ls : r->lane_stream) HIP_CHECK(hipStreamCreateWithFlags(&ls, hipStreamNonBlocking));
   HIP_CHECK(hipStreamCreateWithFlags(&r->copy_in, hipStreamNonBlocking));
@@ -992,11 +1006,11 @@ bool lcx_lanes(const Replica& r) {
 // against 16.5 G/s and reads from the text 10 % slower than the single strided quad kernel: without the 32-bit accelerators
 // (dense SA, text, position seeds) the entry settles too few queries for a second launch to pay.  Selected with
 // AWRY_COUNT_KERNEL=twophase / awry_debug_set_count_kernel(3).
-bool wide_two_phase(uint64_t n) { return count_kernel_override() == 3 && n < (1ull << 32); }
-// the survivor lists of a two-phase launch over n queries: `in` (all three arrays) and, with lanes, the fallback lists `out`
-void two_phase_lists(Replica& r, hipStream_t s, uint64_t n, bool lanes, Nt2Survivors* in, Nt2Survivors* out, unsigned* nblk_out) {
+bool wide_two_phase(uint64_t n) { const int m = count_kernel_override(); return m >= 3 && m <= 5 && n < (1ull << 32); }
+// the survivor lists of a two-phase launch over n queries on a grid of nblk <= num_cus * 8 blocks (one list per block):
+// `in` (all three arrays) and, with lanes, the fallback lists `out`
+void two_phase_lists(Replica& r, hipStream_t s, uint64_t n, unsigned nblk, bool lanes, Nt2Survivors* in, Nt2Survivors* out) {
   Replica::SurvScratch* sc = surv_scratch(r, s);
-  const unsigned nblk = (unsigned)r.num_cus * 8;  // lists = blocks of the probe pass
   const uint64_t per_block = ((n + (uint64_t)nblk * 256 - 1) / ((uint64_t)nblk * 256)) * 256, total = per_block * nblk;
   if (sc->cap < total || (lanes && sc->fcap < total)) {
     HIP_CHECK(hipStreamSynchronize(s));
@@ -1010,7 +1024,7 @@ void two_phase_lists(Replica& r, hipStream_t s, uint64_t n, bool lanes, Nt2Survi
       sc->fcap = total;
     }
   }
-  if (!sc->count.p) sc->count.alloc(nblk);
+  if (!sc->count.p) sc->count.alloc((size_t)r.num_cus * 8);
   if (lanes && !sc->fcount.p) sc->fcount.alloc(8);  // [0] length of the LF list
   *in = Nt2Survivors{sc->w.p, sc->range.p, sc->q.p, sc->count.p, per_block};
   *out = Nt2Survivors{};
@@ -1018,7 +1032,6 @@ void two_phase_lists(Replica& r, hipStream_t s, uint64_t n, bool lanes, Nt2Survi
     *out = Nt2Survivors{sc->fw.p, sc->frange.p, sc->fq.p, sc->fcount.p, total};
     in->lf_count = sc->fcount.p;
   }
-  *nblk_out = nblk;
 }
 // blocks of lcx_quad_kernel that are resident at once: its grid (the pool of survivors is shared out dynamically)
 template <class K>
@@ -1039,8 +1052,8 @@ void launch_count_nt2_long(Replica& r, const uint64_t* d_words, uint64_t n, int 
     const dim3 gw(grid_for(r, n * 4, 256)), bw(256);
     if (sdw && wide_two_phase(n)) {  // per-lane probe pass, then the quads on what has to be stepped
       Nt2Survivors sv, fb;
-      unsigned nblk = 0;
-      two_phase_lists(r, s, n, false, &sv, &fb, &nblk);
+      const unsigned nblk = (unsigned)r.num_cus * 8;
+      two_phase_lists(r, s, n, nblk, false, &sv, &fb);
       if (d_lens) {
         hipLaunchKernelGGL((count_nt2_wide_probe_kernel<true, false>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens, (unsigned long long*)nullptr);
         hipLaunchKernelGGL((count_nt2_wide_kernel<true, true, true>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, d_lens, (unsigned long long*)nullptr, sv);
@@ -1062,13 +1075,13 @@ void launch_count_nt2_long(Replica& r, const uint64_t* d_words, uint64_t n, int 
   const bool vfy = r.dev.text4 && r.dev.dense_ratio == 1;
   const dim3 g(grid_for(r, n * 4, 256)), b(256);
   const int om = count_kernel_override();
-  if (vfy && sd && L - r.seed_k >= 3 && L <= 512 && n < (1ull << 32) && (om < 0 || om == 3)) {
+  if (vfy && sd && L - r.seed_k >= 3 && L <= 512 && n < (1ull << 32) && (om < 0 || (om >= 3 && om <= 5))) {
     // two-phase: a per-lane pass settles the reads their seed entry (plus one SA read and one text window) decides,
     // the quad kernel works through the rest
     const bool lanes = lcx_lanes(r);
     Nt2Survivors sv, fb;
-    unsigned nblk = 0;  // both phases of the quad schedule use this grid
-    two_phase_lists(r, s, n, lanes, &sv, &fb, &nblk);
+    const unsigned nblk = (unsigned)r.num_cus * 8;  // both phases of the quad schedule use this grid
+    two_phase_lists(r, s, n, nblk, lanes, &sv, &fb);
     if (!lanes) sv.w = sv.range = nullptr;  // (the probe pass then lists the reads only)
     const dim3 gq((unsigned)r.num_cus * 8);  // the quad code over what the lanes left
     if (d_lens) {
@@ -1111,8 +1124,8 @@ void launch_count_nt2(Replica& r, const uint64_t* d_words, uint64_t n, int L, ui
     const dim3 gw(grid_for(r, n * 4, 256)), bw(256);
     if (sdw && wide_two_phase(n)) {
       Nt2Survivors sv, fb;
-      unsigned nblk = 0;
-      two_phase_lists(r, s, n, false, &sv, &fb, &nblk);
+      const unsigned nblk = (unsigned)r.num_cus * 8;
+      two_phase_lists(r, s, n, nblk, false, &sv, &fb);
       if (d_tally) hipLaunchKernelGGL((count_nt2_wide_probe_kernel<false, true>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, (uint64_t*)nullptr, sv, (const uint32_t*)nullptr, d_tally);
       else hipLaunchKernelGGL((count_nt2_wide_probe_kernel<false, false>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, (uint64_t*)nullptr, sv, (const uint32_t*)nullptr, d_tally);
       hipLaunchKernelGGL((count_nt2_wide_kernel<true, false, true>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, (uint64_t*)nullptr, (const uint32_t*)nullptr, d_tally, sv);
@@ -1149,19 +1162,24 @@ void launch_count_nt2(Replica& r, const uint64_t* d_words, uint64_t n, int L, ui
     HIP_CHECK(hipGetLastError());
     return;
   }
-  if (kmode == 3 && seeded && n < (1ull << 32)) {
-    // two-phase: per-lane seed probes decide most queries, the quad machinery resumes the survivors
-    Nt2Survivors sv, fb;
-    unsigned nblk = 0;  // both phases use this grid
-    two_phase_lists(r, s, n, false, &sv, &fb, &nblk);
-    const dim3 gp(nblk);
+  if (kmode >= 3 && kmode <= 5 && seeded && n < (1ull << 32)) {
+    // two-phase: per-lane seed probes decide most queries, the quad machinery resumes the survivors -- in one launch on
+    // the resident grid, or (modes 4 and 5, for A/B) as the probe and resume kernels on num_cus * 8 blocks / that grid.
+    // The one launch takes the survivor count from LDS and leaves sv.count untouched.
     // survivors of phase 1 use seed-and-verify whenever its accelerators are resident (cheap: random batches barely
     // reach phase 2); the single-kernel schedules use it only on request (awry_set_verify_kmers)
     const bool vfy = r.dev.text4 != nullptr && r.dev.dense_ratio == 1;
-#define AWRY_LAUNCH_TWO_PHASE(T, V)                                                                                 \
-  do {                                                                                                             \
-    hipLaunchKernelGGL((count_nt2_probe_kernel<T, V>), gp, b, 0, s, dv, d_words, n, L, d_counts, sv, d_tally);     \
-    hipLaunchKernelGGL((count_nt2_resume_kernel<T, V>), gp, b, 0, s, dv, sv, L, d_counts, d_tally);                \
+    const bool pair = kmode != 3;
+    const unsigned nblk = (unsigned)r.num_cus * (kmode == 4 ? 8u : (unsigned)r.probe_resume_per_cu[2 * (d_tally != nullptr) + vfy]);
+    Nt2Survivors sv, fb;
+    two_phase_lists(r, s, n, nblk, false, &sv, &fb);
+    const dim3 gp(nblk);
+#define AWRY_LAUNCH_TWO_PHASE(T, V)                                                                                   \
+  do {                                                                                                               \
+    if (pair) {                                                                                                      \
+      hipLaunchKernelGGL((count_nt2_probe_kernel<T, V>), gp, b, 0, s, dv, d_words, n, L, d_counts, sv, d_tally);     \
+      hipLaunchKernelGGL((count_nt2_resume_kernel<T, V>), gp, b, 0, s, dv, sv, L, d_counts, d_tally);                \
+    } else hipLaunchKernelGGL((count_nt2_probe_resume_kernel<T, V>), gp, b, 0, s, dv, d_words, n, L, d_counts, sv, d_tally); \
   } while (0)
     if (d_tally) { if (vfy) AWRY_LAUNCH_TWO_PHASE(true, true); else AWRY_LAUNCH_TWO_PHASE(true, false); }
     else { if (vfy) AWRY_LAUNCH_TWO_PHASE(false, true); else AWRY_LAUNCH_TWO_PHASE(false, false); }
@@ -1169,7 +1187,7 @@ void launch_count_nt2(Replica& r, const uint64_t* d_words, uint64_t n, int L, ui
     HIP_CHECK(hipGetLastError());
     return;
   }
-  if (kmode == 2 || kmode == 3) {  // groups of 4 consecutive queries per quad: whole-sector result writes
+  if (kmode >= 2 && kmode <= 5) {  // groups of 4 consecutive queries per quad: whole-sector result writes
     const dim3 g4(grid_for(r, n, 256));
     const bool verify = r.verify_kmers && r.dev.text4 != nullptr && r.dev.dense_ratio == 1;
 #define AWRY_LAUNCH_QUAD4(S, T, V) hipLaunchKernelGGL((count_nt2_quad4_kernel<S, T, V>), g4, b, 0, s, r.dev, d_words, n, L, d_counts, d_tally)
@@ -2485,10 +2503,11 @@ void prewarm_host_paths(Replica& r) {
     // scratch of the two-phase schedules on the lane streams (survivor lists of a full chunk)
     for (int li = 0; li < Replica::NLANES; li++) {
       Replica::SurvScratch* sc = surv_scratch(r, r.lane_stream[li]);
-      const unsigned nblk = (unsigned)r.num_cus * 8;
-      const uint64_t per_block = ((cap + (uint64_t)nblk * 256 - 1) / ((uint64_t)nblk * 256)) * 256, total = per_block * nblk;
+      uint64_t total = 0;  // for the grid of the one-launch k-mer schedule and for num_cus * 8 blocks
+      for (const unsigned nblk : {(unsigned)r.num_cus * (unsigned)r.probe_resume_per_cu[1], (unsigned)r.num_cus * 8})
+        total = std::max<uint64_t>(total, ((cap + (uint64_t)nblk * 256 - 1) / ((uint64_t)nblk * 256)) * 256 * nblk);
       if (sc->cap < total) { sc->w.alloc(total); sc->range.alloc(total); sc->q.alloc(total); sc->cap = sc->cap_q = total; }
-      if (!sc->count.p) sc->count.alloc(nblk);
+      if (!sc->count.p) sc->count.alloc((size_t)r.num_cus * 8);
       if (!sc->counters.p) sc->counters.alloc(8);
     }
   }
@@ -2640,22 +2659,23 @@ int awry_debug_force_wide_rows(int on) { g_force_wide.store(on ? 1 : 0); return 
 
 const char* awry_count_schedule(const awry_index_t* idx, int L) {
   static const char* names[] = {"count_nt2_quad_kernel", "count_nt2_chunk_kernel", "count_nt2_quad4_kernel",
+                                "count_nt2_probe_resume_kernel", "count_nt2_probe_kernel+count_nt2_resume_kernel",
                                 "count_nt2_probe_kernel+count_nt2_resume_kernel"};
   if (!idx || idx->reps.empty()) return "";
   const Replica& r = *idx->reps[0];
-  if (r.wide) return count_kernel_override() == 3 && r.seed_k > 0 && r.seed_k <= L ? "count_nt2_wide_probe_kernel+count_nt2_wide_kernel" : "count_nt2_wide_kernel";
+  if (r.wide) return wide_two_phase(1) && r.seed_k > 0 && r.seed_k <= L ? "count_nt2_wide_probe_kernel+count_nt2_wide_kernel" : "count_nt2_wide_kernel";
   const bool seeded = r.seed_k > 0 && r.seed_k <= L;
   if (L > 32) {  // launch_count_nt2_long
     const int om = count_kernel_override();
-    const bool two = r.dev.text4 && r.dev.dense_ratio == 1 && seeded && L - r.seed_k >= 3 && L <= 512 && (om < 0 || om == 3);
+    const bool two = r.dev.text4 && r.dev.dense_ratio == 1 && seeded && L - r.seed_k >= 3 && L <= 512 && (om < 0 || (om >= 3 && om <= 5));
     return two ? "count_nt2_reads_probe_kernel+count_nt2_reads_kernel" : "count_nt2_reads_kernel";
   }
   static const bool rungs_off = getenv("AWRY_SEED_RUNGS") && !strcmp(getenv("AWRY_SEED_RUNGS"), "0");
   if (!seeded && r.seed_k > L && L >= SEED_RUNG_MIN && !rungs_off && count_kernel_override() < 0)
-    return "count_nt2_probe_kernel+count_nt2_resume_kernel (table of its own for this length; batches of 4096 queries and more)";
+    return "count_nt2_probe_resume_kernel (table of its own for this length; batches of 4096 queries and more)";
   int m = count_kernel_mode(r.dev.bwt_len, r.seed_k, seeded);
-  if (m == 3 && !seeded) m = 2;
-  return names[m & 3];
+  if (m >= 3 && m <= 5 && !seeded) m = 2;
+  return names[m >= 0 && m <= 5 ? m : 0];  // (other modes launch the strided quads)
 }
 
 int awry_seed_kmer_len(const awry_index_t* idx) { return idx && !idx->reps.empty() ? idx->reps[0]->seed_k : 0; }
