@@ -86,6 +86,12 @@ def load_library():
     sig("awry_count_packed_kmers", i32, vp, u64p, u64, i32, u64p)
     sig("awry_locate_batch", i32, vp, vp, u64p, u64, C.POINTER(u64p), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p))
     sig("awry_free_buffer", None, vp)
+    sig("awry_count_mismatch_batch", i32, vp, vp, u64p, u64, i32, u64p)
+    sig("awry_locate_mismatch_batch", i32, vp, vp, u64p, u64, i32, C.POINTER(u64p), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p),
+        C.POINTER(u8p))
+    sig("awry_dev_count_mismatch", i32, vp, i32, vp, vp, u64, i32, vp, vp, vp)
+    sig("awry_dev_count_mismatch_tally", i32, vp, i32, vp, vp, u64, i32, vp, vp, vp, vp)
+    sig("awry_debug_rank_all", i32, vp, i32, vp, u64, vp, vp)
     sig("awry_count", i32, vp, vp, u64, u64p)
     sig("awry_search_range", i32, vp, vp, u64, C.POINTER(Range))
     sig("awry_locate", i32, vp, vp, u64, C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), u64p)

@@ -17,7 +17,7 @@ SO = os.path.join(LIBDIR, "libawry_hip.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 SOURCES = ["awry_hip.hip", "sa_builder.hip", "host_index.cpp", "host_pack.cpp"]
-HEADERS = ["kernels.hip.h", "layout.h", "alphabet.h", "host_index.h", "host_pack.h", "sais.hpp", os.path.join("..", "..", "include", "awry_hip.h")]
+HEADERS = ["kernels.hip.h", "mismatch_kernels.hip.h", "layout.h", "alphabet.h", "host_index.h", "host_pack.h", "sais.hpp", os.path.join("..", "..", "include", "awry_hip.h")]
 
 
 def stale():

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
@@ -29,6 +30,7 @@
 #include "host_index.h"
 #include "host_pack.h"
 #include "kernels.hip.h"
+#include "mismatch_kernels.hip.h"
 #include "sais.hpp"
 
 using namespace awry;
@@ -2321,6 +2323,141 @@ int checked_symbol(const awry_index* ix, uint8_t ascii) {
   return index_of_ascii(ix->host.alphabet, ascii);
 }
 
+// ---- substitution-tolerant count / locate (mismatch_kernels.hip.h) ----------------------------------------
+
+void require_mismatches(int k) {
+  if (k < 0 || k > MM_MAX_K) throw ArgError("max_mismatches must be 0, 1 or 2");
+}
+
+// the DFS kernel on a resident grid (lanes draw queries from the work-queue head).  EMIT: the locate pass that writes the
+// leaves of query q to key / val [leaf_off[q], leaf_off[q + 1])
+void launch_count_mismatch(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, int k, uint64_t* d_counts, uint64_t* d_totals,
+                           uint64_t* d_nleaves, uint8_t* d_status, hipStream_t s, unsigned long long* d_tally = nullptr,
+                           const uint64_t* d_leaf_off = nullptr, uint64_t* d_key = nullptr, uint64_t* d_val = nullptr) {
+  if (n == 0) return;
+  unsigned long long* ctr = next_counter(r, s);
+  const bool emit = d_leaf_off != nullptr;
+  const uint64_t want = (n + 255) / 256;
+  auto launch = [&](auto kernel) {
+    const dim3 g((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, resident_grid(r, kernel)))), b(256);
+    hipLaunchKernelGGL(kernel, g, b, 0, s, r.dev, d_q, d_off, n, k, d_counts, d_totals, d_nleaves, d_status, d_leaf_off, d_key, d_val, ctr, d_tally);
+  };
+  if (r.dev.alphabet == NUCLEOTIDE) {
+    if (emit) launch(count_mismatch_kernel<NUCLEOTIDE, true>); else launch(count_mismatch_kernel<NUCLEOTIDE, false>);
+  } else {
+    if (emit) launch(count_mismatch_kernel<AMINO, true>); else launch(count_mismatch_kernel<AMINO, false>);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// upload one chunk's query bytes and chunk-relative offsets (the generic count path's layout)
+void upload_chunk(Replica& r, ChunkBuffers& cb, const uint8_t* qbytes, const uint64_t* qoff, Shard c) {
+  const uint64_t n = c.hi - c.lo, base = qoff[c.lo], nbytes = qoff[c.hi] - base;
+  cb.h_off.resize(n + 1);
+  for (uint64_t i = 0; i <= n; i++) {
+    if (qoff[c.lo + i] < base || (i && qoff[c.lo + i] < qoff[c.lo + i - 1])) throw ArgError("query offsets must be non-decreasing");
+    cb.h_off[i] = qoff[c.lo + i] - base;
+  }
+  if (cb.q.n < nbytes + 16) cb.q.alloc(nbytes + 16);
+  if (cb.off.n < n + 1) cb.off.alloc(n + 1);
+  if (cb.status.n < n) cb.status.alloc(n);
+  if (nbytes) HIP_CHECK(hipMemcpyAsync(cb.q.p, qbytes + base, nbytes, hipMemcpyHostToDevice, r.stream));
+  HIP_CHECK(hipMemcpyAsync(cb.off.p, cb.h_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, r.stream));
+  cb.h_status.resize(n);
+}
+
+void count_mismatch_shard(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard sh, int k, uint64_t* counts_out) {
+  HIP_CHECK(hipSetDevice(r.device));
+  ChunkBuffers cb;
+  for (Shard c : chunk_queries(qoff, sh.lo, sh.hi)) {
+    const uint64_t n = c.hi - c.lo, w = (uint64_t)(k + 1);
+    upload_chunk(r, cb, qbytes, qoff, c);
+    if (cb.counts.n < n * w) cb.counts.alloc(n * w);
+    launch_count_mismatch(r, cb.q.p, cb.off.p, n, k, cb.counts.p, nullptr, nullptr, cb.status.p, r.stream);
+    HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, r.stream));
+    HIP_CHECK(hipMemcpyAsync(counts_out + c.lo * w, cb.counts.p, n * w * 8, hipMemcpyDeviceToHost, r.stream));
+    HIP_CHECK(hipStreamSynchronize(r.stream));
+    check_status(cb, c.lo);
+  }
+}
+
+// Leaves (row ranges of the variants that occur) a locate chunk may hold on the device; a chunk with more is split in halves
+// and each half redone (one query with more gets what it needs).  Read per call: AWRY_MISMATCH_LEAF_CAP (tests shrink it).
+uint64_t mismatch_leaf_cap() {
+  const char* e = getenv("AWRY_MISMATCH_LEAF_CAP");
+  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
+  return v ? std::min<uint64_t>(v, 1ull << 31) : (1ull << 26);
+}
+
+struct MismatchHits {  // one shard's locate result, in query order
+  std::vector<uint64_t> counts;  // hits per query
+  std::vector<uint64_t> gpos;
+  std::vector<awry_pos_t> pos;
+  std::vector<uint8_t> mm;
+};
+
+// pass 1 (counts, leaves per query), scans, pass 2 (leaves), segmented sort by first row within each query, locate over the
+// flat leaf list, distances per hit.  false: the chunk holds more leaves than the cap and more than one query -- nothing appended
+bool locate_mismatch_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, bool want_pos, bool want_gpos, bool want_mm,
+                           MismatchHits& out) {
+  const hipStream_t s = r.stream;
+  const uint64_t n = c.hi - c.lo;
+  ChunkBuffers cb;
+  upload_chunk(r, cb, qbytes, qoff, c);
+  DevBuf<uint64_t> totals(n), nleaves(n), hit_off(n + 1), leaf_off(n + 1), scratch(scan_tiles(n) + 1);
+  launch_count_mismatch(r, cb.q.p, cb.off.p, n, k, nullptr, totals.p, nleaves.p, cb.status.p, s);
+  launch_scan(r, totals.p, n, hit_off.p, scratch.p, s);
+  uint64_t total = 0, nleaf = 0;
+  HIP_CHECK(hipMemcpyAsync(&total, hit_off.p + n, 8, hipMemcpyDeviceToHost, s));
+  launch_scan(r, nleaves.p, n, leaf_off.p, scratch.p, s);
+  HIP_CHECK(hipMemcpyAsync(&nleaf, leaf_off.p + n, 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  check_status(cb, c.lo);
+  if (nleaf > mismatch_leaf_cap() && n > 1) return false;
+  require(nleaf < (1ull << 32), "one query has 2^32 or more occurring variants");
+  const size_t at_q = out.counts.size(), at_h = out.gpos.size();
+  out.counts.resize(at_q + n);
+  HIP_CHECK(hipMemcpyAsync(out.counts.data() + at_q, totals.p, n * 8, hipMemcpyDeviceToHost, s));
+  if (total) {
+    DevBuf<uint64_t> key(nleaf), val(nleaf), key2(nleaf), val2(nleaf), width(nleaf), leaf_hit_off(nleaf + 1), lscratch(scan_tiles(nleaf) + 1);
+    launch_count_mismatch(r, cb.q.p, cb.off.p, n, k, nullptr, nullptr, nullptr, nullptr, s, nullptr, leaf_off.p, key.p, val.p);
+    // DFS from the right end does not visit the leaves in row order: sort each query's leaves by their first row
+    unsigned end_bit = 1;
+    while (end_bit < 64 && (r.dev.bwt_len >> end_bit)) end_bit++;
+    size_t tmp_bytes = 0;
+    HIP_CHECK(rocprim::segmented_radix_sort_pairs(nullptr, tmp_bytes, key.p, key2.p, val.p, val2.p, (unsigned)nleaf, (unsigned)n, leaf_off.p,
+                                                  leaf_off.p + 1, 0, end_bit, s));
+    DevBuf<uint8_t> tmp(std::max<size_t>(tmp_bytes, 8));
+    HIP_CHECK(rocprim::segmented_radix_sort_pairs(tmp.p, tmp_bytes, key.p, key2.p, val.p, val2.p, (unsigned)nleaf, (unsigned)n, leaf_off.p,
+                                                  leaf_off.p + 1, 0, end_bit, s));
+    hipLaunchKernelGGL(mm_leaf_widths_kernel, dim3(grid_for(r, nleaf, 256)), dim3(256), 0, s, val2.p, nleaf, width.p);
+    HIP_CHECK(hipGetLastError());
+    launch_scan(r, width.p, nleaf, leaf_hit_off.p, lscratch.p, s);
+    DevBuf<uint64_t> d_gpos(total), d_pos(want_pos ? 2 * total : 0);
+    DevBuf<uint8_t> d_mm(want_mm ? total : 0);
+    launch_locate(r, key2.p, 1, leaf_hit_off.p, nleaf, total, d_gpos.p, d_pos.p, s);
+    if (want_mm) {
+      hipLaunchKernelGGL(mm_hit_distance_kernel, dim3(grid_for(r, total, 256)), dim3(256), 0, s, leaf_hit_off.p, val2.p, nleaf, total, d_mm.p);
+      HIP_CHECK(hipGetLastError());
+    }
+    if (want_gpos) { out.gpos.resize(at_h + total); HIP_CHECK(hipMemcpyAsync(out.gpos.data() + at_h, d_gpos.p, total * 8, hipMemcpyDeviceToHost, s)); }
+    if (want_pos) { out.pos.resize(at_h + total); HIP_CHECK(hipMemcpyAsync(out.pos.data() + at_h, d_pos.p, total * 16, hipMemcpyDeviceToHost, s)); }
+    if (want_mm) { out.mm.resize(at_h + total); HIP_CHECK(hipMemcpyAsync(out.mm.data() + at_h, d_mm.p, total, hipMemcpyDeviceToHost, s)); }
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  return true;
+}
+
+void locate_mismatch_range(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, bool want_pos, bool want_gpos, bool want_mm,
+                           MismatchHits& out) {
+  if (c.hi <= c.lo) return;
+  if (locate_mismatch_chunk(r, qbytes, qoff, c, k, want_pos, want_gpos, want_mm, out)) return;
+  const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order
+  locate_mismatch_range(r, qbytes, qoff, Shard{c.lo, mid}, k, want_pos, want_gpos, want_mm, out);
+  locate_mismatch_range(r, qbytes, qoff, Shard{mid, c.hi}, k, want_pos, want_gpos, want_mm, out);
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -2760,6 +2897,56 @@ int awry_locate_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* 
 
 void awry_free_buffer(void* p) { release_result(p); }
 
+int awry_count_mismatch_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_mismatches,
+                              uint64_t* counts_out) {
+  return guarded([&] {
+    require(idx && qoff && (counts_out || n == 0), "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_mismatches(max_mismatches);
+    for_each_replica(idx, n, [&](Replica& r, Shard sh, int) { count_mismatch_shard(r, qbytes, qoff, sh, max_mismatches, counts_out); });
+  });
+}
+
+int awry_locate_mismatch_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_mismatches,
+                               uint64_t** hit_off_out, awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** mismatches_out) {
+  return guarded([&] {
+    require(idx && qoff && hit_off_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_mismatches(max_mismatches);
+    std::vector<MismatchHits> res(std::max<size_t>(1, idx->reps.size()));
+    for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
+      HIP_CHECK(hipSetDevice(r.device));
+      for (Shard c : chunk_queries(qoff, sh.lo, sh.hi))
+        locate_mismatch_range(r, qbytes, qoff, c, max_mismatches, hits_out != nullptr, global_pos_out != nullptr, mismatches_out != nullptr, res[g]);
+    });
+    // shards are contiguous in query order: the result arrays are their concatenation
+    MBuf<uint64_t> off, gp;
+    MBuf<awry_pos_t> hits;
+    MBuf<uint8_t> mm;
+    off.grow(n + 1);
+    off.p[0] = 0;
+    uint64_t q = 0, total = 0;
+    for (auto& x : res)
+      for (uint64_t c : x.counts) { total += c; off.p[++q] = total; }
+    require(q == n, "internal: shard results do not cover the batch");
+    if (hits_out) hits.grow(std::max<uint64_t>(1, total));
+    if (global_pos_out) gp.grow(std::max<uint64_t>(1, total));
+    if (mismatches_out) mm.grow(std::max<uint64_t>(1, total));
+    uint64_t at = 0;
+    for (auto& x : res) {
+      const uint64_t t = x.counts.empty() ? 0 : std::max({x.gpos.size(), x.pos.size(), x.mm.size()});
+      if (hits_out && t) pool_memcpy(hits.p + at, x.pos.data(), t * sizeof(awry_pos_t));
+      if (global_pos_out && t) pool_memcpy(gp.p + at, x.gpos.data(), t * 8);
+      if (mismatches_out && t) pool_memcpy(mm.p + at, x.mm.data(), t);
+      at += t;
+    }
+    *hit_off_out = off.release();
+    if (hits_out) *hits_out = hits.release();
+    if (global_pos_out) *global_pos_out = gp.release();
+    if (mismatches_out) *mismatches_out = mm.release();
+  });
+}
+
 namespace {
 // one query through the replica's pinned mailbox; want_rows: the range must be a row interval (no text shortcut)
 // (the caller holds r.mailbox_mu)
@@ -3141,6 +3328,36 @@ int awry_dev_locate_tally(awry_index_t* idx, int slot, const void* d_ranges, int
     require(r.dev.alphabet == NUCLEOTIDE, "the walk census is kept by the nucleotide walk kernel");
     launch_locate(r, (const uint64_t*)d_ranges, range_stride, (const uint64_t*)d_hit_off, n, total, (uint64_t*)d_global_pos,
                   (uint64_t*)d_pos, (hipStream_t)stream, (unsigned long long*)d_tally);
+  });
+}
+
+int awry_dev_count_mismatch(awry_index_t* idx, int slot, const void* d_qbytes, const void* d_qoff, uint64_t n, int max_mismatches,
+                            void* d_counts, void* d_status, void* stream) {
+  return awry_dev_count_mismatch_tally(idx, slot, d_qbytes, d_qoff, n, max_mismatches, d_counts, d_status, nullptr, stream);
+}
+
+int awry_dev_count_mismatch_tally(awry_index_t* idx, int slot, const void* d_qbytes, const void* d_qoff, uint64_t n, int max_mismatches,
+                                  void* d_counts, void* d_status, void* d_tally, void* stream) {
+  return guarded([&] {
+    require_mismatches(max_mismatches);
+    Replica& r = replica(idx, slot);
+    require(n == 0 || (d_qbytes && d_qoff && d_counts), "null argument");
+    launch_count_mismatch(r, (const uint8_t*)d_qbytes, (const uint64_t*)d_qoff, n, max_mismatches, (uint64_t*)d_counts, nullptr, nullptr,
+                          (uint8_t*)d_status, (hipStream_t)stream, (unsigned long long*)d_tally);
+  });
+}
+
+int awry_debug_rank_all(awry_index_t* idx, int slot, const void* d_rows, uint64_t n, void* d_occ, void* stream) {
+  return guarded([&] {
+    Replica& r = replica(idx, slot);
+    if (n == 0) return;
+    require(d_rows && d_occ, "null argument");
+    const dim3 g(grid_for(r, n, 256)), b(256);
+    if (r.dev.alphabet == NUCLEOTIDE)
+      hipLaunchKernelGGL(rank_all_kernel<NUCLEOTIDE>, g, b, 0, (hipStream_t)stream, r.dev, (const uint64_t*)d_rows, n, (uint64_t*)d_occ);
+    else
+      hipLaunchKernelGGL(rank_all_kernel<AMINO>, g, b, 0, (hipStream_t)stream, r.dev, (const uint64_t*)d_rows, n, (uint64_t*)d_occ);
+    HIP_CHECK(hipGetLastError());
   });
 }
 

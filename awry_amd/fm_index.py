@@ -27,6 +27,7 @@ class AwryError(RuntimeError):
 
 
 ERR_IO, ERR_FORMAT, ERR_INVALID_QUERY, ERR_HIP, ERR_OOM, ERR_ARG, ERR_NO_DEVICE = -1, -2, -3, -4, -5, -6, -7
+MAX_MISMATCHES = 2  # AWRY_MAX_MISMATCHES
 
 
 @dataclass
@@ -349,6 +350,74 @@ class FmIndex:
         """src/fm_index.rs:479-487: outer order = input order, inner order = ascending BWT row"""
         off, _, p = self.parallel_locate_csr(*pack_queries(queries))
         return [[LocalizedSequencePosition(int(a), int(b)) for a, b in p[off[i]:off[i + 1]]] for i in range(len(off) - 1)]
+
+    # ------------------------------------------------------------------ substitution-tolerant search (Hamming distance <= k)
+    def parallel_count_mismatch_csr(self, qbytes: np.ndarray, qoff: np.ndarray, k: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """-> uint64[n, k + 1]: row i holds the occurrences of query i at exactly 0, 1, .., k substitutions (include/awry_hip.h
+        states the semantics); `out` (contiguous uint64[n, k + 1]) is filled and returned when given"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        w = max(int(k), 0) + 1
+        if out is None:
+            out = np.empty((n, w), dtype=np.uint64)
+        elif out.dtype != np.uint64 or out.shape != (n, w) or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous uint64 array of shape (n, k + 1)")
+        _check(self._L.awry_count_mismatch_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(k), out.ctypes.data_as(_u64p)))
+        return out
+
+    def parallel_count_mismatch(self, queries: Iterable, k: int) -> np.ndarray:
+        """counts per query and distance, uint64[n, k + 1], in input order"""
+        return self.parallel_count_mismatch_csr(*pack_queries(queries), k)
+
+    def parallel_locate_mismatch_csr(self, qbytes: np.ndarray, qoff: np.ndarray, k: int, want_pos: bool = True):
+        """-> (hit_off uint64[n+1], global_pos uint64[total], pos uint64[total, 2], mismatches uint8[total]): hits of query i
+        in ascending BWT-row order with the distance of each; want_pos=False leaves pos empty"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        off, hits, gp, mm = _u64p(), C.POINTER(_lib.Pos)(), _u64p(), C.POINTER(C.c_uint8)()
+        _check(self._L.awry_locate_mismatch_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(k), C.byref(off),
+                                                  C.byref(hits) if want_pos else None, C.byref(gp), C.byref(mm)))
+        offs = _adopt(self._L, off, n + 1, np.uint64)
+        tot = int(offs[-1])
+        g = _adopt(self._L, gp, tot, np.uint64)
+        p = _adopt(self._L, hits, 2 * tot, np.uint64).reshape(-1, 2) if want_pos else np.zeros((0, 2), np.uint64)
+        d = _adopt(self._L, mm, tot, np.uint8)
+        return offs, g, p, d
+
+    def count_string_mismatch(self, query, k: int) -> int:
+        """occurrences of one query with at most k substitutions"""
+        return int(self.parallel_count_mismatch([query], k).sum())
+
+    def locate_string_mismatch(self, query, k: int):
+        """-> [(LocalizedSequencePosition, distance)] of one query, ascending BWT-row order"""
+        off, _, p, d = self.parallel_locate_mismatch_csr(*pack_queries([query]), k)
+        return [(LocalizedSequencePosition(int(a), int(b)), int(m)) for (a, b), m in zip(p, d)]
+
+    def dev_count_mismatch(self, d_qbytes, d_qoff, n, k, d_counts, d_status=None, stream=None, slot=0):
+        """device-resident count: d_counts[n * (k + 1)] (u64), optional d_status[n] bytes"""
+        _check(self._L.awry_dev_count_mismatch(self._h, slot, d_qbytes, d_qoff, n, int(k), d_counts, d_status, stream))
+
+    def dev_count_mismatch_tally(self, d_qbytes, d_qoff, n, k, d_counts, d_tally, d_status=None, stream=None, slot=0):
+        """dev_count_mismatch + census: d_tally[2] += (expansions, queries searched)"""
+        _check(self._L.awry_dev_count_mismatch_tally(self._h, slot, d_qbytes, d_qoff, n, int(k), d_counts, d_status, d_tally, stream))
+
+    def debug_rank_all(self, rows: np.ndarray, slot=0) -> np.ndarray:
+        """Occ of every non-sentinel symbol at each row through the kernels' all-symbol rank -> uint64[len(rows), S]
+        (column s - 1 = symbol index s; S = 5 nucleotide, 21 amino)"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        S = 5 if self.alphabet() == NUCLEOTIDE else 21
+        if len(r) == 0:
+            return np.zeros((0, S), np.uint64)
+        d_r, d_o = self.dev_upload(r, slot), self.dev_malloc(8 * S * len(r), slot)
+        try:
+            _check(self._L.awry_debug_rank_all(self._h, slot, d_r, len(r), d_o, None))
+            self.dev_synchronize(slot)
+            return self.dev_download(d_o, (len(r), S), np.uint64, slot)
+        finally:
+            self.dev_free(d_r, slot)
+            self.dev_free(d_o, slot)
 
     # ------------------------------------------------------------------ device-resident path
     def dev_malloc(self, nbytes, slot=0) -> int:

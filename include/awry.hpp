@@ -142,6 +142,34 @@ class FmIndex {
     awry_free_buffer(hoff); awry_free_buffer(hits);
     return out;
   }
+  // substitution-tolerant search (no counterpart in the reference; semantics in awry_hip.h): counts[i * (k + 1) + d] =
+  // occurrences of query i at exactly d substitutions
+  template <class StrRange>
+  std::vector<uint64_t> parallel_count_mismatch(const StrRange& queries, int k) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    std::vector<uint64_t> out((off.size() - 1) * (size_t)(k >= 0 ? k + 1 : 1));
+    check(awry_count_mismatch_batch(h_, bytes.data(), off.data(), off.size() - 1, k, out.data()));
+    return out;
+  }
+  struct MismatchHit {
+    LocalizedSequencePosition position;
+    uint8_t mismatches;
+  };
+  // hits of each query in ascending BWT-row order, with their distances
+  template <class StrRange>
+  std::vector<std::vector<MismatchHit>> parallel_locate_mismatch(const StrRange& queries, int k) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* hoff = nullptr; awry_pos_t* hits = nullptr; uint8_t* mm = nullptr;
+    check(awry_locate_mismatch_batch(h_, bytes.data(), off.data(), n, k, &hoff, &hits, nullptr, &mm));
+    std::vector<std::vector<MismatchHit>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = hoff[i]; j < hoff[i + 1]; j++) out[i].push_back({{hits[j].seq_idx, hits[j].local_pos}, mm[j]});
+    awry_free_buffer(hoff); awry_free_buffer(hits); awry_free_buffer(mm);
+    return out;
+  }
   // src/fm_index.rs:559-582, 585-593
   SearchRange update_range_with_symbol(SearchRange r, char symbol) {
     awry_range_t o;

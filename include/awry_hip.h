@@ -148,6 +148,30 @@ int awry_count_packed_kmers(awry_index_t *idx, const uint64_t *words, uint64_t n
  * are neither computed nor moved; with both NULL the call returns the offsets alone. */
 int awry_locate_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n,
                       uint64_t **hit_off_out, awry_pos_t **hits_out, uint64_t **global_pos_out);
+/* ---- substitution-tolerant search (Hamming distance, no counterpart in the reference) --------------------
+ * Query i and the index text are compared as symbol indices, exactly as the exact path maps them: letters are
+ * case-insensitive, U is T, any other byte is N (nucleotide) / X (amino).  The distance of text position p is the number
+ * of positions j < L with text[p + j] != query[j]; p is an occurrence with <= k mismatches when its window
+ * text[p .. p + L) holds no '$' and its distance is <= k.  Substitutions range over every non-sentinel symbol of the
+ * alphabet (nucleotide A C G N T: 4 alternatives per position; amino the 21 symbols, X included: 20), so query N matches
+ * text N as on the exact path, and k = 0 gives exactly awry_count_batch / awry_locate_batch.  k >= L is legal: every
+ * window without '$' then matches.  max_mismatches outside 0..AWRY_MAX_MISMATCHES => AWRY_ERR_ARG; queries are rejected
+ * as in awry_count_batch (empty, '$' / '#', byte >= 0x80 => AWRY_ERR_INVALID_QUERY); no replica => AWRY_ERR_NO_DEVICE.
+ * Distinct substitution patterns spell distinct strings, so their row ranges are disjoint: counts are sums of ranges and
+ * ascending BWT-row order is well defined. */
+enum { AWRY_MAX_MISMATCHES = 2 };
+/* no counterpart in the reference.  counts_out[n * (k + 1)]: row i holds the occurrences of query i at exactly
+ * 0, 1, .., k substitutions (Hamming distance over symbol indices; windows holding '$' never match) */
+int awry_count_mismatch_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n,
+                              int max_mismatches, uint64_t *counts_out);
+/* CSR like awry_locate_batch: hits of query i are [hit_off[i], hit_off[i+1]) in ascending BWT-row order, the
+ * same order awry_locate_batch uses; mismatches_out (nullable) receives each hit's distance.  Each result array is
+ * nullable as in awry_locate_batch; all are released with awry_free_buffer.  A chunk of queries whose occurring variants
+ * exceed the device leaf capacity (2^26 row ranges; env AWRY_MISMATCH_LEAF_CAP, read per call) is split and redone. */
+int awry_locate_mismatch_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n,
+                               int max_mismatches, uint64_t **hit_off_out, awry_pos_t **hits_out,
+                               uint64_t **global_pos_out, uint8_t **mismatches_out);
+
 /* releases an array one of the calls above (or awry_locate / awry_read_query_file) returned.  Result arrays are pinned
  * host memory recycled through a process-wide pool (the device writes results straight into them); never pass them to
  * free().  AWRY_PINNED_CACHE_GB (default 4) bounds what the pool keeps between calls. */
@@ -246,6 +270,18 @@ int awry_dev_count_ascii_uniform(awry_index_t *idx, int slot, const void *d_qbyt
  * (168 B per block); slower than the plain call (per-event atomics) -- for untimed runs */
 int awry_dev_count_ascii_uniform_tally(awry_index_t *idx, int slot, const void *d_qbytes, uint64_t n, uint64_t len,
                                        void *d_counts, void *d_tally, void *stream);
+/* substitution-tolerant count (see awry_count_mismatch_batch), device-resident form for timing and device callers (no
+ * allocation inside; workspace owned by the replica): ASCII queries + u64 offsets[n+1] -> d_counts[n * (k + 1)], optional
+ * d_status[n] bytes (non-zero: rejected query, counts 0) */
+int awry_dev_count_mismatch(awry_index_t *idx, int slot, const void *d_qbytes, const void *d_qoff, uint64_t n,
+                            int max_mismatches, void *d_counts, void *d_status, void *stream);
+/* the same with a work census: d_tally[2] (u64, caller-zeroed) += {expansions -- Occ of every symbol at the two rows of one
+ * node, two block lines --, queries searched}; per-lane atomics at the end of the launch only */
+int awry_dev_count_mismatch_tally(awry_index_t *idx, int slot, const void *d_qbytes, const void *d_qoff, uint64_t n,
+                                  int max_mismatches, void *d_counts, void *d_status, void *d_tally, void *stream);
+/* test hook of the all-symbol rank primitive: d_occ[i * S + s - 1] = Occ(s, d_rows[i]) for every non-sentinel symbol index s
+ * (S = 5 nucleotide, 21 amino; inclusive of the row, as awry_update_range uses it); rows >= bwt_len give zeros */
+int awry_debug_rank_all(awry_index_t *idx, int slot, const void *d_rows, uint64_t n, void *d_occ, void *stream);
 /* exclusive scan of counts[n] -> hit_off[n+1] (d_scratch: awry_dev_scan_scratch_bytes(n) bytes) */
 uint64_t awry_dev_scan_scratch_bytes(uint64_t n);
 int awry_dev_scan_counts(awry_index_t *idx, int slot, const void *d_counts, uint64_t n, void *d_hit_off,

@@ -405,6 +405,56 @@ impl FmIndex {
         Ok(out)
     }
 
+    /// Substitution-tolerant counts (no counterpart in the reference; semantics in include/awry_hip.h): row i of the result
+    /// holds the occurrences of query i at exactly 0, 1, .., `max_mismatches` substitutions (Hamming distance over symbol
+    /// indices, windows holding '$' never match); `max_mismatches` must be 0, 1 or 2.
+    pub fn parallel_count_mismatch<'a>(&self, queries: impl ParallelIterator<Item = &'a str>, max_mismatches: u32) -> Result<Vec<Vec<u64>>, AwryError> {
+        let csr = to_csr(queries);
+        let n = csr.offsets.len() - 1;
+        let w = max_mismatches as usize + 1;
+        let mut counts = vec![0u64; n * w];
+        check(unsafe {
+            sys::awry_count_mismatch_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, max_mismatches as i32, counts.as_mut_ptr())
+        })?;
+        Ok(counts.chunks(w).map(|c| c.to_vec()).collect())
+    }
+
+    /// Substitution-tolerant locations: per query, `(position, distance)` in ascending BWT-row order.
+    pub fn parallel_locate_mismatch<'a>(
+        &self,
+        queries: impl ParallelIterator<Item = &'a str>,
+        max_mismatches: u32,
+    ) -> Result<Vec<Vec<(LocalizedSequencePosition, u8)>>, AwryError> {
+        let csr = to_csr(queries);
+        let n = csr.offsets.len() - 1;
+        let mut hit_off: *mut u64 = std::ptr::null_mut();
+        let mut hits: *mut sys::awry_pos_t = std::ptr::null_mut();
+        let mut mm: *mut u8 = std::ptr::null_mut();
+        check(unsafe {
+            sys::awry_locate_mismatch_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, max_mismatches as i32, &mut hit_off,
+                                            &mut hits, std::ptr::null_mut(), &mut mm)
+        })?;
+        let out = unsafe {
+            let off = std::slice::from_raw_parts(hit_off, n + 1);
+            let total = off[n] as usize;
+            let flat: &[sys::awry_pos_t] = if total == 0 { &[] } else { std::slice::from_raw_parts(hits, total) };
+            let dist: &[u8] = if total == 0 { &[] } else { std::slice::from_raw_parts(mm, total) };
+            (0..n)
+                .map(|i| {
+                    (off[i] as usize..off[i + 1] as usize)
+                        .map(|j| (LocalizedSequencePosition::new(flat[j].seq_idx as usize, flat[j].local_pos as usize), dist[j]))
+                        .collect::<Vec<_>>()
+                })
+                .collect::<Vec<_>>()
+        };
+        unsafe {
+            sys::awry_free_buffer(hit_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(hits as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(mm as *mut std::os::raw::c_void);
+        }
+        Ok(out)
+    }
+
     /// Locations of a batch as flat arrays: `(hit_offsets[n + 1], global text positions)`; the hits of query i are
     /// `positions[hit_offsets[i]..hit_offsets[i + 1]]`, `(SA sample + steps) % bwt_len` of src/fm_index.rs:534.
     /// Passes `hits_out = NULL`: 8 bytes per hit cross PCIe instead of 24.
