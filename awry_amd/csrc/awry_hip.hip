@@ -220,7 +220,8 @@ struct Replica {
     DevBuf<uint64_t> w, range;
     DevBuf<uint32_t> q, count;
     uint64_t cap = 0, cap_q = 0;
-    // what lcx_quad_reads_kernel leaves for the LF pass: one device-wide list (fcount[0] slots)
+    // what lcx_quad_reads_kernel leaves for the LF pass: one device-wide list (fcount[0] slots used, fcap allocated:
+    // lcx_lf_list_bound of the launch)
     DevBuf<uint64_t> fw, frange;
     DevBuf<uint32_t> fq, fcount;
     uint64_t fcap = 0;
@@ -241,6 +242,9 @@ struct Replica {
   // blocks of count_nt2_probe_resume_kernel<TALLY, VERIFY> resident per CU, by [2 * TALLY + VERIFY] (the occupancy query of
   // each instantiation, at replica creation): its grid, and the number of survivor lists two_phase_lists sizes
   int probe_resume_per_cu[4] = {8, 8, 8, 8};
+  // blocks of lcx_quad_reads_kernel<RAGGED> resident at once, by [RAGGED] (the occupancy query at replica creation): its
+  // grid, and the number of waves whose partly filled chunks two_phase_lists makes room for in the LF list
+  unsigned lcx_reads_grid[2] = {0, 0};
   DevIndex dev{};
   ~Replica() {
     if (device >= 0) {
@@ -667,6 +671,12 @@ std::unique_ptr<Replica> make_replica(awry_index* ix, int device) {
       HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused[i], 256, 0));
       r->probe_resume_per_cu[i] = std::max(1, std::min(per_cu, 8));
     }
+    const void* lcx_reads[2] = {(const void*)lcx_quad_reads_kernel<false>, (const void*)lcx_quad_reads_kernel<true>};
+    for (int i = 0; i < 2; i++) {
+      int per_cu = 0;
+      HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lcx_reads[i], 256, 0));
+      r->lcx_reads_grid[i] = (unsigned)r->num_cus * (unsigned)std::max(1, per_cu);
+    }
   }
   HIP_CHECK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
   for (auto& ls : r->lane_stream) HIP_CHECK(hipStreamCreateWithFlags(&ls, hipStreamNonBlocking));
@@ -1009,33 +1019,45 @@ bool lcx_lanes(const Replica& r) {
 // (dense SA, text, position seeds) the entry settles too few queries for a second launch to pay.  Selected with
 // AWRY_COUNT_KERNEL=twophase / awry_debug_set_count_kernel(3).
 bool wide_two_phase(uint64_t n) { const int m = count_kernel_override(); return m >= 3 && m <= 5 && n < (1ull << 32); }
+// The LF list lcx_quad_reads_kernel appends to on a grid of `grid` blocks (4 waves each), for `total` list slots of survivors.
+// A wave reserves LCX_LF_CHUNK slots at a time with one atomic and fills them in order.  One append is one item per quad
+// (16 per wave at most), and the wave reserves its next chunk only when an append does not fit in what is left, so every
+// chunk it leaves behind holds more than LCX_LF_CHUNK - 16 items; the chunk a wave holds at its end may be almost empty.
+// A wave that reserves c chunks thus appends at least (c - 1) (LCX_LF_CHUNK - 15) items, and the waves append at most
+// `total` items in all (each survivor at most once):
+//   sum_w (c_w - 1) <= floor(total / (LCX_LF_CHUNK - 15)),   chunks <= that + nwaves,
+//   slots = LCX_LF_CHUNK * chunks <= total + 15 * ceil(total / (LCX_LF_CHUNK - 15)) + nwaves * LCX_LF_CHUNK.
+uint64_t lcx_lf_list_bound(uint64_t total, unsigned grid) {
+  const uint64_t per = (uint64_t)LCX_LF_CHUNK - 15, nwaves = 4ull * grid;
+  return total + (total + per - 1) / per * 15 + nwaves * (uint64_t)LCX_LF_CHUNK;
+}
 // the survivor lists of a two-phase launch over n queries on a grid of nblk <= num_cus * 8 blocks (one list per block):
-// `in` (all three arrays) and, with lanes, the fallback lists `out`
-void two_phase_lists(Replica& r, hipStream_t s, uint64_t n, unsigned nblk, bool lanes, Nt2Survivors* in, Nt2Survivors* out) {
+// `in` (all three arrays) and, with lcx_grid != 0, the LF list `out` of lcx_quad_reads_kernel on a grid of lcx_grid blocks
+void two_phase_lists(Replica& r, hipStream_t s, uint64_t n, unsigned nblk, unsigned lcx_grid, Nt2Survivors* in, Nt2Survivors* out) {
   Replica::SurvScratch* sc = surv_scratch(r, s);
   const uint64_t per_block = ((n + (uint64_t)nblk * 256 - 1) / ((uint64_t)nblk * 256)) * 256, total = per_block * nblk;
-  if (sc->cap < total || (lanes && sc->fcap < total)) {
+  const uint64_t fneed = lcx_grid ? lcx_lf_list_bound(total, lcx_grid) : 0;
+  if (sc->cap < total || sc->fcap < fneed) {
     HIP_CHECK(hipStreamSynchronize(s));
     if (sc->cap < total) {
       sc->w.alloc(total); sc->range.alloc(total); sc->q.alloc(total);
       sc->cap = sc->cap_q = total;
     }
-    if (lanes && sc->fcap < total) {  // (+ the chunks the waves of lcx_quad_kernel reserve and do not fill)
-      const uint64_t slack = 1ull << 21;
-      sc->fw.alloc(total + slack); sc->frange.alloc(total + slack); sc->fq.alloc(total + slack);
-      sc->fcap = total;
+    if (sc->fcap < fneed) {
+      sc->fw.alloc(fneed); sc->frange.alloc(fneed); sc->fq.alloc(fneed);
+      sc->fcap = fneed;
     }
   }
   if (!sc->count.p) sc->count.alloc((size_t)r.num_cus * 8);
-  if (lanes && !sc->fcount.p) sc->fcount.alloc(8);  // [0] length of the LF list
+  if (lcx_grid && !sc->fcount.p) sc->fcount.alloc(8);  // [0] length of the LF list
   *in = Nt2Survivors{sc->w.p, sc->range.p, sc->q.p, sc->count.p, per_block};
   *out = Nt2Survivors{};
-  if (lanes) {
-    *out = Nt2Survivors{sc->fw.p, sc->frange.p, sc->fq.p, sc->fcount.p, total};
+  if (lcx_grid) {
+    *out = Nt2Survivors{sc->fw.p, sc->frange.p, sc->fq.p, sc->fcount.p, sc->fcap};
     in->lf_count = sc->fcount.p;
   }
 }
-// blocks of lcx_quad_kernel that are resident at once: its grid (the pool of survivors is shared out dynamically)
+// blocks of a kernel that are resident at once: its grid (the work is shared out dynamically)
 template <class K>
 unsigned resident_grid(const Replica& r, K kernel) {
   int per_cu = 0;
@@ -1055,7 +1077,7 @@ void launch_count_nt2_long(Replica& r, const uint64_t* d_words, uint64_t n, int 
     if (sdw && wide_two_phase(n)) {  // per-lane probe pass, then the quads on what has to be stepped
       Nt2Survivors sv, fb;
       const unsigned nblk = (unsigned)r.num_cus * 8;
-      two_phase_lists(r, s, n, nblk, false, &sv, &fb);
+      two_phase_lists(r, s, n, nblk, 0u, &sv, &fb);
       if (d_lens) {
         hipLaunchKernelGGL((count_nt2_wide_probe_kernel<true, false>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens, (unsigned long long*)nullptr);
         hipLaunchKernelGGL((count_nt2_wide_kernel<true, true, true>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, d_lens, (unsigned long long*)nullptr, sv);
@@ -1080,23 +1102,25 @@ void launch_count_nt2_long(Replica& r, const uint64_t* d_words, uint64_t n, int 
   if (vfy && sd && L - r.seed_k >= 3 && L <= 512 && n < (1ull << 32) && (om < 0 || (om >= 3 && om <= 5))) {
     // two-phase: a per-lane pass settles the reads their seed entry (plus one SA read and one text window) decides,
     // the quad kernel works through the rest
-    const bool lanes = lcx_lanes(r);
-    Nt2Survivors sv, fb;
     const unsigned nblk = (unsigned)r.num_cus * 8;  // both phases of the quad schedule use this grid
-    two_phase_lists(r, s, n, nblk, lanes, &sv, &fb);
+    // the pooled pass (lcx_quad_reads_kernel + count_nt2_reads_pool_kernel) holds the prefix sums of the nblk lists in LDS
+    // and numbers the slots of its LF list with u32: it is taken only while both fit
+    const unsigned gl = r.lcx_reads_grid[d_lens != nullptr];
+    const uint64_t per_block = ((n + (uint64_t)nblk * 256 - 1) / ((uint64_t)nblk * 256)) * 256;
+    const bool lanes = lcx_lanes(r) && gl > 0 && nblk <= (unsigned)LIST_MAX_LISTS && lcx_lf_list_bound(per_block * nblk, gl) <= 0xFFFFFFFFull;
+    Nt2Survivors sv, fb;
+    two_phase_lists(r, s, n, nblk, lanes ? gl : 0u, &sv, &fb);
     if (!lanes) sv.w = sv.range = nullptr;  // (the probe pass then lists the reads only)
     const dim3 gq((unsigned)r.num_cus * 8);  // the quad code over what the lanes left
     if (d_lens) {
       hipLaunchKernelGGL(count_nt2_reads_probe_kernel<true>, dim3(nblk), b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens);
       if (lanes) {
-        static const unsigned gl = resident_grid(r, lcx_quad_reads_kernel<true>);
         hipLaunchKernelGGL(lcx_quad_reads_kernel<true>, dim3(gl), b, 0, s, r.dev, d_words, L, d_counts, d_range_start, sv, fb, nblk, d_lens);
         hipLaunchKernelGGL(count_nt2_reads_pool_kernel<true>, gq, b, 0, s, r.dev, d_words, L, d_counts, d_range_start, fb, d_lens);
       } else hipLaunchKernelGGL((count_nt2_reads_kernel<true, true, true, true>), dim3(nblk), b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens);
     } else {
       hipLaunchKernelGGL(count_nt2_reads_probe_kernel<false>, dim3(nblk), b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens);
       if (lanes) {
-        static const unsigned gl = resident_grid(r, lcx_quad_reads_kernel<false>);
         hipLaunchKernelGGL(lcx_quad_reads_kernel<false>, dim3(gl), b, 0, s, r.dev, d_words, L, d_counts, d_range_start, sv, fb, nblk, d_lens);
         hipLaunchKernelGGL(count_nt2_reads_pool_kernel<false>, gq, b, 0, s, r.dev, d_words, L, d_counts, d_range_start, fb, d_lens);
       } else hipLaunchKernelGGL((count_nt2_reads_kernel<true, true, true, false>), dim3(nblk), b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens);
@@ -1127,7 +1151,7 @@ void launch_count_nt2(Replica& r, const uint64_t* d_words, uint64_t n, int L, ui
     if (sdw && wide_two_phase(n)) {
       Nt2Survivors sv, fb;
       const unsigned nblk = (unsigned)r.num_cus * 8;
-      two_phase_lists(r, s, n, nblk, false, &sv, &fb);
+      two_phase_lists(r, s, n, nblk, 0u, &sv, &fb);
       if (d_tally) hipLaunchKernelGGL((count_nt2_wide_probe_kernel<false, true>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, (uint64_t*)nullptr, sv, (const uint32_t*)nullptr, d_tally);
       else hipLaunchKernelGGL((count_nt2_wide_probe_kernel<false, false>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, (uint64_t*)nullptr, sv, (const uint32_t*)nullptr, d_tally);
       hipLaunchKernelGGL((count_nt2_wide_kernel<true, false, true>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, (uint64_t*)nullptr, (const uint32_t*)nullptr, d_tally, sv);
@@ -1174,7 +1198,7 @@ void launch_count_nt2(Replica& r, const uint64_t* d_words, uint64_t n, int L, ui
     const bool pair = kmode != 3;
     const unsigned nblk = (unsigned)r.num_cus * (kmode == 4 ? 8u : (unsigned)r.probe_resume_per_cu[2 * (d_tally != nullptr) + vfy]);
     Nt2Survivors sv, fb;
-    two_phase_lists(r, s, n, nblk, false, &sv, &fb);
+    two_phase_lists(r, s, n, nblk, 0u, &sv, &fb);
     const dim3 gp(nblk);
 #define AWRY_LAUNCH_TWO_PHASE(T, V)                                                                                   \
   do {                                                                                                               \

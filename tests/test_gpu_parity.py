@@ -565,11 +565,12 @@ def test_host_pipelines_over_many_chunks(oracle):
 
 
 @pytest.mark.parametrize("n,recs", [(248_956_422, 1), (3_100_000_000, 25)], ids=["chr1_scale", "grch38_scale"])
-def test_full_scale_properties(n, recs):
+def test_full_scale_properties(oracle, tmp_path, n, recs):
     """BASELINE.json's full sizes (index built on the GPU in seconds): size-independent properties.
     * every k-mer sampled from the text is found, at its own position, and every located window equals the query;
     * count == number of locations; the seeded, unseeded and generic kernels agree;
-    * letter totals in the prefix sums equal the text's histogram (checksum of the BWT)."""
+    * letter totals in the prefix sums equal the text's histogram (checksum of the BWT);
+    * chr1 scale: counts, positions and their order equal the oracle's (same index via an .awry round trip) on 2e4 queries."""
     text, st, hd = synth.make_text(n, 0, 0xA5A50000 + 2, recs, 0.05)
     ix = gpu_index(text, 0, 8, 0, st, hd)
     hist = np.bincount(text, minlength=256)
@@ -595,10 +596,24 @@ def test_full_scale_properties(n, recs):
     for ptr in (d_q, d_o, d_c):
         ix.dev_free(ptr)
     assert np.array_equal(seeded, ix.parallel_count_csr(qb, qo))  # host boundary (packed fast path)
+    sample = None
+    if n < 1_000_000_000:  # chr1 scale: the oracle on every other present and every other random query
+        path = str(tmp_path / "c.awry")
+        ix.save(path)
+        oi = oracle.OracleIndex.load(path)
+        sample = np.concatenate([np.arange(0, len(present), 2), np.arange(len(present), len(q2d), 2)])
+        assert len(sample) == 20000
+        ooff, ogpos, opos, _ = oi.parallel_locate(*synth.fixed_to_csr(q2d[sample]), 8)
+        oi.close()
+        os.remove(path)
+        assert np.array_equal(np.diff(ooff), seeded[sample])
     for ratio in (0, 4):
         ix.set_locate_sa_ratio(ratio)
         off, gpos, pos = ix.locate_reads_nt2(q2d)
         assert np.array_equal(np.diff(off), seeded)
+        if sample is not None:
+            assert np.array_equal(np.concatenate([gpos[int(off[i]):int(off[i + 1])] for i in sample]), ogpos), ratio
+            assert np.array_equal(np.concatenate([pos[int(off[i]):int(off[i + 1])] for i in sample]), opos), ratio
         qi = np.repeat(np.arange(len(q2d)), seeded.astype(np.int64))
         assert np.array_equal(text[gpos.astype(np.int64)[:, None] + np.arange(L)[None, :]], q2d[qi])
         first = off[:len(present)].astype(np.int64)

@@ -180,6 +180,95 @@ def test_repeat_rich_counts_and_locations_match_the_oracle(oracle, n, seed):
     oi.close()
 
 
+def planted_units_text(n, seed, units, margin=200):
+    """n i.i.d. letters with exact copies of random units planted, [(unit length, copies)]: every copy sits in a slot of its
+    own, at least `margin` letters from the slot's ends, so copies neither overlap nor touch -- a window of a unit then
+    occurs exactly `copies` times (a chance match elsewhere is ~4^-L away) -> (text with '$', [(unit letters, copies)])"""
+    rng = np.random.default_rng(seed)
+    body = synth.NT[rng.integers(0, 4, size=n, dtype=np.uint8)]
+    made = [(synth.NT[rng.integers(0, 4, size=u, dtype=np.uint8)], c) for u, c in units]
+    which = rng.permutation(np.repeat(np.arange(len(made)), [c for _, c in made]))
+    slot = n // len(which)
+    for j, w in enumerate(which.tolist()):
+        u = made[w][0]
+        assert slot >= len(u) + 2 * margin
+        s = j * slot + int(rng.integers(margin, slot - len(u) - margin + 1))
+        body[s:s + len(u)] = u
+    return np.concatenate([body, np.frombuffer(b"$", np.uint8)]), made
+
+
+def test_lf_list_of_a_launch_of_2_pow_26_reads(oracle):
+    """2^26 reads of 101 letters in ONE dev_count_nt2_long launch, every read a window of a unit planted 12 or 40 times: more
+    than 8 hits each, so lcx_quad_reads_kernel sends every read to its device-wide LF list (more than 2^24 items through the
+    pool: its u32 prefix sums and wave shares, and the list's chunked reservations at their largest).  Counts of all reads,
+    with range starts and without, and on three slices of 2^20 reads the locations and their order are the oracle's."""
+    L, N, ns = 101, 1 << 26, 1 << 20
+    text, units = planted_units_text(4_000_000, 21, [(2000, 12), (1000, 40)])
+    ix = FmIndex.from_text(text, 0, 8, 0, [0], ["one"]).set_devices([0])
+    assert ix.lcx_enabled() and ix.verify_enabled() and ix.locate_sa_ratio() == 1  # (what the pooled pass needs)
+    win = np.concatenate([np.stack([u[j:j + L] for j in range(len(u) - L + 1)]) for u, _ in units])
+    copies = np.concatenate([np.full(len(u) - L + 1, c, np.uint64) for u, c in units])
+    oi = oracle.OracleIndex.from_text(text, 0, 8, 0, [0], ["one"])
+    ooff, ogpos, opos, _ = oi.parallel_locate(*synth.fixed_to_csr(win), 8)
+    oi.close()
+    assert np.array_equal(np.diff(ooff), copies)
+    nd, W = len(win), (L + 31) // 32
+    bufs = []
+
+    def dmalloc(nbytes):
+        bufs.append(ix.dev_malloc(nbytes))
+        return bufs[-1]
+
+    try:
+        bufs.append(ix.dev_upload(np.ascontiguousarray(win).reshape(-1)))
+        d_dw, d_bad = dmalloc(8 * nd * W), dmalloc(8)
+        ix.dev_memset(d_bad, 0, 8)
+        ix.dev_pack_nt2(bufs[0], nd, L, d_dw, d_bad)
+        ix.dev_synchronize()
+        assert int(ix.dev_download(d_bad, (1,), np.uint64)[0]) == 0
+        dw = ix.dev_download(d_dw, (nd, W), np.uint64)
+        pick = np.random.default_rng(22).integers(0, nd, size=N).astype(np.uint32)
+        words = dw[pick]  # 2 GiB of packed reads
+        bufs.append(ix.dev_upload(words))
+        d_words = bufs[-1]
+        del words
+        want = copies[pick]
+        d_counts, d_rs = dmalloc(8 * N), dmalloc(8 * N)
+        for rs in (None, d_rs):
+            ix.dev_memset(d_counts, 0xFF, 8 * N)
+            ix.dev_count_nt2_long(d_words, N, L, d_counts, rs)
+            ix.dev_synchronize()
+            counts = ix.dev_download(d_counts, (N,), np.uint64)
+            bad = np.flatnonzero(counts != want)
+            assert len(bad) == 0, ("range starts" if rs else "counts only", len(bad), bad[:5], counts[bad[:5]], want[bad[:5]])
+            del counts
+        d_off, d_scr = dmalloc(8 * (ns + 1)), dmalloc(ix.dev_scan_scratch_bytes(ns))
+        for s0 in (0, N // 2 - ns // 2, N - ns):
+            ix.dev_scan_counts(d_counts + 8 * s0, ns, d_off, d_scr)
+            ix.dev_synchronize()
+            off = ix.dev_download(d_off, (ns + 1,), np.uint64)
+            idx = pick[s0:s0 + ns]
+            lens = copies[idx].astype(np.int64)
+            assert off[0] == 0 and np.array_equal(np.diff(off), copies[idx])
+            total = int(off[-1])
+            d_g, d_p = ix.dev_malloc(8 * total), ix.dev_malloc(16 * total)
+            try:
+                ix.dev_locate(d_rs + 8 * s0, d_off, ns, total, d_g, d_p, range_stride=1)
+                ix.dev_synchronize()
+                g = ix.dev_download(d_g, (total,), np.uint64)
+                p = ix.dev_download(d_p, (total, 2), np.uint64)
+            finally:
+                ix.dev_free(d_g)
+                ix.dev_free(d_p)
+            src = np.repeat(ooff[:-1][idx].astype(np.int64) - off[:-1].astype(np.int64), lens) + np.arange(total)
+            assert np.array_equal(g, ogpos[src]), s0
+            assert np.array_equal(p, opos[src]), s0
+    finally:
+        for b in bufs:
+            ix.dev_free(b)
+        ix.close()
+
+
 def test_reads_next_to_gaps_and_the_text_start(oracle):
     """suffixes whose 32 left letters do not all exist (behind a run of N, a record delimiter, the text's first letters) sit in
     their buckets' unsorted tails: reads and k-mers that end right behind such places still count and locate like the oracle's"""
