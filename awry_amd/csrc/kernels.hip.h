@@ -28,7 +28,7 @@
 //   locate                LOCATE_TILE_KERNEL<A>              hit -> row, sampled / verified hits finished
 //                         + LOCATE_WALK_NT_LANE_KERNEL       LF walks of the rest, one hit per lane, whole block per step
 //                         + LOCALISE_WALKED_KERNEL           record / offset of the walked hits
-//                         locate_walk_kernel<A>              generic walk (amino), locate_scalar_kernel<A> (round-1 baseline)
+//                         LOCATE_WALK_KERNEL<AMINO>          generic walk, the amino indexes' second pass
 //   accelerators          seed_level1/extend/finalize (+aa_*), seed_rows_to_positions_kernel, densify_sa_kernel,
 //                         nblock_sa_kernel, text4_scatter_kernel, text8_scatter_kernel
 //   glue                  pack_nt2_tile_kernel<R>, scan_*_kernel, ref_kmer_table_kernel,
@@ -802,42 +802,6 @@ __global__ __launch_bounds__(256) void ref_kmer_table_kernel(DevIndex ix, int km
     }
     table[2 * slot] = sp;
     table[2 * slot + 1] = ep;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// locate: one hit per lane.  hit h belongs to the query q with hit_off[q] <= h < hit_off[q+1]; its BWT
-// row is ranges[2q] + (h - hit_off[q]) -- ascending row order inside a query, src/fm_index.rs:521.
-// ------------------------------------------------------------------------------------------------
-template <int A>
-__global__ __launch_bounds__(256) void locate_scalar_kernel(DevIndex ix, const uint64_t* __restrict__ ranges,
-                                                            const uint64_t* __restrict__ hit_off, uint64_t n,
-                                                            uint64_t total, uint64_t* __restrict__ gpos,
-                                                            uint64_t* __restrict__ pos /* (seq_idx, local) pairs */) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; h < total; h += stride) {
-    uint64_t lo = 0, hi = n;  // largest q with hit_off[q] <= h
-    while (hi - lo > 1) {
-      uint64_t mid = (lo + hi) >> 1;
-      if (hit_off[mid] <= h) lo = mid; else hi = mid;
-    }
-    uint64_t row = ranges[2 * lo] + (h - hit_off[lo]);
-    uint64_t steps = 0;
-    while (row % ix.sa_ratio != 0) {  // position_is_sampled, src/compressed_suffix_array.rs:109-111
-      row = backstep_scalar<A>(ix, row);
-      steps++;
-    }
-    const uint64_t g = (sa_sample(ix, row / ix.sa_ratio) + steps) % ix.bwt_len;  // src/fm_index.rs:534
-    gpos[h] = g;
-    if (pos) {
-      uint64_t a = 0, z = ix.nseq;  // largest i with seq_starts[i] <= g
-      while (z - a > 1) {
-        uint64_t mid = (a + z) >> 1;
-        if (ix.seq_starts[mid] <= g) a = mid; else z = mid;
-      }
-      pos[2 * h] = a;
-      pos[2 * h + 1] = g - (ix.nseq ? ix.seq_starts[a] : 0);
-    }
   }
 }
 

@@ -1,0 +1,409 @@
+// launchers.h -- count-kernel mode policy and every kernel launch helper (all asynchronous on the stream they are given)
+// A part of awry_hip.hip (one translation unit): included there, in order, and not on its own.
+#pragma once
+
+namespace {
+
+// which instantiation serves awry_dev_count_nt2: 0 strided quads, 1 LDS-staged chunks, 2 groups of four, 3 two-phase,
+// 4 two-phase with the k-mer probe and resume passes as two launches on num_cus * 8 blocks (the schedule before the one
+// launch), 5 the same two launches on the one launch's grid (for A/B of fusion and grid size; other paths treat 4, 5 as 3)
+std::atomic<int> g_count_kernel{-1};
+// -1: no explicit choice (env / policy)
+int count_kernel_override() {
+  int m = g_count_kernel.load();
+  if (m >= 0) return m;
+  const char* e = getenv("AWRY_COUNT_KERNEL");
+  if (e && !strcmp(e, "strided")) return 0;
+  if (e && !strcmp(e, "chunk")) return 1;
+  if (e && !strcmp(e, "quad4")) return 2;
+  if (e && !strcmp(e, "twophase")) return 3;
+  return -1;
+}
+// Policy, from measurements on MI355X, GRCh38-scale, 10 M random 31-mers per launch (tools/ab_count.py, G queries/s):
+//   seed k   strided  quad4  chunk  twophase
+//     14      10.1    10.3    9.9     8.2
+//     16      19.4    21.8   14.4    21.3
+//     17      25.3    28.1     -     29.9
+// quad4 is the general default; once the table is so sparse that most queries are decided by their entry alone
+// (4^k >= 3 bwt_len) the per-lane probe pass of the two-phase schedule wins.
+int count_kernel_mode(uint64_t bwt_len, int seed_k, bool seeded) {
+  const int m = count_kernel_override();
+  if (m >= 0) return m;
+  if (seeded && seed_k >= 1 && seed_k <= 31 && (1ull << (2 * seed_k)) / 3 >= bwt_len) return 3;
+  return 2;
+}
+
+// ---- kernel launch helpers (all asynchronous on `s`) ------------------------------------------------
+
+// slots of one survivor list of a two-phase launch over n queries on nblk blocks: the queries a block sees, ceil(n / (nblk * 256)) * 256
+uint64_t list_slots_per_block(uint64_t n, unsigned nblk) { return ((n + (uint64_t)nblk * 256 - 1) / ((uint64_t)nblk * 256)) * 256; }
+
+// ASCII -> packed 2-bit words.  d_off == nullptr: n queries of L bytes each; else query q = bytes [d_off[q] - base, d_off[q+1] - base)
+// of d_ascii (total_bytes in all), W words per query (stride), lengths to d_lens.
+void launch_pack_nt2(Replica& r, const uint8_t* d_ascii, const uint64_t* d_off, uint64_t base, uint64_t n, uint64_t total_bytes, int L, int W,
+                     uint64_t* d_words, uint32_t* d_lens, unsigned long long* d_bad, hipStream_t s, uint32_t* d_bad_list = nullptr) {
+  if (n == 0) return;
+  const dim3 g(grid_for(r, (n + 63) / 64 * 64, 256)), b(256);
+  with_flags(d_off != nullptr, [&](auto R) {
+    hipLaunchKernelGGL(pack_nt2_tile_kernel<R()>, g, b, 0, s, d_ascii, d_off, base, n, total_bytes, L, W, d_words, d_lens, d_bad, d_bad_list);
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
+// The amino k-mer schedule: count_aa_kmer_probe_kernel (one query per lane: the seed entry, or the entry plus a text
+// window, decides most) and the generic kernel over what it listed, as one pool.  d_off == nullptr: n queries of L residues
+// back to back; else query q = d_q[d_off[q], d_off[q + 1]) of any length (k .. 24 residues take the first pass, the rest
+// is listed).  d_ranges (optional): RS_* words / row starts for the locate pass, in the generic kernel's layout.
+void launch_aa_two_phase(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, int L, uint64_t* d_counts, uint64_t* d_ranges,
+                         uint8_t* d_status, hipStream_t s, unsigned long long* d_tally) {
+  Replica::SurvScratch* sc = surv_scratch(r, s);
+  const unsigned nblk = (unsigned)r.num_cus * 8;
+  const uint64_t per_block = list_slots_per_block(n, nblk);
+  if (sc->cap_q < per_block * nblk) {
+    HIP_CHECK(hipStreamSynchronize(s));
+    sc->q.alloc(per_block * nblk);
+    sc->cap_q = per_block * nblk;
+    sc->cap = 0;  // the nucleotide k-mer path re-allocates its three lists together
+  }
+  if (!sc->count.p) sc->count.alloc(nblk);
+  // the second pass works through all lists as one pool on a grid sized to what is resident at once (3 blocks per CU)
+  const bool pooled = nblk <= (unsigned)LIST_MAX_LISTS;
+  const QueryList ql{sc->q.p, sc->count.p, per_block, nullptr, nullptr, 0, d_tally, pooled ? nblk : 0u};
+  const unsigned nblk2 = pooled ? (unsigned)r.num_cus * 3 : nblk;
+  // Two queries in flight per lane (one: the same rate; four: 141 VGPRs, 10 % slower).  The second pass is a latency
+  // chain over a few per cent of the batch; running it for the first half of a batch on a side stream beside the first
+  // pass of the second half (event fork / join) was measured and costs more than it hides (12.7 -> 10.7 G present
+  // 12-mers/s, host path 0.83 -> 0.52 G queries/s).
+  // queries of more than 24 residues (up to AA_KMER_LONG_MAX): the LONG instantiations -- the same pass over a query's last 24
+  // residues plus a comparison of the rest with the text for the candidates that are left
+  static const bool no_long = getenv("AWRY_AA_LONG") && !strcmp(getenv("AWRY_AA_LONG"), "0");
+  const bool lng = d_off ? !no_long : L > AA_KMER_MAX;
+  with_flags(d_off != nullptr, lng, [&](auto R, auto G) {
+    hipLaunchKernelGGL((count_aa_kmer_probe_kernel<2, R(), G()>), dim3(nblk), dim3(256), 0, s, r.dev, d_q, d_off, n, d_off ? 0 : L, d_counts, d_ranges, d_status, ql);
+  });
+  hipLaunchKernelGGL((count_scalar_kernel<AMINO, LIST_BLOCK>), dim3(nblk2), dim3(256), 0, s, r.dev, d_q, d_off, n, d_counts, d_ranges, d_status, 1,
+                     d_off ? 0 : (uint64_t)L, ql);
+  HIP_CHECK(hipGetLastError());
+}
+
+// allow_verify: the generic kernel may finish queries against the text (ranges then hold RS_* words for locate, not rows)
+// ulen != 0: n queries of ulen bytes each, back to back (d_off is not read)
+// ref_kmer_len >= 0: the reference's own step schedule with that lookup_table_kmer_len -- no seed table, kmer_len - 1 steps taken
+// unconditionally (src/fm_index.rs:402-438, src/kmer_lookup_table.rs:90-110): what awry_search_range returns, rows of absent queries included
+void launch_count_ascii(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, uint64_t* d_counts,
+                        uint64_t* d_ranges, uint8_t* d_status, hipStream_t s, bool allow_verify, uint64_t ulen = 0, int ref_kmer_len = -1) {
+  if (n == 0) return;
+  const int vmode = ref_kmer_len >= 0 ? (2 | (ref_kmer_len << 8)) : (allow_verify ? 1 : 0);
+  if (ref_kmer_len >= 0) allow_verify = false;
+  static const bool aa_off = getenv("AWRY_AA_KMER") && !strcmp(getenv("AWRY_AA_KMER"), "0");
+  if (r.dev.alphabet == AMINO && allow_verify && !ulen && d_off && r.seed_k >= 1 && n >= 4096 && n < (1ull << 32) && !aa_off) {
+    // amino batches of any lengths: the k-mer schedule with per-query lengths (queries it does not take are listed)
+    launch_aa_two_phase(r, d_q, d_off, n, 0, d_counts, d_ranges, d_status, s, nullptr);
+    return;
+  }
+  const dim3 g(grid_for(r, n, 256)), b(256);
+  const QueryList none{};
+  with_alphabet(r.dev.alphabet, [&](auto A) {
+    hipLaunchKernelGGL((count_scalar_kernel<A(), LIST_NONE>), g, b, 0, s, r.dev, d_q, d_off, n, d_counts, d_ranges, d_status, vmode, ulen, none);
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
+uint64_t scan_tiles(uint64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
+
+void launch_scan(Replica& r, const uint64_t* d_counts, uint64_t n, uint64_t* d_hit_off, uint64_t* d_scratch, hipStream_t s) {
+  if (n == 0) { HIP_CHECK(hipMemsetAsync(d_hit_off, 0, 8, s)); return; }
+  const uint64_t tiles = scan_tiles(n);
+  hipLaunchKernelGGL(scan_tile_sums_kernel, dim3((unsigned)tiles), dim3(256), 0, s, d_counts, n, d_scratch);
+  hipLaunchKernelGGL(scan_tile_offsets_kernel, dim3(1), dim3(256), 0, s, d_scratch, tiles, d_scratch + tiles);
+  hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, s, d_counts, n, d_scratch, d_hit_off);
+  HIP_CHECK(hipGetLastError());
+}
+
+// d_range_start[q * rs_stride] = first BWT row of query q's range
+void launch_locate(Replica& r, const uint64_t* d_range_start, int rs_stride, const uint64_t* d_hit_off, uint64_t n, uint64_t total,
+                   uint64_t* d_gpos, uint64_t* d_pos, hipStream_t s, unsigned long long* d_tally = nullptr) {
+  if (total == 0) return;
+  unsigned long long* ctr = next_counter(r, s);
+  const uint64_t tiles = (total + LOC_TILE - 1) / LOC_TILE;
+  const dim3 g((unsigned)std::min<uint64_t>(tiles, (uint64_t)r.num_cus * 8)), b(256);
+  // consecutive tiles a block draws at a time (one search of the whole offset array per run): long enough to amortise
+  // that search, short enough that every block still draws several runs and the launch ends evenly
+  const uint32_t run_len = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, tiles / ((uint64_t)g.x * 4)));
+  const uint32_t* dense = r.dense_ratio ? r.dense_sa.p : nullptr;
+  with_alphabet(r.dev.alphabet, [&](auto A) {
+    hipLaunchKernelGGL(locate_tile_kernel<A()>, g, b, 0, s, r.dev, d_range_start, rs_stride, d_hit_off, n, total, dense, r.dense_ratio, d_gpos, d_pos, ctr, run_len);
+  });
+  HIP_CHECK(hipGetLastError());
+  if (r.dense_ratio == 1) return;  // every row is a sampled row: nothing was deferred
+  // the hits whose row is not sampled walk in a second pass that is not tied to tiles (locate_walk_kernel)
+  unsigned long long* wctr = next_counter(r, s);
+  if (r.dev.alphabet == NUCLEOTIDE)
+    with_flags(d_tally != nullptr, [&](auto T) {
+      hipLaunchKernelGGL((locate_walk_nt_lane_kernel<true, T()>), dim3(grid_for(r, total, 256, 4)), b, 0, s, r.dev, total, dense, r.dense_ratio, d_gpos, wctr, d_tally);
+    });
+  else hipLaunchKernelGGL(locate_walk_kernel<AMINO>, dim3(grid_for(r, total, 256, 7)), b, 0, s, r.dev, total, dense, r.dense_ratio, d_gpos, d_pos, wctr);
+  if (d_pos) hipLaunchKernelGGL(localise_walked_kernel, dim3(grid_for(r, total, 256)), b, 0, s, r.dev, total, d_gpos, d_pos);
+  HIP_CHECK(hipGetLastError());
+}
+
+// reads: phase 2 as a pooled search pass (lcx_quad_reads_kernel) + LF pass whenever the left-context index is resident;
+// else count_nt2_reads_kernel<.., LIST> (block b works through block b's list)
+bool lcx_lanes(const Replica& r) {
+  return r.dev.lcx_key != nullptr && r.dev.text4 != nullptr && r.dev.dense_ratio == 1;
+}
+// wide-row replicas: the two-phase schedule (count_nt2_wide_probe_kernel + the listed quad pass) is an alternative, not the
+// policy -- on a GRCh38-scale index forced onto 64-bit rows (k = 16, 69 GB of 16-byte entries) it runs random 31-mers at 16.7
+// against 16.5 G/s and reads from the text 10 % slower than the single strided quad kernel: without the 32-bit accelerators
+// (dense SA, text, position seeds) the entry settles too few queries for a second launch to pay.  Selected with
+// AWRY_COUNT_KERNEL=twophase / awry_debug_set_count_kernel(3).
+bool wide_two_phase(uint64_t n) { const int m = count_kernel_override(); return m >= 3 && m <= 5 && n < (1ull << 32); }
+// The LF list lcx_quad_reads_kernel appends to on a grid of `grid` blocks (4 waves each), for `total` list slots of survivors.
+// A wave reserves LCX_LF_CHUNK slots at a time with one atomic and fills them in order.  One append is one item per quad
+// (16 per wave at most), and the wave reserves its next chunk only when an append does not fit in what is left, so every
+// chunk it leaves behind holds more than LCX_LF_CHUNK - 16 items; the chunk a wave holds at its end may be almost empty.
+// A wave that reserves c chunks thus appends at least (c - 1) (LCX_LF_CHUNK - 15) items, and the waves append at most
+// `total` items in all (each survivor at most once):
+//   sum_w (c_w - 1) <= floor(total / (LCX_LF_CHUNK - 15)),   chunks <= that + nwaves,
+//   slots = LCX_LF_CHUNK * chunks <= total + 15 * ceil(total / (LCX_LF_CHUNK - 15)) + nwaves * LCX_LF_CHUNK.
+uint64_t lcx_lf_list_bound(uint64_t total, unsigned grid) {
+  const uint64_t per = (uint64_t)LCX_LF_CHUNK - 15, nwaves = 4ull * grid;
+  return total + (total + per - 1) / per * 15 + nwaves * (uint64_t)LCX_LF_CHUNK;
+}
+// the survivor lists of a two-phase launch over n queries on a grid of nblk <= num_cus * 8 blocks (one list per block):
+// `in` (all three arrays) and, with lcx_grid != 0, the LF list `out` of lcx_quad_reads_kernel on a grid of lcx_grid blocks
+void two_phase_lists(Replica& r, hipStream_t s, uint64_t n, unsigned nblk, unsigned lcx_grid, Nt2Survivors* in, Nt2Survivors* out) {
+  Replica::SurvScratch* sc = surv_scratch(r, s);
+  const uint64_t per_block = list_slots_per_block(n, nblk), total = per_block * nblk;
+  const uint64_t fneed = lcx_grid ? lcx_lf_list_bound(total, lcx_grid) : 0;
+  if (sc->cap < total || sc->fcap < fneed) {
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (sc->cap < total) {
+      sc->w.alloc(total); sc->range.alloc(total); sc->q.alloc(total);
+      sc->cap = sc->cap_q = total;
+    }
+    if (sc->fcap < fneed) {
+      sc->fw.alloc(fneed); sc->frange.alloc(fneed); sc->fq.alloc(fneed);
+      sc->fcap = fneed;
+    }
+  }
+  if (!sc->count.p) sc->count.alloc((size_t)r.num_cus * 8);
+  if (lcx_grid && !sc->fcount.p) sc->fcount.alloc(8);  // [0] length of the LF list
+  *in = Nt2Survivors{sc->w.p, sc->range.p, sc->q.p, sc->count.p, per_block};
+  *out = Nt2Survivors{};
+  if (lcx_grid) {
+    *out = Nt2Survivors{sc->fw.p, sc->frange.p, sc->fq.p, sc->fcount.p, sc->fcap};
+    in->lf_count = sc->fcount.p;
+  }
+}
+// blocks of a kernel that are resident at once: its grid (the work is shared out dynamically)
+template <class K>
+unsigned resident_grid(const Replica& r, K kernel) {
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 2; }
+  return (unsigned)r.num_cus * (unsigned)per_cu;
+}
+
+// d_lens != nullptr: read q has d_lens[q] letters (1..L) in its W = ceil(L / 32) words; else every read has L letters
+void launch_count_nt2_long(Replica& r, const uint64_t* d_words, uint64_t n, int L, uint64_t* d_counts, uint64_t* d_range_start,
+                           bool use_seed, hipStream_t s, const uint32_t* d_lens = nullptr) {
+  require(r.dev.alphabet == NUCLEOTIDE, "packed 2-bit queries need a nucleotide index");
+  require(L >= 1 && L <= 1 << 20, "packed read length out of range");
+  if (n == 0) return;
+  if (r.wide) {  // 64-bit rows
+    const bool sdw = use_seed && r.seed_k > 0 && r.dev.seed64 && (d_lens || r.seed_k <= L);
+    const dim3 gw(grid_for(r, n * 4, 256)), bw(256);
+    if (sdw && wide_two_phase(n)) {  // per-lane probe pass, then the quads on what has to be stepped
+      Nt2Survivors sv, fb;
+      const unsigned nblk = (unsigned)r.num_cus * 8;
+      two_phase_lists(r, s, n, nblk, 0u, &sv, &fb);
+      with_flags(d_lens != nullptr, [&](auto R) {
+        hipLaunchKernelGGL((count_nt2_wide_probe_kernel<R(), false>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens, (unsigned long long*)nullptr);
+        hipLaunchKernelGGL((count_nt2_wide_kernel<true, R(), true>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, d_lens, (unsigned long long*)nullptr, sv);
+      });
+      HIP_CHECK(hipGetLastError());
+      return;
+    }
+    with_flags(sdw, d_lens != nullptr, [&](auto S, auto R) {
+      hipLaunchKernelGGL((count_nt2_wide_kernel<S(), R()>), gw, bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, d_lens, (unsigned long long*)nullptr);
+    });
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  const bool sd = use_seed && r.seed_k > 0 && (d_lens || r.seed_k <= L);  // ragged reads decide per read
+  const bool vfy = r.dev.text4 && r.dev.dense_ratio == 1;
+  const dim3 g(grid_for(r, n * 4, 256)), b(256);
+  const int om = count_kernel_override();
+  if (vfy && sd && L - r.seed_k >= 3 && L <= 512 && n < (1ull << 32) && (om < 0 || (om >= 3 && om <= 5))) {
+    // two-phase: a per-lane pass settles the reads their seed entry (plus one SA read and one text window) decides,
+    // the quad kernel works through the rest
+    const unsigned nblk = (unsigned)r.num_cus * 8;  // both phases of the quad schedule use this grid
+    // the pooled pass (lcx_quad_reads_kernel + count_nt2_reads_pool_kernel) holds the prefix sums of the nblk lists in LDS
+    // and numbers the slots of its LF list with u32: it is taken only while both fit
+    const unsigned gl = r.lcx_reads_grid[d_lens != nullptr];
+    const bool lanes = lcx_lanes(r) && gl > 0 && nblk <= (unsigned)LIST_MAX_LISTS && lcx_lf_list_bound(list_slots_per_block(n, nblk) * nblk, gl) <= 0xFFFFFFFFull;
+    Nt2Survivors sv, fb;
+    two_phase_lists(r, s, n, nblk, lanes ? gl : 0u, &sv, &fb);
+    if (!lanes) sv.w = sv.range = nullptr;  // (the probe pass then lists the reads only)
+    const dim3 gq((unsigned)r.num_cus * 8);  // the quad code over what the lanes left
+    with_flags(d_lens != nullptr, [&](auto R) {
+      hipLaunchKernelGGL(count_nt2_reads_probe_kernel<R()>, dim3(nblk), b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens);
+      if (lanes) {
+        hipLaunchKernelGGL(lcx_quad_reads_kernel<R()>, dim3(gl), b, 0, s, r.dev, d_words, L, d_counts, d_range_start, sv, fb, nblk, d_lens);
+        hipLaunchKernelGGL(count_nt2_reads_pool_kernel<R()>, gq, b, 0, s, r.dev, d_words, L, d_counts, d_range_start, fb, d_lens);
+      } else hipLaunchKernelGGL((count_nt2_reads_kernel<true, true, true, R()>), dim3(nblk), b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens);
+    });
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  const Nt2Survivors none{};
+  with_flags(sd, vfy, d_lens != nullptr, [&](auto S, auto V, auto R) {
+    hipLaunchKernelGGL((count_nt2_reads_kernel<S(), V(), false, R()>), g, b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, none, d_lens);
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_count_nt2(Replica& r, const uint64_t* d_words, uint64_t n, int L, uint64_t* d_counts, bool use_seed, hipStream_t s,
+                      unsigned long long* d_tally = nullptr) {
+  require(r.dev.alphabet == NUCLEOTIDE, "packed 2-bit queries need a nucleotide index");
+  require(L >= 1 && L <= 32, "packed k-mer length must be in 1..32");
+  if (n == 0) return;
+  if (r.wide) {  // 64-bit rows: one word per k-mer is the W = 1 case of the wide kernel
+    const bool sdw = use_seed && r.seed_k > 0 && r.dev.seed64 && r.seed_k <= L;
+    const dim3 gw(grid_for(r, n * 4, 256)), bw(256);
+    if (sdw && wide_two_phase(n)) {
+      Nt2Survivors sv, fb;
+      const unsigned nblk = (unsigned)r.num_cus * 8;
+      two_phase_lists(r, s, n, nblk, 0u, &sv, &fb);
+      with_flags(d_tally != nullptr, [&](auto T) {
+        hipLaunchKernelGGL((count_nt2_wide_probe_kernel<false, T()>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, (uint64_t*)nullptr, sv, (const uint32_t*)nullptr, d_tally);
+      });
+      hipLaunchKernelGGL((count_nt2_wide_kernel<true, false, true>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, (uint64_t*)nullptr, (const uint32_t*)nullptr, d_tally, sv);
+      HIP_CHECK(hipGetLastError());
+      return;
+    }
+    with_flags(sdw, [&](auto S) {
+      hipLaunchKernelGGL((count_nt2_wide_kernel<S(), false>), gw, bw, 0, s, r.dev, d_words, n, L, d_counts, (uint64_t*)nullptr, (const uint32_t*)nullptr, d_tally);
+    });
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  // k-mers shorter than the seed table's k: their own complete table ("rung", built on first use) -- the entry IS the
+  // answer, where LF steps from the last letter cost L dependent block reads (GRCh38 scale: 12-mers 5.6 -> 30+ G/s)
+  DevIndex dv = r.dev;
+  bool rung = false;
+  if (use_seed && r.seed_k > L && r.seed.p && n >= 4096 && n < (1ull << 32) && count_kernel_override() < 0)
+    if (const SeedEntry* t = seed_rung(r, L)) { dv.seed = t; dv.seed_k = L; dv.seed_pos = 0; dv.ctx_extra = 0; rung = true; }
+  const bool seeded = rung || (use_seed && r.seed_k > 0 && r.seed_k <= L);
+  const dim3 g(grid_for(r, n * 4, 256)), b(256);
+  // AWRY_COUNT_KERNEL=chunk selects the LDS-staged variant (count_nt2_chunk_kernel).  Measured on MI355X it is
+  // equal at seed k=14 and 23% slower at k=16 (GRCh38-scale): the strided kernel's query words already arrive
+  // as L2 hits, so staging only removes the partial-line result writes and pays chunk drain + refill for it.
+  const int kmode = rung ? 3 : count_kernel_mode(r.dev.bwt_len, r.seed_k, seeded);
+  const bool use_chunk = kmode == 1;
+  if (use_chunk) {
+    unsigned long long* ctr = next_counter(r, s);
+    with_flags(seeded, d_tally != nullptr, [&](auto S, auto T) {
+      hipLaunchKernelGGL((count_nt2_chunk_kernel<S(), T()>), g, b, 0, s, r.dev, d_words, n, L, d_counts, ctr, d_tally);
+    });
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  if (kmode >= 3 && kmode <= 5 && seeded && n < (1ull << 32)) {
+    // two-phase: per-lane seed probes decide most queries, the quad machinery resumes the survivors -- in one launch on
+    // the resident grid, or (modes 4 and 5, for A/B) as the probe and resume kernels on num_cus * 8 blocks / that grid.
+    // The one launch takes the survivor count from LDS and leaves sv.count untouched.
+    // survivors of phase 1 use seed-and-verify whenever its accelerators are resident (cheap: random batches barely
+    // reach phase 2); the single-kernel schedules use it only on request (awry_set_verify_kmers)
+    const bool vfy = r.dev.text4 != nullptr && r.dev.dense_ratio == 1;
+    const bool pair = kmode != 3;
+    const unsigned nblk = (unsigned)r.num_cus * (kmode == 4 ? 8u : (unsigned)r.probe_resume_per_cu[2 * (d_tally != nullptr) + vfy]);
+    Nt2Survivors sv, fb;
+    two_phase_lists(r, s, n, nblk, 0u, &sv, &fb);
+    const dim3 gp(nblk);
+    with_flags(d_tally != nullptr, vfy, [&](auto T, auto V) {
+      if (pair) {
+        hipLaunchKernelGGL((count_nt2_probe_kernel<T(), V()>), gp, b, 0, s, dv, d_words, n, L, d_counts, sv, d_tally);
+        hipLaunchKernelGGL((count_nt2_resume_kernel<T(), V()>), gp, b, 0, s, dv, sv, L, d_counts, d_tally);
+      } else hipLaunchKernelGGL((count_nt2_probe_resume_kernel<T(), V()>), gp, b, 0, s, dv, d_words, n, L, d_counts, sv, d_tally);
+    });
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  if (kmode >= 2 && kmode <= 5) {  // groups of 4 consecutive queries per quad: whole-sector result writes
+    const dim3 g4(grid_for(r, n, 256));
+    const bool verify = r.verify_kmers && r.dev.text4 != nullptr && r.dev.dense_ratio == 1;
+    with_flags(seeded, d_tally != nullptr, verify, [&](auto S, auto T, auto V) {
+      hipLaunchKernelGGL((count_nt2_quad4_kernel<S(), T(), V()>), g4, b, 0, s, r.dev, d_words, n, L, d_counts, d_tally);
+    });
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  with_flags(seeded, d_tally != nullptr, [&](auto S, auto T) {
+    hipLaunchKernelGGL((count_nt2_quad_kernel<S(), T()>), g, b, 0, s, r.dev, d_words, n, L, d_counts, d_tally);
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
+// n ASCII queries of L bytes each, back to back: counts (and status) only.  Nucleotide: packed on the device and served by
+// the packed kernels.  Amino k-mers with a seed table: the two-phase schedule (count_aa_kmer_probe_kernel, then the
+// generic kernel on what it listed).  Anything else: the generic kernel reading its queries at q * L.
+// d_ranges (optional): (start, end) / RS_* words per query for the locate pass, as launch_count_ascii writes them.
+void launch_count_ascii_uniform(Replica& r, const uint8_t* d_q, uint64_t n, uint64_t L, uint64_t* d_counts, uint8_t* d_status, hipStream_t s,
+                                uint64_t* d_ranges = nullptr, unsigned long long* d_tally = nullptr) {
+  if (n == 0) return;
+  require(L >= 1, "query length must be at least 1");
+  static const bool off = getenv("AWRY_AA_KMER") && !strcmp(getenv("AWRY_AA_KMER"), "0");
+  static const bool no_long = getenv("AWRY_AA_LONG") && !strcmp(getenv("AWRY_AA_LONG"), "0");
+  const bool two_phase = !off && r.dev.alphabet == AMINO && L >= (uint64_t)AA_KMER_MIN && L <= (uint64_t)(no_long ? AA_KMER_MAX : AA_KMER_LONG_MAX) &&
+                         r.seed_k >= 1 && (uint64_t)r.seed_k <= L && n < (1ull << 32);
+  Replica::SurvScratch* sc = surv_scratch(r, s);
+  if (r.dev.alphabet == NUCLEOTIDE && !d_ranges && L <= 4096 && n < (1ull << 32)) {
+    // the device half of the packed host path: pack 2 bits per letter, packed kernels, and the generic kernel over the
+    // pack kernel's list for the queries with letters outside ACGT (it also writes their status)
+    const uint64_t W = (L + 31) / 32;
+    if (sc->u_words.n < n * W || sc->u_list.n < n || !sc->u_bad.p) {
+      HIP_CHECK(hipStreamSynchronize(s));
+      if (sc->u_words.n < n * W) sc->u_words.alloc(n * W + n * W / 4);
+      if (sc->u_list.n < n) sc->u_list.alloc(n + n / 4);
+      if (!sc->u_bad.p) sc->u_bad.alloc(2);
+    }
+    HIP_CHECK(hipMemsetAsync(sc->u_bad.p, 0, 16, s));
+    if (d_status) HIP_CHECK(hipMemsetAsync(d_status, 0, n, s));
+    launch_pack_nt2(r, d_q, nullptr, 0, n, n * L, (int)L, (int)W, sc->u_words.p, nullptr, sc->u_bad.p, s, sc->u_list.p);
+    if (L <= 32) launch_count_nt2(r, sc->u_words.p, n, (int)L, d_counts, true, s, nullptr);
+    else launch_count_nt2_long(r, sc->u_words.p, n, (int)L, d_counts, nullptr, true, s, nullptr);
+    const QueryList ql{sc->u_list.p, nullptr, 0, sc->u_bad.p, nullptr, 0};
+    hipLaunchKernelGGL((count_scalar_kernel<NUCLEOTIDE, LIST_GLOBAL>), dim3((unsigned)r.num_cus * 2), dim3(256), 0, s, r.dev, d_q, nullptr, n,
+                       d_counts, nullptr, d_status, 1, L, ql);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  if (!two_phase) {
+    require(!d_tally, "the census is kept by the amino k-mer schedule only");
+    launch_count_ascii(r, d_q, nullptr, n, d_counts, d_ranges, d_status, s, true, L);
+    return;
+  }
+  launch_aa_two_phase(r, d_q, nullptr, n, (int)L, d_counts, d_ranges, d_status, s, d_tally);
+}
+
+// the DFS kernel on a resident grid (lanes draw queries from the work-queue head).  EMIT: the locate pass that writes the
+// leaves of query q to key / val [leaf_off[q], leaf_off[q + 1])
+void launch_count_mismatch(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, int k, uint64_t* d_counts, uint64_t* d_totals,
+                           uint64_t* d_nleaves, uint8_t* d_status, hipStream_t s, unsigned long long* d_tally = nullptr,
+                           const uint64_t* d_leaf_off = nullptr, uint64_t* d_key = nullptr, uint64_t* d_val = nullptr) {
+  if (n == 0) return;
+  unsigned long long* ctr = next_counter(r, s);
+  const bool emit = d_leaf_off != nullptr;
+  const uint64_t want = (n + 255) / 256;
+  with_alphabet(r.dev.alphabet, [&](auto A) {
+    with_flags(emit, [&](auto E) {
+      auto kernel = count_mismatch_kernel<decltype(A)::value, E()>;  // (A is a capture here: its type names the value)
+      const dim3 g((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, resident_grid(r, kernel)))), b(256);
+      hipLaunchKernelGGL(kernel, g, b, 0, s, r.dev, d_q, d_off, n, k, d_counts, d_totals, d_nleaves, d_status, d_leaf_off, d_key, d_val, ctr, d_tally);
+    });
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace

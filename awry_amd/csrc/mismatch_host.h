@@ -1,0 +1,121 @@
+// mismatch_host.h -- shard drivers of the substitution-tolerant count and locate
+// A part of awry_hip.hip (one translation unit): included there, in order, and not on its own.
+#pragma once
+
+namespace {
+
+// ---- substitution-tolerant count / locate (mismatch_kernels.hip.h) ----------------------------------------
+
+void require_mismatches(int k) {
+  if (k < 0 || k > MM_MAX_K) throw ArgError("max_mismatches must be 0, 1 or 2");
+}
+
+// upload one chunk's query bytes and chunk-relative offsets (the generic count path's layout)
+void upload_chunk(Replica& r, ChunkBuffers& cb, const uint8_t* qbytes, const uint64_t* qoff, Shard c) {
+  const uint64_t n = c.hi - c.lo, base = qoff[c.lo], nbytes = qoff[c.hi] - base;
+  cb.h_off.resize(n + 1);
+  for (uint64_t i = 0; i <= n; i++) {
+    if (qoff[c.lo + i] < base || (i && qoff[c.lo + i] < qoff[c.lo + i - 1])) throw ArgError("query offsets must be non-decreasing");
+    cb.h_off[i] = qoff[c.lo + i] - base;
+  }
+  if (cb.q.n < nbytes + 16) cb.q.alloc(nbytes + 16);
+  if (cb.off.n < n + 1) cb.off.alloc(n + 1);
+  if (cb.status.n < n) cb.status.alloc(n);
+  if (nbytes) HIP_CHECK(hipMemcpyAsync(cb.q.p, qbytes + base, nbytes, hipMemcpyHostToDevice, r.stream));
+  HIP_CHECK(hipMemcpyAsync(cb.off.p, cb.h_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, r.stream));
+  cb.h_status.resize(n);
+}
+
+void count_mismatch_shard(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard sh, int k, uint64_t* counts_out) {
+  HIP_CHECK(hipSetDevice(r.device));
+  ChunkBuffers cb;
+  for (Shard c : chunk_queries(qoff, sh.lo, sh.hi)) {
+    const uint64_t n = c.hi - c.lo, w = (uint64_t)(k + 1);
+    upload_chunk(r, cb, qbytes, qoff, c);
+    if (cb.counts.n < n * w) cb.counts.alloc(n * w);
+    launch_count_mismatch(r, cb.q.p, cb.off.p, n, k, cb.counts.p, nullptr, nullptr, cb.status.p, r.stream);
+    HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, r.stream));
+    HIP_CHECK(hipMemcpyAsync(counts_out + c.lo * w, cb.counts.p, n * w * 8, hipMemcpyDeviceToHost, r.stream));
+    HIP_CHECK(hipStreamSynchronize(r.stream));
+    check_status(cb, c.lo);
+  }
+}
+
+// Leaves (row ranges of the variants that occur) a locate chunk may hold on the device; a chunk with more is split in halves
+// and each half redone (one query with more gets what it needs).  Read per call: AWRY_MISMATCH_LEAF_CAP (tests shrink it).
+uint64_t mismatch_leaf_cap() {
+  const char* e = getenv("AWRY_MISMATCH_LEAF_CAP");
+  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
+  return v ? std::min<uint64_t>(v, 1ull << 31) : (1ull << 26);
+}
+
+struct MismatchHits {  // one shard's locate result, in query order
+  std::vector<uint64_t> counts;  // hits per query
+  std::vector<uint64_t> gpos;
+  std::vector<awry_pos_t> pos;
+  std::vector<uint8_t> mm;
+};
+
+// pass 1 (counts, leaves per query), scans, pass 2 (leaves), segmented sort by first row within each query, locate over the
+// flat leaf list, distances per hit.  false: the chunk holds more leaves than the cap and more than one query -- nothing appended
+bool locate_mismatch_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, bool want_pos, bool want_gpos, bool want_mm,
+                           MismatchHits& out) {
+  const hipStream_t s = r.stream;
+  const uint64_t n = c.hi - c.lo;
+  ChunkBuffers cb;
+  upload_chunk(r, cb, qbytes, qoff, c);
+  DevBuf<uint64_t> totals(n), nleaves(n), hit_off(n + 1), leaf_off(n + 1), scratch(scan_tiles(n) + 1);
+  launch_count_mismatch(r, cb.q.p, cb.off.p, n, k, nullptr, totals.p, nleaves.p, cb.status.p, s);
+  launch_scan(r, totals.p, n, hit_off.p, scratch.p, s);
+  uint64_t total = 0, nleaf = 0;
+  HIP_CHECK(hipMemcpyAsync(&total, hit_off.p + n, 8, hipMemcpyDeviceToHost, s));
+  launch_scan(r, nleaves.p, n, leaf_off.p, scratch.p, s);
+  HIP_CHECK(hipMemcpyAsync(&nleaf, leaf_off.p + n, 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  check_status(cb, c.lo);
+  if (nleaf > mismatch_leaf_cap() && n > 1) return false;
+  require(nleaf < (1ull << 32), "one query has 2^32 or more occurring variants");
+  const size_t at_q = out.counts.size(), at_h = out.gpos.size();
+  out.counts.resize(at_q + n);
+  HIP_CHECK(hipMemcpyAsync(out.counts.data() + at_q, totals.p, n * 8, hipMemcpyDeviceToHost, s));
+  if (total) {
+    DevBuf<uint64_t> key(nleaf), val(nleaf), key2(nleaf), val2(nleaf), width(nleaf), leaf_hit_off(nleaf + 1), lscratch(scan_tiles(nleaf) + 1);
+    launch_count_mismatch(r, cb.q.p, cb.off.p, n, k, nullptr, nullptr, nullptr, nullptr, s, nullptr, leaf_off.p, key.p, val.p);
+    // DFS from the right end does not visit the leaves in row order: sort each query's leaves by their first row
+    unsigned end_bit = 1;
+    while (end_bit < 64 && (r.dev.bwt_len >> end_bit)) end_bit++;
+    size_t tmp_bytes = 0;
+    HIP_CHECK(rocprim::segmented_radix_sort_pairs(nullptr, tmp_bytes, key.p, key2.p, val.p, val2.p, (unsigned)nleaf, (unsigned)n, leaf_off.p,
+                                                  leaf_off.p + 1, 0, end_bit, s));
+    DevBuf<uint8_t> tmp(std::max<size_t>(tmp_bytes, 8));
+    HIP_CHECK(rocprim::segmented_radix_sort_pairs(tmp.p, tmp_bytes, key.p, key2.p, val.p, val2.p, (unsigned)nleaf, (unsigned)n, leaf_off.p,
+                                                  leaf_off.p + 1, 0, end_bit, s));
+    hipLaunchKernelGGL(mm_leaf_widths_kernel, dim3(grid_for(r, nleaf, 256)), dim3(256), 0, s, val2.p, nleaf, width.p);
+    HIP_CHECK(hipGetLastError());
+    launch_scan(r, width.p, nleaf, leaf_hit_off.p, lscratch.p, s);
+    DevBuf<uint64_t> d_gpos(total), d_pos(want_pos ? 2 * total : 0);
+    DevBuf<uint8_t> d_mm(want_mm ? total : 0);
+    launch_locate(r, key2.p, 1, leaf_hit_off.p, nleaf, total, d_gpos.p, d_pos.p, s);
+    if (want_mm) {
+      hipLaunchKernelGGL(mm_hit_distance_kernel, dim3(grid_for(r, total, 256)), dim3(256), 0, s, leaf_hit_off.p, val2.p, nleaf, total, d_mm.p);
+      HIP_CHECK(hipGetLastError());
+    }
+    if (want_gpos) { out.gpos.resize(at_h + total); HIP_CHECK(hipMemcpyAsync(out.gpos.data() + at_h, d_gpos.p, total * 8, hipMemcpyDeviceToHost, s)); }
+    if (want_pos) { out.pos.resize(at_h + total); HIP_CHECK(hipMemcpyAsync(out.pos.data() + at_h, d_pos.p, total * 16, hipMemcpyDeviceToHost, s)); }
+    if (want_mm) { out.mm.resize(at_h + total); HIP_CHECK(hipMemcpyAsync(out.mm.data() + at_h, d_mm.p, total, hipMemcpyDeviceToHost, s)); }
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  return true;
+}
+
+void locate_mismatch_range(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, bool want_pos, bool want_gpos, bool want_mm,
+                           MismatchHits& out) {
+  if (c.hi <= c.lo) return;
+  if (locate_mismatch_chunk(r, qbytes, qoff, c, k, want_pos, want_gpos, want_mm, out)) return;
+  const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order
+  locate_mismatch_range(r, qbytes, qoff, Shard{c.lo, mid}, k, want_pos, want_gpos, want_mm, out);
+  locate_mismatch_range(r, qbytes, qoff, Shard{mid, c.hi}, k, want_pos, want_gpos, want_mm, out);
+}
+
+}  // namespace
