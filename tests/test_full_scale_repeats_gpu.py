@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from awry_amd.fm_index import FmIndex
+from tests import mismatch_ref as mr
 from tests import synth
 
 pytestmark = pytest.mark.gpu
@@ -22,6 +23,8 @@ pytestmark = pytest.mark.gpu
 N_TEXT, RECORDS, TEXT_SEED = 3_100_000_000, 25, 0xA5A50000 + 6  # bench.py: WORKLOADS["grch38-repeats"], workload_text()
 ORACLE_HITS = 2_000_000  # the oracle's locate budget: satellite windows have 10^4 .. 10^5 hits each
 THREADS = 16
+MM_HIT_BUDGET = 1 << 24  # hits one mismatch locate call of the sample may return (a host-memory guard: 25 B per hit, not a tolerance)
+MM_LIGHT = 4096          # sample queries with at most this many hits are all located; heavier ones while the budget lasts
 # (length, present windows, uniform windows the heavy set is drawn from, most of them kept at 2..8 / at more than 8 hits, seed)
 GROUPS = ((31, 100_000, 400_000, 20_000, 5_000, 31), (101, 50_000, 200_000, 10_000, 5_000, 101))
 
@@ -98,6 +101,36 @@ def run_batch(ix, b):
     return out
 
 
+def mismatch_sample(text, oi, q31_group):
+    """the substitution-tolerant legs' sample, with the oracle's variant-enumeration counts (mismatch_ref.oracle_counts_batch)
+    while its index is open: ~1 500 31-mers (present, 1 and 2 planted substitutions, random, and the exact path's heavy set:
+    windows of the repeat families, which meet their diverged copies), 500 16-mers (at 3.1 Gbp most of a 16-mer's 1 985
+    variants at k = 2 occur) and 300 101-bp reads (k = 1 on all, k = 2 on 50).
+    -> [(name, queries uint8[., L], k, counts uint64[., k + 1], rows to locate, [(row, oracle_locate result)])]"""
+    t0 = time.time()
+    rng = np.random.default_rng(77)
+    s31 = synth.sampled_queries(text, 1000, 31, 771)
+    q31 = np.concatenate([s31[:400], substitute(s31[400:700], rng), substitute(substitute(s31[700:], rng), rng),
+                          synth.random_queries(300, 31, 0, 772), q31_group[-200:]])
+    s16 = synth.sampled_queries(text, 250, 16, 773)
+    q16 = np.concatenate([s16, synth.random_queries(250, 16, 0, 774)])
+    s101 = synth.sampled_queries(text, 300, 101, 775)
+    reads = np.concatenate([s101[:100], substitute(s101[100:200], rng), substitute(substitute(s101[200:], rng), rng)])
+    reads = reads[rng.permutation(len(reads))]
+    legs = []
+    for name, q, k, n_order in (("31-mers", q31, 2, 24), ("16-mers", q16, 2, 24), ("reads", reads, 1, 8), ("reads", reads[:50], 2, 4)):
+        counts, _ = mr.oracle_counts_batch(oi, [bytes(r) for r in q], k, 0, THREADS)
+        ks = (1, 2) if k == 2 and name != "reads" else (k,)
+        for kk in ks:
+            tot = counts[:, :kk + 1].sum(axis=1).astype(np.int64)
+            rows, n_heavy = mr.budgeted_rows(tot, MM_LIGHT, MM_HIT_BUDGET, 780 + kk)
+            cand = np.flatnonzero((tot >= 1) & (tot <= 3000))
+            pick = np.random.default_rng(790 + kk).choice(cand, size=min(n_order, len(cand)), replace=False)
+            order = [(int(i), mr.oracle_locate(oi, bytes(q[i]), kk, 0)) for i in np.sort(pick)]
+            legs.append((name, q, kk, counts[:, :kk + 1], rows, n_heavy, order))
+    return legs, time.time() - t0
+
+
 @pytest.fixture(scope="module")
 def repeats(oracle, tmp_path_factory):
     import torch
@@ -146,8 +179,12 @@ def repeats(oracle, tmp_path_factory):
             so[1:] = np.cumsum(b["lens"][sample])
             sb = qb[np.repeat(qo[:-1][sample].astype(np.int64) - so[:-1].astype(np.int64), b["lens"][sample]) + np.arange(int(so[-1]))]
             ooff, ogpos, opos, _ = oi.parallel_locate(sb, so, THREADS)
+            t_mm = time.time()
+            mm_legs, mm_ref_s = mismatch_sample(text, oi, groups[0][0])
         finally:
             oi.close()
+        t0 += time.time() - t_mm  # (setup_s below stays the exact legs' setup; the mismatch sample reports its own time)
+        b.update(mm_legs=mm_legs, mm_ref_s=mm_ref_s)
         b.update(text=text, starts=np.array(st, dtype=np.uint64), want=want, sample=sample, oracle_loc=(ooff, ogpos, opos),
                  n_heavy=len(heavy), setup_s=time.time() - t0)
         yield ix, b
@@ -236,3 +273,54 @@ def test_configurations_agree(repeats):
     assert not ix.verify_enabled() and ix.locate_sa_ratio() == ix.suffix_array_compression_ratio()  # (no dense SA: the file's)
     same(run_batch(ix, b), "verify off, ratio 0")
     print("repeat-rich full scale: three more configurations %.1f s" % (time.time() - t0))
+
+
+def test_mismatch_legs_match_the_oracle(repeats):
+    """substitution-tolerant count and locate on the full-size index (rows beyond 2^31, the dense-SA / seed-and-verify
+    locate fed from leaf lists): counts are the oracle's over all variants; the located hits are checked against the text
+    itself (as many per query and distance as counted, distinct, every window free of '$' and at the reported distance),
+    which is set equality with the definition; order and (record, offset) are mismatch_ref.oracle_locate's on a few dozen.
+    Then 10^6 device-resident sampled 31-mers: column 0 at k = 2 is the exact count (which this module proves against the
+    oracle), and columns 0..1 at k = 1 are columns 0..1 at k = 2."""
+    ix, b = repeats
+    t0 = time.time()
+    text, starts = b["text"], b["starts"]
+    report = []
+    for name, q, k, want, rows, n_heavy, order in b["mm_legs"]:
+        qb, qo = synth.fixed_to_csr(q)
+        got = ix.parallel_count_mismatch_csr(qb, qo, k)
+        bad = np.flatnonzero((got != want).any(axis=1))
+        assert len(bad) == 0, (name, k, len(bad), bad[:5], got[bad[:5]], want[bad[:5]])
+        sb, so = synth.fixed_to_csr(q[rows])
+        off, g, p, d = ix.parallel_locate_mismatch_csr(sb, so, k)
+        mr.assert_hits_are_the_definition(text, 0, q[rows], k, want[rows], off, g, d)
+        si = np.searchsorted(starts, g, side="right") - 1
+        assert np.array_equal(p[:, 0], si.astype(np.uint64)) and np.array_equal(p[:, 1], g - starts[si]), (name, k)
+        at = {int(r): j for j, r in enumerate(rows)}
+        for i, (og, op, od) in order:
+            a, e = int(off[at[i]]), int(off[at[i] + 1])
+            assert np.array_equal(g[a:e], og) and np.array_equal(p[a:e], op) and np.array_equal(d[a:e], od), (name, k, i)
+        report.append("%s k = %d: %d counted, %d located (%d heavy), %d hits, order on %d" % (name, k, len(q), len(rows), n_heavy, len(g), len(order)))
+    legs = {(name, k): (want, n_heavy) for name, q, k, want, rows, n_heavy, order in b["mm_legs"]}
+    assert len(b["mm_legs"][0][1]) >= 1500 and legs[("31-mers", 2)][1] >= 10, "the 31-mer sample should hold located queries with thousands of hits"
+    assert float(np.median(legs[("16-mers", 2)][0].sum(axis=1))) > 500
+    # consistency on a device-resident batch
+    n = 1_000_000
+    q2d = synth.sampled_queries(text, n, 31, 799)
+    qb, qo = synth.fixed_to_csr(q2d)
+    d_q, d_o = ix.dev_upload(np.concatenate([qb, np.zeros(16, np.uint8)])), ix.dev_upload(qo)
+    d_c, d_e = ix.dev_malloc(8 * n * 3), ix.dev_malloc(8 * n)
+    try:
+        ix.dev_count_ascii(d_q, d_o, n, d_e)
+        ix.dev_count_mismatch(d_q, d_o, n, 2, d_c)
+        ix.dev_synchronize()
+        exact, c2 = ix.dev_download(d_e, (n,), np.uint64), ix.dev_download(d_c, (n, 3), np.uint64)
+        ix.dev_count_mismatch(d_q, d_o, n, 1, d_c)
+        ix.dev_synchronize()
+        c1 = ix.dev_download(d_c, (n, 2), np.uint64)
+    finally:
+        for ptr in (d_q, d_o, d_c, d_e):
+            ix.dev_free(ptr)
+    assert (exact >= 1).all() and np.array_equal(c2[:, 0], exact) and np.array_equal(c1, c2[:, :2])
+    print("repeat-rich full scale, mismatch legs: reference %.1f s, GPU legs and text checks %.1f s; %s; 10^6 resident 31-mers: %d hits at k = 2"
+          % (b["mm_ref_s"], time.time() - t0, "; ".join(report), int(c2.sum())))

@@ -1389,6 +1389,54 @@ def test_grch38_scale_101bp_reads(oracle, tmp_path):
     assert np.array_equal(results[0][0], results[1][0]) and np.array_equal(results[0][1], results[1][1])
 
 
+def _swissprot_mismatch_leg(ix, oi, text, st):
+    """substitution-tolerant search on the 9e7-residue index (the 219-VGPR amino kernel with u32 Occ values at the size it is
+    meant for): 400 queries of 5, 6, 8 and 12 residues -- windows of the text (some across a record join: they hold X) and
+    random ones, every fifth with an X put in -- for k = 1, 2.  Counts against the oracle over all variants (26 641 per 12-mer
+    at k = 2); locate against the text itself (mismatch_ref.assert_hits_are_the_definition) under a hit budget of 2^24 per
+    call (a host-memory guard: every query with at most 4 096 hits, heavier ones in a seeded order while it lasts); order
+    and (record, offset) against mismatch_ref.oracle_locate on a dozen.  On i.i.d. residues the 5- and 6-mers have thousands
+    of approximate hits; the 12-mers check the deep, narrow DFS."""
+    import time
+    from tests import mismatch_ref as mr
+    t0 = time.time()
+    rng = np.random.default_rng(1212)
+    starts = np.array(st, dtype=np.uint64)
+    n = len(text) - 1
+    report, n_order = [], 0
+    for L in (5, 6, 8, 12):
+        pos = rng.integers(0, n - L, size=50)
+        pos[:5] = starts[rng.integers(1, len(starts), size=5)].astype(np.int64) - rng.integers(1, L, size=5)  # across a join
+        q = np.concatenate([text[pos[:, None] + np.arange(L)[None, :]], synth.random_queries(50, L, 1, 1200 + L)])
+        q[::5, rng.integers(0, L)] = ord("X")
+        want, _ = mr.oracle_counts_batch(oi, [bytes(r) for r in q], 2, 1, 16)
+        qb, qo = synth.fixed_to_csr(q)
+        for k in (1, 2):
+            got = ix.parallel_count_mismatch_csr(qb, qo, k)
+            bad = np.flatnonzero((got != want[:, :k + 1]).any(axis=1))
+            assert len(bad) == 0, (L, k, len(bad), bad[:5], got[bad[:5]], want[bad[:5]])
+            tot = want[:, :k + 1].sum(axis=1).astype(np.int64)
+            rows, n_heavy = mr.budgeted_rows(tot, 4096, 1 << 24, 1300 + 10 * L + k)
+            sb, so = synth.fixed_to_csr(q[rows])
+            off, g, p, d = ix.parallel_locate_mismatch_csr(sb, so, k)
+            mr.assert_hits_are_the_definition(text, 1, q[rows], k, want[rows], off, g, d)
+            si = np.searchsorted(starts, g, side="right") - 1
+            assert np.array_equal(p[:, 0], si.astype(np.uint64)) and np.array_equal(p[:, 1], g - starts[si]), (L, k)
+            cand = np.flatnonzero((tot[rows] >= 1) & (tot[rows] <= 3000))
+            for j in cand[:3]:
+                og, op, od = mr.oracle_locate(oi, bytes(q[rows[j]]), k, 1)
+                a, e = int(off[j]), int(off[j + 1])
+                assert np.array_equal(g[a:e], og) and np.array_equal(p[a:e], op) and np.array_equal(d[a:e], od), (L, k, j)
+            n_order += min(3, len(cand))
+            if k == 2 and L in (5, 6):  # the queries with thousands of hits are located, not only counted
+                assert n_heavy > 0 and int(tot[rows].max()) > 4096, (L, n_heavy)
+            report.append("L = %d k = %d: %d located (%d heavy), %d hits" % (L, k, len(rows), n_heavy, len(g)))
+        if L == 5:
+            assert int(np.median(want.sum(axis=1))) > 1000, "5-mers should have thousands of approximate hits"
+    assert n_order >= 12
+    print("swiss-prot scale, mismatch leg: %.1f s; %s" % (time.time() - t0, "; ".join(report)))
+
+
 def test_swissprot_scale_amino_12mers(oracle, tmp_path):
     """BASELINE.json configs[3] at its own size: 9e7 residues in 2.5e5 records, 12-mers through awry_count_batch (the amino
     k-mer schedule), the device entry point and awry_locate_batch; properties on everything, the oracle on 1e5 queries"""
@@ -1416,6 +1464,7 @@ def test_swissprot_scale_amino_12mers(oracle, tmp_path):
     sample = np.sort(rng.choice(len(q2d), size=100_000, replace=False))
     sb, so = synth.fixed_to_csr(q2d[sample])
     ooff, ogpos, opos, _ = oi.parallel_locate(sb, so, 8)
+    _swissprot_mismatch_leg(ix, oi, text, st)
     oi.close()
     assert np.array_equal(np.diff(ooff), counts[sample])
     assert np.array_equal(np.concatenate([g[int(off[i]):int(off[i + 1])] for i in sample]), ogpos)

@@ -30,6 +30,63 @@ def test_variant_enumeration_sizes():
     assert mr.variants(b"r", 0) == [b"N"]
 
 
+ODD_QUERIES = {0: [b"ACGTNacgu", b"r", b"ACGTRYKMSWBDHVN", b"acgtnnnnacgt", b"UUAGC", b"AC", b"G", b"ACGTACGTACGTACGTACGTACGTACGTACG"],
+               1: [b"MKVx", b"b", b"WYACD", b"mkvBZJOU", b"ACGU", b"XXX", b"L"]}
+
+
+@pytest.mark.parametrize("alphabet", [0, 1])
+def test_vectorised_enumerator_equals_variants(alphabet):
+    """the same strings in the same order as the itertools enumerator, for N / X, lower case, U and IUPAC bytes and d > L"""
+    for q in ODD_QUERIES[alphabet]:
+        for d in (0, 1, 2, 3):
+            a = mr.variants_array(q, d, alphabet)
+            assert a.dtype == np.uint8 and a.shape[1] == len(q)
+            want = mr.variants(q, d, alphabet) if d <= len(q) else []
+            assert [bytes(r) for r in a] == want, (q, d)
+            assert len(set(want)) == len(want)
+    L, na = 31, 4
+    assert len(mr.variants_array(b"A" * L, 2, 0)) == L * (L - 1) // 2 * na * na
+    assert len(mr.variants_array(b"M" * 12, 2, 1)) == 66 * 400
+
+
+@pytest.mark.parametrize("alphabet,n,recs,nfrac,seed", [(0, 120_000, 4, 0.02, 11), (1, 60_000, 5, 0.01, 12)])
+def test_oracle_batch_reference_equals_brute_force_and_oracle_locate(oracle, alphabet, n, recs, nfrac, seed):
+    """oracle_counts_batch / oracle_search_batch (chunked: max_bytes forces several oracle calls) against the definition, and
+    the batch's hit lists against oracle_locate"""
+    text, st, hd = synth.make_text(n, alphabet, seed, recs, nfrac)
+    oi = oracle.OracleIndex.from_text(text, alphabet, 4, 0, st, hd)
+    rng = np.random.default_rng(seed)
+    lens = (1, 2, 3, 6, 9, 14, 31) if alphabet == 0 else (1, 2, 3, 4, 6, 9)
+    qs = list(ODD_QUERIES[alphabet]) + [b""]
+    for L in lens:
+        qs += [bytes(q) for q in synth.sampled_queries(text, 2, L, seed + L, alphabet=alphabet)]
+        qs += [bytes(q) for q in synth.random_queries(1, L, alphabet, seed + L)]
+        q = bytearray(synth.sampled_queries(text, 1, L, seed + 50 + L, alphabet=alphabet)[0])
+        for _ in range(min(2, L)):
+            j = int(rng.integers(0, L))
+            q[j] = ord("C") if q[j] != ord("C") else ord("A")
+        qs.append(bytes(q))
+    qs += [bytes(text[s - 4:s + 5]) for s in st[1:]] + [bytes(text[st[1] - 2:st[1] + 3]).lower()]
+    amb = np.flatnonzero(text[:-1] == (ord("N") if alphabet == 0 else ord("X")))
+    qs.append(bytes(text[int(amb[0]) - 5:int(amb[0]) + 3]))
+    for k in (0, 1, 2):
+        counts, leaves, off, g, p, d = mr.oracle_search_batch(oi, qs, k, alphabet, 4, True, max_bytes=20_000)
+        c2, l2 = mr.oracle_counts_batch(oi, qs, k, alphabet, 4)
+        assert np.array_equal(c2, counts) and np.array_equal(l2, leaves)
+        assert counts.shape == (len(qs), k + 1) and int(off[-1]) == len(g) == len(p) == len(d)
+        for i, q in enumerate(qs):
+            want, pos, dist = mr.brute_force(text, q, k, alphabet)
+            assert np.array_equal(counts[i], want), (q, k, counts[i], want)
+            a, b = int(off[i]), int(off[i + 1])
+            order = np.argsort(g[a:b], kind="stable")
+            assert np.array_equal(g[a:b][order].astype(np.int64), pos) and np.array_equal(d[a:b][order], dist), (q, k)
+            if len(q) and (i % 3 == 0 or len(q) <= 3):
+                og, op, od = mr.oracle_locate(oi, q, k, alphabet)
+                assert np.array_equal(g[a:b], og) and np.array_equal(p[a:b], op) and np.array_equal(d[a:b], od), (q, k)
+                assert leaves[i] <= len(og) and (leaves[i] > 0) == (len(og) > 0)
+    assert int(leaves.max()) > 100
+
+
 @pytest.mark.parametrize("alphabet,n,recs,nfrac,seed", [(0, 60_000, 3, 0.02, 1), (0, 20_000, 1, 0.0, 2), (1, 30_000, 4, 0.01, 3)])
 def test_brute_force_agrees_with_variant_enumeration(oracle, alphabet, n, recs, nfrac, seed):
     text, st, hd = synth.make_text(n, alphabet, seed, recs, nfrac)
