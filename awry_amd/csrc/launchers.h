@@ -56,6 +56,7 @@ void launch_pack_nt2(Replica& r, const uint8_t* d_ascii, const uint64_t* d_off, 
 // is listed).  d_ranges (optional): RS_* words / row starts for the locate pass, in the generic kernel's layout.
 void launch_aa_two_phase(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, int L, uint64_t* d_counts, uint64_t* d_ranges,
                          uint8_t* d_status, hipStream_t s, unsigned long long* d_tally) {
+  const ScratchLock scratch_lock(r, s);
   Replica::SurvScratch* sc = surv_scratch(r, s);
   const unsigned nblk = (unsigned)r.num_cus * 8;
   const uint64_t per_block = list_slots_per_block(n, nblk);
@@ -171,7 +172,8 @@ uint64_t lcx_lf_list_bound(uint64_t total, unsigned grid) {
   return total + (total + per - 1) / per * 15 + nwaves * (uint64_t)LCX_LF_CHUNK;
 }
 // the survivor lists of a two-phase launch over n queries on a grid of nblk <= num_cus * 8 blocks (one list per block):
-// `in` (all three arrays) and, with lcx_grid != 0, the LF list `out` of lcx_quad_reads_kernel on a grid of lcx_grid blocks
+// `in` (all three arrays) and, with lcx_grid != 0, the LF list `out` of lcx_quad_reads_kernel on a grid of lcx_grid blocks.
+// The caller holds the stream's ScratchLock until it has queued the kernels that take these pointers.
 void two_phase_lists(Replica& r, hipStream_t s, uint64_t n, unsigned nblk, unsigned lcx_grid, Nt2Survivors* in, Nt2Survivors* out) {
   Replica::SurvScratch* sc = surv_scratch(r, s);
   const uint64_t per_block = list_slots_per_block(n, nblk), total = per_block * nblk;
@@ -210,6 +212,7 @@ void launch_count_nt2_long(Replica& r, const uint64_t* d_words, uint64_t n, int 
   require(r.dev.alphabet == NUCLEOTIDE, "packed 2-bit queries need a nucleotide index");
   require(L >= 1 && L <= 1 << 20, "packed read length out of range");
   if (n == 0) return;
+  const ScratchLock scratch_lock(r, s);
   if (r.wide) {  // 64-bit rows
     const bool sdw = use_seed && r.seed_k > 0 && r.dev.seed64 && (d_lens || r.seed_k <= L);
     const dim3 gw(grid_for(r, n * 4, 256)), bw(256);
@@ -268,6 +271,7 @@ void launch_count_nt2(Replica& r, const uint64_t* d_words, uint64_t n, int L, ui
   require(r.dev.alphabet == NUCLEOTIDE, "packed 2-bit queries need a nucleotide index");
   require(L >= 1 && L <= 32, "packed k-mer length must be in 1..32");
   if (n == 0) return;
+  const ScratchLock scratch_lock(r, s);
   if (r.wide) {  // 64-bit rows: one word per k-mer is the W = 1 case of the wide kernel
     const bool sdw = use_seed && r.seed_k > 0 && r.dev.seed64 && r.seed_k <= L;
     const dim3 gw(grid_for(r, n * 4, 256)), bw(256);
@@ -357,6 +361,7 @@ void launch_count_ascii_uniform(Replica& r, const uint8_t* d_q, uint64_t n, uint
   static const bool no_long = getenv("AWRY_AA_LONG") && !strcmp(getenv("AWRY_AA_LONG"), "0");
   const bool two_phase = !off && r.dev.alphabet == AMINO && L >= (uint64_t)AA_KMER_MIN && L <= (uint64_t)(no_long ? AA_KMER_MAX : AA_KMER_LONG_MAX) &&
                          r.seed_k >= 1 && (uint64_t)r.seed_k <= L && n < (1ull << 32);
+  const ScratchLock scratch_lock(r, s);
   Replica::SurvScratch* sc = surv_scratch(r, s);
   if (r.dev.alphabet == NUCLEOTIDE && !d_ranges && L <= 4096 && n < (1ull << 32)) {
     // the device half of the packed host path: pack 2 bits per letter, packed kernels, and the generic kernel over the

@@ -128,8 +128,13 @@ struct Replica {
     // head is free again by the time the ring comes back to it, however many launches other streams have in flight
     DevBuf<unsigned long long> counters;
     unsigned counter_seq = 0;
+    // Held by a launch helper from the moment it reads these buffers until its kernels are queued (ScratchLock), growth
+    // included: two host threads that drive ONE stream -- the replica's own in the unpipelined host drivers, the NULL stream
+    // of two device-resident callers -- then never launch with a list the other has just freed.  Recursive: the uniform entry
+    // point holds it around the packed launchers, which take it again.  Never contended when a stream has one driver.
+    std::recursive_mutex mu;
   };
-  std::mutex scratch_mu;
+  std::mutex scratch_mu;  // the map below and the head ring's sequence numbers
   std::map<hipStream_t, std::unique_ptr<SurvScratch>> scratch;
   int seed_k = 0;
   int num_cus = 256;
@@ -213,6 +218,12 @@ Replica::SurvScratch* surv_scratch(Replica& r, hipStream_t s) {
   if (!slot) slot = std::make_unique<Replica::SurvScratch>();
   return slot.get();
 }
+
+// exclusive use of the scratch of stream `s` for the rest of the scope: read, grow and launch as one step (SurvScratch::mu)
+struct ScratchLock {
+  std::unique_lock<std::recursive_mutex> lk;
+  ScratchLock(Replica& r, hipStream_t s) : lk(surv_scratch(r, s)->mu) {}
+};
 
 unsigned long long* next_counter(Replica& r, hipStream_t s) {
   Replica::SurvScratch* sc = surv_scratch(r, s);

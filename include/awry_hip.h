@@ -232,7 +232,18 @@ void awry_host_memcpy(void *dst, const void *src, uint64_t bytes); /* memcpy cut
  *      `stream` (a hipStream_t, NULL = default stream) and NOT synchronised.  Scratch (survivor lists, work-queue
  *      heads) is kept per stream, so any number of launches may be in flight across streams.  Query byte buffers
  *      (d_qbytes, d_ascii) are read in aligned 8-byte words: they must be readable up to 8 bytes past the last
- *      query (allocations of awry_dev_malloc and hipMalloc are) ------------------------------------------------ */
+ *      query (allocations of awry_dev_malloc and hipMalloc are).
+ *      What a caller may do at the same time:
+ *      - streams: any number of streams per replica, each with any number of launches queued; a call that has to grow its
+ *        stream's scratch first waits for that stream alone (hipStreamSynchronize), then frees and reallocates;
+ *      - host threads: any number, on the same or on different streams and replicas, next to threads inside the batch and
+ *        scalar entry points above.  The handle is immutable after awry_set_devices; the awry_set_* / awry_debug_* knobs and
+ *        awry_set_devices itself are NOT safe beside running queries;
+ *      - one stream (the NULL stream included -- what a caller that passes no stream gets) from two host threads: safe for
+ *        the library's own state -- an entry point reads, grows and launches with its stream's scratch as one step under
+ *        a lock of that stream, and hands out work-queue heads in launch order -- but the two threads' launches are queued
+ *        in whatever order the threads arrive, so the buffers a caller passes must not be shared between them unless the
+ *        caller orders the threads itself. ----------------------------------------------------------------------- */
 int awry_replica_device(const awry_index_t *idx, int slot);
 /* fixed-length ACGT reads, ASCII n*L bytes -> n * ceil(L/32) packed u64 words (letter j in word j/32, bits 2(j%32));
  * *d_bad (u64 on device, caller-zeroed) counts queries with other bytes */

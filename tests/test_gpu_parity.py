@@ -457,9 +457,11 @@ def test_dense_device_sa_does_not_change_locations(oracle, tmp_path, alphabet):
 
 
 @pytest.mark.parametrize("L", [12, 31, 32, 40, 101])
-def test_host_batch_fast_path_equals_generic(oracle, L, monkeypatch):
-    """parallel_count on fixed-length batches takes the pipelined packed path; chunks with N / IUPAC / lower-case / U
-    fall back per chunk to the generic kernel.  Both must give the oracle's counts."""
+def test_host_batch_fast_path_equals_generic(oracle, L):
+    """parallel_count on fixed-length batches takes the pipelined packed path; in a chunk that holds N / IUPAC / lower-case /
+    U, the queries with such letters are redone by the generic kernel (the per-chunk fallback -- what "generic" means here).
+    Clean and dirty batches must both give the oracle's counts.  The generic host DRIVERS (AWRY_HOST_PATH=generic, read
+    once per process) are not run here: tests/test_inflight_gpu.py runs them in a child process."""
     text, st, hd = synth.make_text(400000, 0, 61, 3, 0.05)
     ix = gpu_index(text, 0, 8, 0, st, hd)
     oi = oracle.OracleIndex.from_text(text, 0, 8, 0, st, hd)
