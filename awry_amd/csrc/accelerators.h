@@ -39,26 +39,30 @@ int default_seed_k(const HostIndex& h) {
   return k;
 }
 
-// the complete sigma^k table of (first row, count + BWT symbol of a singleton) entries for a 32-bit-row replica, built
-// level by level on the replica's own stream (see seed_extend_kernel); synchronous
-void build_seed_table(Replica& r, bool nt, int k, DevBuf<SeedEntry>& out) {
+// the complete sigma^k table of (first row, count + BWT symbol of a singleton) entries -- SeedEntry for a 32-bit-row replica,
+// SeedEntry64 (nucleotide only) for a wide-row one -- built level by level on the replica's own stream (see seed_extend_kernel);
+// synchronous
+template <class Entry>
+void build_seed_table(Replica& r, bool nt, int k, DevBuf<Entry>& out) {
+  constexpr bool wide = std::is_same<Entry, SeedEntry64>::value;
   const uint64_t sigma = nt ? 4 : AA_SEED_SIGMA;
   uint64_t nfinal = 1;
   for (int j = 0; j < k; j++) nfinal *= sigma;
-  DevBuf<SeedEntry> a(nfinal), b(std::max<uint64_t>(sigma, nfinal / sigma));
+  DevBuf<Entry> a(nfinal), b(std::max<uint64_t>(sigma, nfinal / sigma));
   // level j lands in `a` when (k - j) is even, so the last level is in `a`
-  SeedEntry* cur = ((k - 1) % 2 == 0) ? a.p : b.p;
-  if (nt) hipLaunchKernelGGL(seed_level1_kernel, dim3(1), dim3(256), 0, r.stream, r.dev, cur);
-  else hipLaunchKernelGGL(aa_seed_level1_kernel, dim3(1), dim3(256), 0, r.stream, r.dev, cur);
+  Entry* cur = ((k - 1) % 2 == 0) ? a.p : b.p;
+  if (nt) hipLaunchKernelGGL(seed_level1_kernel<Entry>, dim3(1), dim3(256), 0, r.stream, r.dev, cur);
+  else if constexpr (!wide) hipLaunchKernelGGL(aa_seed_level1_kernel, dim3(1), dim3(256), 0, r.stream, r.dev, cur);
   uint64_t nchild = sigma;
   for (int j = 2; j <= k; j++) {
-    SeedEntry* nxt = ((k - j) % 2 == 0) ? a.p : b.p;
+    Entry* nxt = ((k - j) % 2 == 0) ? a.p : b.p;
     nchild *= sigma;
-    if (nt) hipLaunchKernelGGL(seed_extend_kernel, dim3(grid_for(r, nchild * 4, 256)), dim3(256), 0, r.stream, r.dev, cur, nxt, nchild);
-    else hipLaunchKernelGGL(aa_seed_extend_kernel, dim3(grid_for(r, nchild, 256)), dim3(256), 0, r.stream, r.dev, cur, nxt, nchild);
+    if (nt) hipLaunchKernelGGL(seed_extend_kernel<Entry>, dim3(grid_for(r, nchild * 4, 256)), dim3(256), 0, r.stream, r.dev, cur, nxt, nchild);
+    else if constexpr (!wide) hipLaunchKernelGGL(aa_seed_extend_kernel, dim3(grid_for(r, nchild, 256)), dim3(256), 0, r.stream, r.dev, cur, nxt, nchild);
     cur = nxt;
   }
-  if (nt) hipLaunchKernelGGL(seed_finalize_kernel, dim3(grid_for(r, nfinal, 256)), dim3(256), 0, r.stream, r.dev, a.p, nfinal);
+  if constexpr (wide) hipLaunchKernelGGL(seed64_finalize_kernel, dim3(grid_for(r, nfinal, 256)), dim3(256), 0, r.stream, r.dev, a.p, nfinal);
+  else if (nt) hipLaunchKernelGGL(seed_finalize_kernel, dim3(grid_for(r, nfinal, 256)), dim3(256), 0, r.stream, r.dev, a.p, nfinal);
   else hipLaunchKernelGGL(aa_seed_finalize_kernel, dim3(grid_for(r, nfinal, 256)), dim3(256), 0, r.stream, r.dev, a.p, nfinal);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(r.stream));
@@ -102,7 +106,6 @@ const SeedEntry* seed_rung(Replica& r, int L) {
   return p;
 }
 
-// level-by-level seed table on the replica's device (see seed_extend_kernel)
 void drop_lcx(Replica& r) {
   r.lcx_key.reset(); r.lcx_rowpos.reset(); r.lcx_inner.reset();
   r.dev.lcx_key = r.dev.lcx_rowpos = r.dev.lcx_inner = nullptr;
@@ -123,20 +126,8 @@ void build_seed(awry_index* ix, Replica& r, int k) {
   if (r.wide) {  // 64-bit rows: 16-byte entries, nucleotide only
     require(ix->host.alphabet == NUCLEOTIDE, "a wide-row seed table needs a nucleotide index");
     require(k <= 17, "seed k-mer length must be <= 17");
-    const uint64_t nfinal = 1ull << (2 * k);
-    DevBuf<SeedEntry64> a(nfinal), b(std::max<uint64_t>(4, nfinal / 4));
-    SeedEntry64* cur = ((k - 1) % 2 == 0) ? a.p : b.p;
-    hipLaunchKernelGGL(seed64_level1_kernel, dim3(1), dim3(256), 0, r.stream, r.dev, cur);
-    uint64_t nchild = 4;
-    for (int j = 2; j <= k; j++) {
-      SeedEntry64* nxt = ((k - j) % 2 == 0) ? a.p : b.p;
-      nchild *= 4;
-      hipLaunchKernelGGL(seed64_extend_kernel, dim3(grid_for(r, nchild * 4, 256)), dim3(256), 0, r.stream, r.dev, cur, nxt, nchild);
-      cur = nxt;
-    }
-    hipLaunchKernelGGL(seed64_finalize_kernel, dim3(grid_for(r, nfinal, 256)), dim3(256), 0, r.stream, r.dev, a.p, nfinal);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(r.stream));
+    DevBuf<SeedEntry64> a;
+    build_seed_table(r, true, k, a);
     r.seed64 = std::move(a);
     r.seed_k = k;
     r.dev.seed64 = r.seed64.p;

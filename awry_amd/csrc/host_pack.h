@@ -1,7 +1,7 @@
 // host_pack.h -- host half of the drop-in batch boundary (awry_count_batch / awry_locate_batch): a persistent worker
 // pool and the AVX2 packer that turns ASCII nucleotide queries into the 2-bit words the packed kernels read, so that
 // 8 B per 31-mer cross PCIe instead of 31 B (hard part 2; caller side of
-// /root/reference src/fm_index.rs:455-487).  Same arithmetic as pack_nt2_tile_kernel (kernels.hip.h): case fold,
+// /root/reference src/fm_index.rs:455-487).  Same arithmetic as pack_nt2_tile_kernel (kernels_pack.hip.h): case fold,
 // membership test against A C G T, bits 1..2 of the ASCII code, swap of the last two codes, squeeze.
 // Nothing here searches: queries with any other byte are only LISTED, and the device redoes them with the generic kernel.
 #pragma once

@@ -1,5 +1,5 @@
 // lcx.hip.h -- the left-context index (LCX, layout.h): device helpers for searching it with a wavefront quad, and the
-// kernels that build it.  Included by kernels.hip.h (needs quad_sum, Text20).
+// kernels that build it.  A part of kernels.hip.h: included there behind kernels_quad.hip.h (needs quad_sum, Text20), and not on its own.
 //
 // Why: backward search (/root/reference src/fm_index.rs:402-438) consumes a query right to left, one LF step per letter,
 // and every step of a range wider than a block costs two random 128-B lines.  The seed table replaces the first k steps

@@ -1,5 +1,6 @@
 // lcx_kernels.hip.h -- phase 2 of the two-phase count schedules when the left-context index (layout.h, lcx.hip.h) is
-// resident.  Included at the end of kernels.hip.h.
+// resident.  A part of kernels.hip.h: included there behind the count parts (needs Nt2Survivors of kernels_nt2_kmer.hip.h,
+// lcx_quad_step of lcx.hip.h, block_excl_scan of kernels_scan.hip.h), and not on its own.
 //
 // count_nt2_resume_kernel / count_nt2_reads_kernel<.., LIST> search the index too, but they are built around LF steps: one
 // survivor per quad at a time, block b working through the list block b wrote.  A search is a chain of 3..6 dependent

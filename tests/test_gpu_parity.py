@@ -1661,6 +1661,66 @@ def test_wide_row_kernels(oracle):
         ix.set_verify(2)  # the verify accelerators are 32-bit structures
 
 
+@pytest.mark.gpu
+def test_seed_tables_of_every_depth_and_width(oracle):
+    """the seed tables are built level by level by one host function and one level-1 / extend kernel per entry width: a
+    table of k = 1 is level 1 alone, k = 2 one extend pass that ends in the other of the two build buffers, and so on in
+    turns.  Every depth 1..4 with 32-bit and with 64-bit rows (nucleotide), 1..3 for the amino table, queried with the
+    seed window alone (the entry is the answer) and with 1 and 5 letters in front of it, against the oracle"""
+    import torch
+    import awry_amd
+    L_ = awry_amd.load_library()
+    text, st, hd = synth.make_text(20_000, 0, 61, 2, 0.02)
+    assert len(st) == 2 and (text == ord("N")).sum() > 0
+    oi = oracle.OracleIndex.from_text(text, 0, 8, 0, st, hd)
+    narrow = gpu_index(text, 0, 8, 0, st, hd)
+    L_.awry_debug_force_wide_rows(1)
+    try:
+        wide = gpu_index(text, 0, 8, 0, st, hd)
+    finally:
+        L_.awry_debug_force_wide_rows(0)
+    assert "count_nt2_wide_kernel" in wide.count_schedule(31) and "count_nt2_wide_kernel" not in narrow.count_schedule(31)
+    ks = (1, 2, 3, 4)
+    batches = {}  # per query length, computed once: the queries and what the oracle says
+    for L in sorted({k + d for k in ks for d in (0, 1, 5)}):
+        q2d = np.concatenate([synth.sampled_queries(text, 600, L, 10 + L), synth.random_queries(400, L, 0, 30 + L)])
+        qb, qo = synth.fixed_to_csr(q2d)
+        batches[L] = (q2d, oi.parallel_count(qb, qo, 4)[0], oi.parallel_locate(qb, qo, 4)[:3])
+    for name, ix in (("narrow", narrow), ("wide", wide)):
+        for k in ks:
+            ix.set_seed_kmer_len(k)
+            assert ix.seed_kmer_len() == k
+            for L in (k, k + 1, k + 5):
+                q2d, want_c, want_l = batches[L]
+                assert np.array_equal(ix.count_kmers_nt2(q2d, True), want_c), (name, k, L)
+                got = ix.locate_reads_nt2(q2d)
+                assert all(np.array_equal(x, y) for x, y in zip(got, want_l)), (name, k, L)
+    # the amino table: batches large enough for the k-mer schedule
+    aa, ast, ahd = synth.make_text(20_000, 1, 62, 3, 0.01)
+    ax = gpu_index(aa, 1, 8, 0, ast, ahd)
+    ao = oracle.OracleIndex.from_text(aa, 1, 8, 0, ast, ahd)
+    aks = (1, 2, 3)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.current_stream().cuda_stream
+    abatches = {}
+    for L in sorted({k + d for k in aks for d in (0, 1, 5)}):
+        q2d = np.concatenate([synth.sampled_queries(aa, 2600, L, 50 + L, False, 1), synth.random_queries(1500, L, 1, 70 + L)])
+        qb, qo = synth.fixed_to_csr(q2d)
+        abatches[L] = (torch.from_numpy(np.concatenate([qb, np.zeros(16, dtype=np.uint8)])).to(dev), len(q2d), ao.parallel_count(qb, qo, 4)[0])
+    for k in aks:
+        ax.set_seed_kmer_len(k)
+        assert ax.seed_kmer_len() == k
+        for L in (k, k + 1, k + 5):
+            d_q, nq, want_c = abatches[L]
+            assert nq >= 4096
+            d_c = torch.full((nq,), -1, dtype=torch.int64, device=dev)
+            d_s = torch.full((nq,), 77, dtype=torch.uint8, device=dev)
+            ax.dev_count_ascii_uniform(d_q.data_ptr(), nq, L, d_c.data_ptr(), d_s.data_ptr(), stream, 0)
+            torch.cuda.synchronize()
+            assert np.array_equal(d_c.cpu().numpy().astype(np.uint64), want_c), (k, L)
+            assert int(d_s.max()) == 0, (k, L)
+
+
 def test_ecoli_scale_21mers_against_the_oracle(oracle):
     """BASELINE configs[0]'s shape on the HIP path: an E. coli K-12-sized text (4.6 Mbp, one record), 10 k random and 10 k
     present 21-mers, counts through the host boundary and the packed kernels, locations of the present ones -- all against
