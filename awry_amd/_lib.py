@@ -22,6 +22,10 @@ class Range(C.Structure):
     _fields_ = [("start_ptr", C.c_uint64), ("end_ptr", C.c_uint64)]
 
 
+class Anchor(C.Structure):  # awry_anchor_t
+    _fields_ = [("q_begin", C.c_uint32), ("q_len", C.c_uint32), ("start_row", C.c_uint64), ("count", C.c_uint64)]
+
+
 class BuildArgs(C.Structure):
     _fields_ = [("input_path", C.c_char_p), ("sa_tmp_path", C.c_char_p), ("sa_ratio", C.c_uint64),
                 ("kmer_len", C.c_uint8), ("alphabet", C.c_uint8), ("max_query_len", C.c_uint64),
@@ -91,6 +95,13 @@ def load_library():
         C.POINTER(u8p))
     sig("awry_dev_count_mismatch", i32, vp, i32, vp, vp, u64, i32, vp, vp, vp)
     sig("awry_dev_count_mismatch_tally", i32, vp, i32, vp, vp, u64, i32, vp, vp, vp, vp)
+    u32 = C.c_uint32
+    app = C.POINTER(C.POINTER(Anchor))
+    sig("awry_anchor_batch", i32, vp, vp, u64p, u64, u32, i32, C.POINTER(u64p), app)
+    sig("awry_locate_anchors_batch", i32, vp, vp, u64p, u64, u32, i32, u64, C.POINTER(u64p), app, C.POINTER(u64p),
+        C.POINTER(C.POINTER(Pos)), C.POINTER(u64p))
+    sig("awry_dev_anchors", i32, vp, i32, vp, vp, u64, u32, i32, vp, vp, vp, vp, vp)
+    sig("awry_dev_anchors_tally", i32, vp, i32, vp, vp, u64, u32, i32, vp, vp, vp, vp, vp, vp)
     sig("awry_debug_rank_all", i32, vp, i32, vp, u64, vp, vp)
     sig("awry_count", i32, vp, vp, u64, u64p)
     sig("awry_search_range", i32, vp, vp, u64, C.POINTER(Range))

@@ -7,6 +7,7 @@
 #include "host_count.h"
 #include "host_locate.h"
 #include "mismatch_host.h"
+#include "anchor_host.h"
 #include "prewarm.h"
 
 namespace {
@@ -382,6 +383,28 @@ int awry_locate_mismatch_batch(awry_index_t* idx, const uint8_t* qbytes, const u
     if (hits_out) *hits_out = hits.release();
     if (global_pos_out) *global_pos_out = gp.release();
     if (mismatches_out) *mismatches_out = mm.release();
+  });
+}
+
+int awry_anchor_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, int skip,
+                      uint64_t** anchor_off_out, awry_anchor_t** anchors_out) {
+  return guarded([&] {
+    require(idx && qoff && anchor_off_out && anchors_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_anchor_args(min_len, skip);
+    anchor_batch(idx, qbytes, qoff, n, min_len, skip, 0, anchor_off_out, anchors_out, nullptr, nullptr, nullptr);
+  });
+}
+
+int awry_locate_anchors_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, int skip,
+                              uint64_t max_hits, uint64_t** anchor_off_out, awry_anchor_t** anchors_out, uint64_t** hit_off_out,
+                              awry_pos_t** hits_out, uint64_t** global_pos_out) {
+  return guarded([&] {
+    require(idx && qoff && anchor_off_out && anchors_out && hit_off_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_anchor_args(min_len, skip);
+    require(max_hits != 0, "max_hits must be at least 1 (a one-letter anchor has a quarter of the text as hits)");
+    anchor_batch(idx, qbytes, qoff, n, min_len, skip, max_hits, anchor_off_out, anchors_out, hit_off_out, hits_out, global_pos_out);
   });
 }
 
@@ -778,6 +801,22 @@ int awry_dev_count_mismatch_tally(awry_index_t* idx, int slot, const void* d_qby
     require(n == 0 || (d_qbytes && d_qoff && d_counts), "null argument");
     launch_count_mismatch(r, (const uint8_t*)d_qbytes, (const uint64_t*)d_qoff, n, max_mismatches, (uint64_t*)d_counts, nullptr, nullptr,
                           (uint8_t*)d_status, (hipStream_t)stream, (unsigned long long*)d_tally);
+  });
+}
+
+int awry_dev_anchors(awry_index_t* idx, int slot, const void* d_qbytes, const void* d_qoff, uint64_t n, uint32_t min_len, int skip,
+                     void* d_n_anchors, const void* d_anchor_off, void* d_anchors, void* d_status, void* stream) {
+  return awry_dev_anchors_tally(idx, slot, d_qbytes, d_qoff, n, min_len, skip, d_n_anchors, d_anchor_off, d_anchors, d_status, nullptr, stream);
+}
+
+int awry_dev_anchors_tally(awry_index_t* idx, int slot, const void* d_qbytes, const void* d_qoff, uint64_t n, uint32_t min_len, int skip,
+                           void* d_n_anchors, const void* d_anchor_off, void* d_anchors, void* d_status, void* d_tally, void* stream) {
+  return guarded([&] {
+    require_anchor_args(min_len, skip);
+    Replica& r = replica(idx, slot);
+    require(n == 0 || (d_qbytes && d_qoff && (d_anchor_off ? d_anchors != nullptr : d_n_anchors != nullptr)), "null device pointer");
+    launch_anchors(r, (const uint8_t*)d_qbytes, (const uint64_t*)d_qoff, n, min_len, skip, (uint64_t*)d_n_anchors, (const uint64_t*)d_anchor_off,
+                   (Anchor*)d_anchors, (uint8_t*)d_status, (hipStream_t)stream, (unsigned long long*)d_tally);
   });
 }
 

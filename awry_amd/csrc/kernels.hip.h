@@ -27,6 +27,8 @@
 //   count, packed reads   COUNT_NT2_READS_PROBE_KERNEL<R>    phase 1 for reads of any (per-read) length [kernels_reads]
 //                         + COUNT_NT2_READS_KERNEL<..LIST>   quads on the listed reads; without LIST: the single-kernel schedule [kernels_reads]
 //                         + LCX_QUAD_READS_KERNEL<R>         the listed reads as one pool, when the left-context index is resident [lcx_kernels]
+//   anchors, any query    ANCHOR_SCALAR_KERNEL<A, FILL>      greedy longest-match factorisation, one query per lane: count pass, scan, fill pass [kernels_anchor]
+//                         + ANCHOR_RANGES_KERNEL             anchor records -> row pairs and located counts for the locate kernels [kernels_anchor]
 //   count, wide rows      count_nt2_wide_kernel, count_nt2_wide_probe_kernel   64-bit rows [kernels_wide]
 //   locate                LOCATE_TILE_KERNEL<A>              hit -> row, sampled / verified hits finished [this file]
 //                         + LOCATE_WALK_NT_LANE_KERNEL       LF walks of the rest, one hit per lane, whole block per step [this file]
@@ -49,6 +51,7 @@
 #include "kernels_rank.hip.h"
 #include "kernels_scan.hip.h"
 #include "kernels_count.hip.h"     // block_excl_scan
+#include "kernels_anchor.hip.h"    // step_scalar, ByteStream, seed_probe, tally_add
 #include "kernels_aa_kmer.hip.h"   // QueryList, tally_add
 #include "kernels_quad.hip.h"      // slice_mask
 #include "lcx.hip.h"               // quad_sum, Text20

@@ -411,4 +411,27 @@ void launch_count_mismatch(Replica& r, const uint8_t* d_q, const uint64_t* d_off
   HIP_CHECK(hipGetLastError());
 }
 
+// anchors (kernels_anchor.hip.h) on a resident grid.  d_anchor_off == nullptr: the count pass (d_n_anchors, d_status); else the
+// fill pass, which writes the records of query q at d_anchors[d_anchor_off[q] ...) (d_n_anchors / d_status nullable there)
+void launch_anchors(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, uint32_t min_len, int skip, uint64_t* d_n_anchors,
+                    const uint64_t* d_anchor_off, Anchor* d_anchors, uint8_t* d_status, hipStream_t s, unsigned long long* d_tally = nullptr) {
+  if (n == 0) return;
+  const uint64_t want = (n + 255) / 256;
+  with_alphabet(r.dev.alphabet, [&](auto A) {
+    with_flags(d_anchor_off != nullptr, [&](auto F) {
+      auto kernel = anchor_scalar_kernel<decltype(A)::value, F() ? 1 : 0>;
+      const dim3 g((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, resident_grid(r, kernel)))), b(256);
+      hipLaunchKernelGGL(kernel, g, b, 0, s, r.dev, d_q, d_off, n, min_len, (uint32_t)skip, d_n_anchors, d_anchor_off, d_anchors, d_status, d_tally);
+    });
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
+// anchor records -> (start_row, end_row) pairs and located counts (0 for anchors of more than max_hits rows)
+void launch_anchor_ranges(Replica& r, const Anchor* d_anchors, uint64_t n, uint64_t max_hits, uint64_t* d_ranges, uint64_t* d_located, hipStream_t s) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(anchor_ranges_kernel, dim3(grid_for(r, n, 256)), dim3(256), 0, s, d_anchors, n, max_hits, d_ranges, d_located);
+  HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace

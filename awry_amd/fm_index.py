@@ -91,6 +91,9 @@ def pack_queries(queries: Iterable):
 
 _u64p = C.POINTER(C.c_uint64)
 
+# awry_anchor_t as a numpy record (24 bytes, the C layout)
+ANCHOR_DTYPE = np.dtype([("q_begin", np.uint32), ("q_len", np.uint32), ("start_row", np.uint64), ("count", np.uint64)])
+
 
 class _Owned:
     """a malloc'ed result buffer of the C ABI, exposed to numpy without a copy and released (awry_free_buffer) with
@@ -402,6 +405,57 @@ class FmIndex:
     def dev_count_mismatch_tally(self, d_qbytes, d_qoff, n, k, d_counts, d_tally, d_status=None, stream=None, slot=0):
         """dev_count_mismatch + census: d_tally[2] += (expansions, queries searched)"""
         _check(self._L.awry_dev_count_mismatch_tally(self._h, slot, d_qbytes, d_qoff, n, int(k), d_counts, d_status, d_tally, stream))
+
+    # ------------------------------------------------------------------ anchors (greedy longest-match factorisation)
+    def parallel_anchors_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 1, skip: int = 0):
+        """-> (anchor_off uint64[n+1], anchors ANCHOR_DTYPE[total]): the maximal exact matches of every query, found right to
+        left (include/awry_hip.h states the definition); anchors of query i are anchors[anchor_off[i]:anchor_off[i+1]]"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        off, an = _u64p(), C.POINTER(_lib.Anchor)()
+        _check(self._L.awry_anchor_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(skip), C.byref(off), C.byref(an)))
+        offs = _adopt(self._L, off, n + 1, np.uint64)
+        return offs, _adopt(self._L, an, 24 * int(offs[-1]), np.uint8).view(ANCHOR_DTYPE)
+
+    def parallel_anchors(self, queries: Iterable, min_len: int = 1, skip: int = 0):
+        """-> per query, its anchors as (q_begin, q_len, start_row, count) tuples in the order found (descending q_begin)"""
+        off, an = self.parallel_anchors_csr(*pack_queries(queries), min_len, skip)
+        return [[tuple(int(v) for v in a) for a in an[off[i]:off[i + 1]]] for i in range(len(off) - 1)]
+
+    def anchors_string(self, query, min_len: int = 1, skip: int = 0):
+        """anchors of one query"""
+        return self.parallel_anchors([query], min_len, skip)[0]
+
+    def parallel_locate_anchors_csr(self, qbytes: np.ndarray, qoff: np.ndarray, max_hits: int, min_len: int = 1, skip: int = 0,
+                                    want_pos: bool = True):
+        """-> (anchor_off, anchors, hit_off uint64[total+1], global_pos uint64[hits], pos uint64[hits, 2]): hits of anchor s are
+        [hit_off[s], hit_off[s+1]) in ascending BWT-row order; an anchor of more than max_hits rows gets none"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        off, an, hoff, hits, gp = _u64p(), C.POINTER(_lib.Anchor)(), _u64p(), C.POINTER(_lib.Pos)(), _u64p()
+        _check(self._L.awry_locate_anchors_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(skip), int(max_hits),
+                                                 C.byref(off), C.byref(an), C.byref(hoff), C.byref(hits) if want_pos else None, C.byref(gp)))
+        offs = _adopt(self._L, off, n + 1, np.uint64)
+        tot = int(offs[-1])
+        anchors = _adopt(self._L, an, 24 * tot, np.uint8).view(ANCHOR_DTYPE)
+        hit_off = _adopt(self._L, hoff, tot + 1, np.uint64)
+        nh = int(hit_off[-1])
+        g = _adopt(self._L, gp, nh, np.uint64)
+        p = _adopt(self._L, hits, 2 * nh, np.uint64).reshape(-1, 2) if want_pos else np.zeros((0, 2), np.uint64)
+        return offs, anchors, hit_off, g, p
+
+    def dev_anchors(self, d_qbytes, d_qoff, n, min_len, skip, d_n_anchors, d_anchor_off=None, d_anchors=None, d_status=None, stream=None, slot=0):
+        """device-resident anchors: d_anchor_off None = the count pass (d_n_anchors[n] u64, optional d_status[n]); else the fill
+        pass writing 24-byte records at d_anchors[d_anchor_off[q] ...); scan d_n_anchors with dev_scan_counts in between"""
+        _check(self._L.awry_dev_anchors(self._h, slot, d_qbytes, d_qoff, n, int(min_len), int(skip), d_n_anchors, d_anchor_off, d_anchors, d_status, stream))
+
+    def dev_anchors_tally(self, d_qbytes, d_qoff, n, min_len, skip, d_n_anchors, d_tally, d_anchor_off=None, d_anchors=None, d_status=None,
+                          stream=None, slot=0):
+        """dev_anchors + census: d_tally[3] += (LF steps executed, probes that supplied a range, anchors reported)"""
+        _check(self._L.awry_dev_anchors_tally(self._h, slot, d_qbytes, d_qoff, n, int(min_len), int(skip), d_n_anchors, d_anchor_off, d_anchors,
+                                              d_status, d_tally, stream))
 
     def debug_rank_all(self, rows: np.ndarray, slot=0) -> np.ndarray:
         """Occ of every non-sentinel symbol at each row through the kernels' all-symbol rank -> uint64[len(rows), S]

@@ -170,6 +170,49 @@ class FmIndex {
     awry_free_buffer(hoff); awry_free_buffer(hits); awry_free_buffer(mm);
     return out;
   }
+  // anchors (no counterpart in the reference; the definition is in awry_hip.h): the greedy longest-match factorisation of
+  // every query, found right to left -- q[q_begin .. q_begin + q_len) occupies the BWT rows `rows`
+  struct Anchor {
+    uint32_t q_begin, q_len;
+    SearchRange rows;
+  };
+  template <class StrRange>
+  std::vector<std::vector<Anchor>> parallel_anchors(const StrRange& queries, uint32_t min_len = 1, bool skip_failed_letter = false) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* aoff = nullptr; awry_anchor_t* an = nullptr;
+    check(awry_anchor_batch(h_, bytes.data(), off.data(), n, min_len, skip_failed_letter ? 1 : 0, &aoff, &an));
+    std::vector<std::vector<Anchor>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = aoff[i]; j < aoff[i + 1]; j++) out[i].push_back({an[j].q_begin, an[j].q_len, {an[j].start_row, an[j].start_row + an[j].count - 1}});
+    awry_free_buffer(aoff); awry_free_buffer(an);
+    return out;
+  }
+  // the same with every anchor of at most max_hits (>= 1) occurrences located, in ascending BWT-row order; larger ones keep
+  // their record and an empty list
+  struct LocatedAnchor {
+    Anchor anchor;
+    std::vector<LocalizedSequencePosition> hits;
+  };
+  template <class StrRange>
+  std::vector<std::vector<LocatedAnchor>> parallel_locate_anchors(const StrRange& queries, uint64_t max_hits, uint32_t min_len = 1,
+                                                                  bool skip_failed_letter = false) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* aoff = nullptr; awry_anchor_t* an = nullptr; uint64_t* hoff = nullptr; awry_pos_t* hits = nullptr;
+    check(awry_locate_anchors_batch(h_, bytes.data(), off.data(), n, min_len, skip_failed_letter ? 1 : 0, max_hits, &aoff, &an, &hoff, &hits, nullptr));
+    std::vector<std::vector<LocatedAnchor>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = aoff[i]; j < aoff[i + 1]; j++) {
+        LocatedAnchor la{{an[j].q_begin, an[j].q_len, {an[j].start_row, an[j].start_row + an[j].count - 1}}, {}};
+        for (uint64_t h = hoff[j]; h < hoff[j + 1]; h++) la.hits.push_back({hits[h].seq_idx, hits[h].local_pos});
+        out[i].push_back(std::move(la));
+      }
+    awry_free_buffer(aoff); awry_free_buffer(an); awry_free_buffer(hoff); awry_free_buffer(hits);
+    return out;
+  }
   // src/fm_index.rs:559-582, 585-593
   SearchRange update_range_with_symbol(SearchRange r, char symbol) {
     awry_range_t o;

@@ -172,6 +172,40 @@ int awry_locate_mismatch_batch(awry_index_t *idx, const uint8_t *qbytes, const u
                                int max_mismatches, uint64_t **hit_off_out, awry_pos_t **hits_out,
                                uint64_t **global_pos_out, uint8_t **mismatches_out);
 
+/* ---- anchors: greedy longest-match factorisation of a query (no counterpart in the reference) ---------------
+ * What a mapper does with a read that does not occur as a whole: cut it into maximal exact matches and chain those.
+ * Queries are mapped to symbol indices exactly as on the exact path (letters case-insensitive, U = T, any other byte N /
+ * X; query N matches text N) and rejected as there (empty, '$' / '#', byte >= 0x80).  For a query q of L letters, with
+ * occurs(b, e) = "q[b..e) has at least one occurrence (awry_count > 0)", min_len >= 1 and skip in {0, 1}:
+ *     e = L
+ *     while e > 0:
+ *         if not occurs(e-1, e):        # the letter itself is absent from the text
+ *             e -= 1; continue
+ *         b = smallest b' such that occurs(b', e)     # backward search until the range would become empty
+ *         if e - b >= min_len: report anchor (q_begin = b, q_len = e - b, start_row, count) = row range of q[b..e)
+ *         if b == 0: stop
+ *         e = b - skip                  # skip = 0: the letter that failed ends the next anchor; 1: it is left out
+ * Anchors of one query are reported in the order found: right to left, descending q_begin.  Anchors shorter than min_len
+ * are not reported but still consume their letters.  A query that occurs as a whole yields exactly one anchor, q_begin =
+ * 0, q_len = L, whose rows are what awry_search_range returns for it.  start_row / count are rows of the BWT (awry_range_t:
+ * start_ptr = start_row, end_ptr = start_row + count - 1); no accelerator changes them (the seed table only lets an anchor
+ * start seed_k letters in).  min_len == 0 or skip outside 0..1 => AWRY_ERR_ARG; a rejected query fails the whole batch
+ * with AWRY_ERR_INVALID_QUERY and leaves the out-pointers untouched; no replica => AWRY_ERR_NO_DEVICE; a query of 2^32
+ * letters or more => AWRY_ERR_ARG. */
+typedef struct { uint32_t q_begin, q_len; uint64_t start_row, count; } awry_anchor_t;
+/* CSR output, library-allocated (awry_free_buffer): anchors of query i are anchors[anchor_off[i] .. anchor_off[i+1]) */
+int awry_anchor_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len, int skip,
+                      uint64_t **anchor_off_out, awry_anchor_t **anchors_out);
+/* the same, and every anchor located: hits of anchor s (index into anchors) are [hit_off[s], hit_off[s+1]) in ascending
+ * BWT-row order -- exactly what awry_locate_batch returns for that substring; hit_off has anchor_off[n] + 1 entries.  An
+ * anchor with count > max_hits keeps its record and gets no hits; max_hits == 0 => AWRY_ERR_ARG (a cap is mandatory: a
+ * one-letter anchor has a quarter of the text as hits).  hits_out / global_pos_out are nullable as in awry_locate_batch.  A
+ * chunk of queries whose located hits exceed the device hit capacity (2^26; env AWRY_ANCHOR_HIT_CAP, read per call) and
+ * which holds more than one query is split and redone. */
+int awry_locate_anchors_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len,
+                              int skip, uint64_t max_hits, uint64_t **anchor_off_out, awry_anchor_t **anchors_out,
+                              uint64_t **hit_off_out, awry_pos_t **hits_out, uint64_t **global_pos_out);
+
 /* releases an array one of the calls above (or awry_locate / awry_read_query_file) returned.  Result arrays are pinned
  * host memory recycled through a process-wide pool (the device writes results straight into them); never pass them to
  * free().  AWRY_PINNED_CACHE_GB (default 4) bounds what the pool keeps between calls. */
@@ -290,6 +324,19 @@ int awry_dev_count_mismatch(awry_index_t *idx, int slot, const void *d_qbytes, c
  * node, two block lines --, queries searched}; per-lane atomics at the end of the launch only */
 int awry_dev_count_mismatch_tally(awry_index_t *idx, int slot, const void *d_qbytes, const void *d_qoff, uint64_t n,
                                   int max_mismatches, void *d_counts, void *d_status, void *d_tally, void *stream);
+/* anchors (see awry_anchor_batch), device-resident form: no synchronisation, no allocation, any stream.  Two calls with the
+ * caller's scan between them: d_anchor_off == NULL is the count pass -- ASCII queries + u64 offsets[n+1] -> d_n_anchors[n]
+ * (u64) and optional d_status[n] bytes (non-zero: rejected query, 0 anchors); awry_dev_scan_counts turns d_n_anchors into
+ * d_anchor_off[n+1]; the fill pass (d_anchor_off given) repeats the walk and writes the awry_anchor_t records of query q at
+ * d_anchors[d_anchor_off[q] ...) (d_n_anchors / d_status nullable there; a slot at or beyond d_anchor_off[q+1] is never
+ * written).  Every query must be shorter than 2^32 letters. */
+int awry_dev_anchors(awry_index_t *idx, int slot, const void *d_qbytes, const void *d_qoff, uint64_t n, uint32_t min_len, int skip,
+                     void *d_n_anchors, const void *d_anchor_off, void *d_anchors, void *d_status, void *stream);
+/* the same with a work census: d_tally[3] (u64, caller-zeroed) += {LF steps executed (the ones that emptied the range
+ * included), seed-table probes that supplied a range, anchors reported}; one atomic per query and counter */
+int awry_dev_anchors_tally(awry_index_t *idx, int slot, const void *d_qbytes, const void *d_qoff, uint64_t n, uint32_t min_len,
+                           int skip, void *d_n_anchors, const void *d_anchor_off, void *d_anchors, void *d_status,
+                           void *d_tally, void *stream);
 /* test hook of the all-symbol rank primitive: d_occ[i * S + s - 1] = Occ(s, d_rows[i]) for every non-sentinel symbol index s
  * (S = 5 nucleotide, 21 amino; inclusive of the row, as awry_update_range uses it); rows >= bwt_len give zeros */
 int awry_debug_rank_all(awry_index_t *idx, int slot, const void *d_rows, uint64_t n, void *d_occ, void *stream);

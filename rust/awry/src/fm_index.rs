@@ -15,7 +15,7 @@ use std::os::raw::c_char;
 use std::path::{Path, PathBuf};
 use std::sync::Arc;
 
-use awry_hip_sys as sys;
+use awry_hip_sys::{self as sys, awry_anchor_t as RawAnchor};
 use rayon::iter::{IndexedParallelIterator, IntoParallelIterator, IntoParallelRefIterator, ParallelIterator};
 
 use crate::{
@@ -451,6 +451,44 @@ impl FmIndex {
             sys::awry_free_buffer(hit_off as *mut std::os::raw::c_void);
             sys::awry_free_buffer(hits as *mut std::os::raw::c_void);
             sys::awry_free_buffer(mm as *mut std::os::raw::c_void);
+        }
+        Ok(out)
+    }
+
+    /// Anchors (no counterpart in the reference; the definition is in include/awry_hip.h): per query, its greedy longest-match
+    /// factorisation found right to left, as `(q_begin, q_len, SearchRange)` -- the maximal exact matches a mapper chains when a
+    /// read does not occur as a whole.  Anchors shorter than `min_len` (>= 1) are left out; `skip_failed_letter` leaves the
+    /// letter that ended an anchor out of the next one.
+    pub fn parallel_anchors<'a>(
+        &self,
+        queries: impl ParallelIterator<Item = &'a str>,
+        min_len: u32,
+        skip_failed_letter: bool,
+    ) -> Result<Vec<Vec<(usize, usize, SearchRange)>>, AwryError> {
+        let csr = to_csr(queries);
+        let n = csr.offsets.len() - 1;
+        let mut anchor_off: *mut u64 = std::ptr::null_mut();
+        let mut anchors: *mut RawAnchor = std::ptr::null_mut();
+        check(unsafe {
+            sys::awry_anchor_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, min_len, skip_failed_letter as i32, &mut anchor_off,
+                                   &mut anchors)
+        })?;
+        let out = unsafe {
+            let off = std::slice::from_raw_parts(anchor_off, n + 1);
+            let total = off[n] as usize;
+            let flat: &[RawAnchor] = if total == 0 { &[] } else { std::slice::from_raw_parts(anchors, total) };
+            (0..n)
+                .map(|i| {
+                    flat[off[i] as usize..off[i + 1] as usize]
+                        .iter()
+                        .map(|a| (a.q_begin as usize, a.q_len as usize, SearchRange { start_ptr: a.start_row, end_ptr: a.start_row + a.count - 1 }))
+                        .collect::<Vec<_>>()
+                })
+                .collect::<Vec<_>>()
+        };
+        unsafe {
+            sys::awry_free_buffer(anchor_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(anchors as *mut std::os::raw::c_void);
         }
         Ok(out)
     }
