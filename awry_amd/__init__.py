@@ -13,5 +13,6 @@ from .fm_index import (  # noqa: F401
     LocalizedSequencePosition,
     SearchRange,
     SymbolAlphabet,
+    pattern_class,
 )
 from ._lib import lib_path, load_library  # noqa: F401

@@ -96,6 +96,12 @@ def load_library():
     sig("awry_dev_count_mismatch", i32, vp, i32, vp, vp, u64, i32, vp, vp, vp)
     sig("awry_dev_count_mismatch_tally", i32, vp, i32, vp, vp, u64, i32, vp, vp, vp, vp)
     u32 = C.c_uint32
+    sig("awry_pattern_class", u32, i32, u8)
+    sig("awry_count_pattern_batch", i32, vp, vp, u64p, u64, i32, u64p)
+    sig("awry_locate_pattern_batch", i32, vp, vp, u64p, u64, i32, C.POINTER(u64p), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p),
+        C.POINTER(u8p))
+    sig("awry_dev_count_pattern", i32, vp, i32, vp, vp, u64, i32, vp, vp, vp)
+    sig("awry_dev_count_pattern_tally", i32, vp, i32, vp, vp, u64, i32, vp, vp, vp, vp)
     app = C.POINTER(C.POINTER(Anchor))
     sig("awry_anchor_batch", i32, vp, vp, u64p, u64, u32, i32, C.POINTER(u64p), app)
     sig("awry_locate_anchors_batch", i32, vp, vp, u64p, u64, u32, i32, u64, C.POINTER(u64p), app, C.POINTER(u64p),

@@ -57,6 +57,34 @@ AWRY_HD int index_of_ascii(int alphabet, uint8_t a) {
     default: return 20;
   }
 }
+// ASCII byte -> class mask of a pattern letter (awry_count_pattern_batch): bit s = symbol index s belongs to the class, 0 =
+// the byte is no class letter.  Nucleotide: A C G T (U == T), the IUPAC classes R Y S W K M B D H V, N = {A, C, G, T}.
+// Amino: the 20 standard residues, B = {D, N}, Z = {E, Q}, J = {I, L}, X = the 20.  Case-insensitive.  No class holds the
+// sentinel or the text's ambiguity symbol (nucleotide index 4, amino index 20).  The one table of host and device.
+AWRY_HD uint32_t pattern_class(int alphabet, uint8_t a) {
+  if (a >= 'a' && a <= 'z') a = (uint8_t)(a - 32);
+  if (a < 'A' || a > 'Z') return 0;
+  if (alphabet == NUCLEOTIDE) {
+    constexpr uint32_t A = 1u << 1, C = 1u << 2, G = 1u << 3, T = 1u << 5;
+    switch (a) {
+      case 'A': return A;          case 'C': return C;          case 'G': return G;          case 'T': case 'U': return T;
+      case 'R': return A | G;      case 'Y': return C | T;      case 'S': return C | G;      case 'W': return A | T;
+      case 'K': return G | T;      case 'M': return A | C;      case 'B': return C | G | T;  case 'D': return A | G | T;
+      case 'H': return A | C | T;  case 'V': return A | C | G;  case 'N': return A | C | G | T;
+      default: return 0;
+    }
+  }
+  constexpr uint32_t STD = 0x3FFFFEu & ~(1u << 20);  // indices 1 .. 21 without X (20)
+  switch (a) {
+    case 'B': return (1u << 3) | (1u << 12);   // D, N
+    case 'Z': return (1u << 4) | (1u << 14);   // E, Q
+    case 'J': return (1u << 8) | (1u << 10);   // I, L
+    case 'X': return STD;
+    case 'O': case 'U': return 0;
+    default: return 1u << index_of_ascii(AMINO, a);  // the 20 letters that are left are the standard residues
+  }
+}
+
 AWRY_HD uint8_t ascii_of_index(int alphabet, int idx) {
   if (alphabet == NUCLEOTIDE) {
     constexpr char T[7] = "$ACGNT";

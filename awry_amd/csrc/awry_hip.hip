@@ -7,6 +7,7 @@
 #include "host_count.h"
 #include "host_locate.h"
 #include "mismatch_host.h"
+#include "pattern_host.h"
 #include "anchor_host.h"
 #include "prewarm.h"
 
@@ -338,51 +339,29 @@ void awry_free_buffer(void* p) { release_result(p); }
 
 int awry_count_mismatch_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_mismatches,
                               uint64_t* counts_out) {
-  return guarded([&] {
-    require(idx && qoff && (counts_out || n == 0), "null argument");
-    require(qbytes || qoff[n] == qoff[0], "null query bytes");
-    require_mismatches(max_mismatches);
-    for_each_replica(idx, n, [&](Replica& r, Shard sh, int) { count_mismatch_shard(r, qbytes, qoff, sh, max_mismatches, counts_out); });
-  });
+  return guarded([&] { count_leaves_batch(idx, qbytes, qoff, n, max_mismatches, counts_out, launch_count_mismatch); });
 }
 
 int awry_locate_mismatch_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_mismatches,
                                uint64_t** hit_off_out, awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** mismatches_out) {
   return guarded([&] {
-    require(idx && qoff && hit_off_out, "null argument");
-    require(qbytes || qoff[n] == qoff[0], "null query bytes");
-    require_mismatches(max_mismatches);
-    std::vector<MismatchHits> res(std::max<size_t>(1, idx->reps.size()));
-    for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
-      HIP_CHECK(hipSetDevice(r.device));
-      for (Shard c : chunk_queries(qoff, sh.lo, sh.hi))
-        locate_mismatch_range(r, qbytes, qoff, c, max_mismatches, hits_out != nullptr, global_pos_out != nullptr, mismatches_out != nullptr, res[g]);
-    });
-    // shards are contiguous in query order: the result arrays are their concatenation
-    MBuf<uint64_t> off, gp;
-    MBuf<awry_pos_t> hits;
-    MBuf<uint8_t> mm;
-    off.grow(n + 1);
-    off.p[0] = 0;
-    uint64_t q = 0, total = 0;
-    for (auto& x : res)
-      for (uint64_t c : x.counts) { total += c; off.p[++q] = total; }
-    require(q == n, "internal: shard results do not cover the batch");
-    if (hits_out) hits.grow(std::max<uint64_t>(1, total));
-    if (global_pos_out) gp.grow(std::max<uint64_t>(1, total));
-    if (mismatches_out) mm.grow(std::max<uint64_t>(1, total));
-    uint64_t at = 0;
-    for (auto& x : res) {
-      const uint64_t t = x.counts.empty() ? 0 : std::max({x.gpos.size(), x.pos.size(), x.mm.size()});
-      if (hits_out && t) pool_memcpy(hits.p + at, x.pos.data(), t * sizeof(awry_pos_t));
-      if (global_pos_out && t) pool_memcpy(gp.p + at, x.gpos.data(), t * 8);
-      if (mismatches_out && t) pool_memcpy(mm.p + at, x.mm.data(), t);
-      at += t;
-    }
-    *hit_off_out = off.release();
-    if (hits_out) *hits_out = hits.release();
-    if (global_pos_out) *global_pos_out = gp.release();
-    if (mismatches_out) *mismatches_out = mm.release();
+    locate_leaves_batch(idx, qbytes, qoff, n, max_mismatches, hit_off_out, hits_out, global_pos_out, mismatches_out, launch_count_mismatch);
+  });
+}
+
+uint32_t awry_pattern_class(int alphabet, uint8_t ascii) {
+  return alphabet == AWRY_NUCLEOTIDE || alphabet == AWRY_AMINO ? pattern_class(alphabet, ascii) : 0;
+}
+
+int awry_count_pattern_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_mismatches,
+                             uint64_t* counts_out) {
+  return guarded([&] { count_pattern_batch(idx, qbytes, qoff, n, max_mismatches, counts_out); });
+}
+
+int awry_locate_pattern_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_mismatches,
+                              uint64_t** hit_off_out, awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** mismatches_out) {
+  return guarded([&] {
+    locate_pattern_batch(idx, qbytes, qoff, n, max_mismatches, hit_off_out, hits_out, global_pos_out, mismatches_out);
   });
 }
 
@@ -801,6 +780,22 @@ int awry_dev_count_mismatch_tally(awry_index_t* idx, int slot, const void* d_qby
     require(n == 0 || (d_qbytes && d_qoff && d_counts), "null argument");
     launch_count_mismatch(r, (const uint8_t*)d_qbytes, (const uint64_t*)d_qoff, n, max_mismatches, (uint64_t*)d_counts, nullptr, nullptr,
                           (uint8_t*)d_status, (hipStream_t)stream, (unsigned long long*)d_tally);
+  });
+}
+
+int awry_dev_count_pattern(awry_index_t* idx, int slot, const void* d_qbytes, const void* d_qoff, uint64_t n, int max_mismatches,
+                           void* d_counts, void* d_status, void* stream) {
+  return awry_dev_count_pattern_tally(idx, slot, d_qbytes, d_qoff, n, max_mismatches, d_counts, d_status, nullptr, stream);
+}
+
+int awry_dev_count_pattern_tally(awry_index_t* idx, int slot, const void* d_qbytes, const void* d_qoff, uint64_t n, int max_mismatches,
+                                 void* d_counts, void* d_status, void* d_tally, void* stream) {
+  return guarded([&] {
+    require_mismatches(max_mismatches);
+    Replica& r = replica(idx, slot);
+    require(n == 0 || (d_qbytes && d_qoff && d_counts), "null argument");
+    launch_count_pattern(r, (const uint8_t*)d_qbytes, (const uint64_t*)d_qoff, n, max_mismatches, (uint64_t*)d_counts, nullptr, nullptr,
+                         (uint8_t*)d_status, (hipStream_t)stream, (unsigned long long*)d_tally);
   });
 }
 

@@ -34,6 +34,7 @@
 #include "host_pack.h"
 #include "kernels.hip.h"
 #include "mismatch_kernels.hip.h"
+#include "pattern_kernels.hip.h"
 #include "sais.hpp"
 
 using namespace awry;

@@ -58,6 +58,10 @@ void run_count_chunk(Replica& r, ChunkBuffers& cb, const uint8_t* qbytes, const 
 
 [[noreturn]] void raise_bad_query(uint64_t query, uint8_t status) {
   static const char* why[] = {"", "empty query", "query contains '$' or '#'", "query contains a non-ASCII byte"};
+  static const char* why_pattern[] = {"pattern contains a byte that is no class letter of the index's alphabet",
+                                      "pattern has more than 16 class positions (AWRY_MAX_CLASS_POSITIONS)",
+                                      "pattern search abandoned at the expansion cap (AWRY_PATTERN_MAX_EXPANSIONS)"};
+  if (status >= Q_NOT_CLASS_LETTER && status <= Q_EXPANSION_CAP) throw QueryError("query " + std::to_string(query) + ": " + why_pattern[status - Q_NOT_CLASS_LETTER]);
   throw QueryError("query " + std::to_string(query) + ": " + why[status & 3] + " (undefined in the reference: src/fm_index.rs:406, src/bwt.rs:126-128)");
 }
 // raises INVALID_QUERY naming the first query of status[0, n) that the reference leaves undefined

@@ -99,7 +99,10 @@ __device__ __forceinline__ uint64_t sa_sample(const DevIndex& ix, uint64_t sampl
 }
 
 // status of a query (counts' companion array): != Q_OK marks inputs the reference leaves undefined
-enum : uint8_t { Q_OK = 0, Q_EMPTY = 1, Q_SENTINEL = 2, Q_NON_ASCII = 3 };
+enum : uint8_t { Q_OK = 0, Q_EMPTY = 1, Q_SENTINEL = 2, Q_NON_ASCII = 3,
+                 // class patterns only (pattern_kernels.hip.h): a byte that is no class letter, more class positions than
+                 // AWRY_MAX_CLASS_POSITIONS, a search abandoned at the expansion cap
+                 Q_NOT_CLASS_LETTER = 4, Q_CLASS_POSITIONS = 5, Q_EXPANSION_CAP = 6 };
 
 // Byte access through aligned 8-byte loads: one memory instruction per 8 consecutive bytes instead of one per byte
 // (the lanes of a wave read different queries, so every byte load is a line lookup of its own in the texture path;

@@ -411,6 +411,41 @@ void launch_count_mismatch(Replica& r, const uint8_t* d_q, const uint64_t* d_off
   HIP_CHECK(hipGetLastError());
 }
 
+// Expansions (rank_all pairs) one pattern may take before its search is abandoned with Q_EXPANSION_CAP.  A safety bound for
+// a shared card (DESIGN.md 5d has its basis).  Read per call: AWRY_PATTERN_MAX_EXPANSIONS (tests shrink it).
+uint64_t pattern_max_expansions() {
+  const char* e = getenv("AWRY_PATTERN_MAX_EXPANSIONS");
+  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
+  return v ? v : (uint64_t)AWRY_PATTERN_DEFAULT_MAX_EXPANSIONS;
+}
+
+// the class-pattern DFS kernel (pattern_kernels.hip.h) on a resident grid; arguments as launch_count_mismatch.  The frames a
+// lane cannot keep in registers live in the stream's scratch, sized to the grid.
+void launch_count_pattern(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, int k, uint64_t* d_counts, uint64_t* d_totals,
+                          uint64_t* d_nleaves, uint8_t* d_status, hipStream_t s, unsigned long long* d_tally = nullptr,
+                          const uint64_t* d_leaf_off = nullptr, uint64_t* d_key = nullptr, uint64_t* d_val = nullptr) {
+  if (n == 0) return;
+  const ScratchLock scratch_lock(r, s);
+  Replica::SurvScratch* sc = surv_scratch(r, s);
+  unsigned long long* ctr = next_counter(r, s);
+  const bool emit = d_leaf_off != nullptr;
+  const uint64_t want = (n + 255) / 256, max_exp = pattern_max_expansions();
+  with_alphabet(r.dev.alphabet, [&](auto A) {
+    with_flags(emit, [&](auto E) {
+      auto kernel = count_pattern_kernel<decltype(A)::value, E()>;
+      const dim3 g((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, resident_grid(r, kernel)))), b(256);
+      const size_t need = (size_t)PT_WS_WORDS * g.x * b.x;
+      if (sc->pat_stack.n < need) {
+        HIP_CHECK(hipStreamSynchronize(s));
+        sc->pat_stack.alloc(need);
+      }
+      hipLaunchKernelGGL(kernel, g, b, 0, s, r.dev, d_q, d_off, n, k, max_exp, d_counts, d_totals, d_nleaves, d_status, d_leaf_off, d_key, d_val,
+                         sc->pat_stack.p, ctr, d_tally);
+    });
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 // anchors (kernels_anchor.hip.h) on a resident grid.  d_anchor_off == nullptr: the count pass (d_n_anchors, d_status); else the
 // fill pass, which writes the records of query q at d_anchors[d_anchor_off[q] ...) (d_n_anchors / d_status nullable there)
 void launch_anchors(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, uint32_t min_len, int skip, uint64_t* d_n_anchors,

@@ -26,14 +26,18 @@ void upload_chunk(Replica& r, ChunkBuffers& cb, const uint8_t* qbytes, const uin
   cb.h_status.resize(n);
 }
 
-void count_mismatch_shard(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard sh, int k, uint64_t* counts_out) {
+// the launch that produces the leaves of a chunk (launch_count_mismatch, or launch_count_pattern with the same arguments)
+using LeafLaunch = void (*)(Replica&, const uint8_t*, const uint64_t*, uint64_t, int, uint64_t*, uint64_t*, uint64_t*, uint8_t*, hipStream_t,
+                            unsigned long long*, const uint64_t*, uint64_t*, uint64_t*);
+
+void count_mismatch_shard(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard sh, int k, uint64_t* counts_out, LeafLaunch launch_leaves) {
   HIP_CHECK(hipSetDevice(r.device));
   ChunkBuffers cb;
   for (Shard c : chunk_queries(qoff, sh.lo, sh.hi)) {
     const uint64_t n = c.hi - c.lo, w = (uint64_t)(k + 1);
     upload_chunk(r, cb, qbytes, qoff, c);
     if (cb.counts.n < n * w) cb.counts.alloc(n * w);
-    launch_count_mismatch(r, cb.q.p, cb.off.p, n, k, cb.counts.p, nullptr, nullptr, cb.status.p, r.stream);
+    launch_leaves(r, cb.q.p, cb.off.p, n, k, cb.counts.p, nullptr, nullptr, cb.status.p, r.stream, nullptr, nullptr, nullptr, nullptr);
     HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, r.stream));
     HIP_CHECK(hipMemcpyAsync(counts_out + c.lo * w, cb.counts.p, n * w * 8, hipMemcpyDeviceToHost, r.stream));
     HIP_CHECK(hipStreamSynchronize(r.stream));
@@ -59,13 +63,13 @@ struct MismatchHits {  // one shard's locate result, in query order
 // pass 1 (counts, leaves per query), scans, pass 2 (leaves), segmented sort by first row within each query, locate over the
 // flat leaf list, distances per hit.  false: the chunk holds more leaves than the cap and more than one query -- nothing appended
 bool locate_mismatch_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, bool want_pos, bool want_gpos, bool want_mm,
-                           MismatchHits& out) {
+                           MismatchHits& out, LeafLaunch launch_leaves) {
   const hipStream_t s = r.stream;
   const uint64_t n = c.hi - c.lo;
   ChunkBuffers cb;
   upload_chunk(r, cb, qbytes, qoff, c);
   DevBuf<uint64_t> totals(n), nleaves(n), hit_off(n + 1), leaf_off(n + 1), scratch(scan_tiles(n) + 1);
-  launch_count_mismatch(r, cb.q.p, cb.off.p, n, k, nullptr, totals.p, nleaves.p, cb.status.p, s);
+  launch_leaves(r, cb.q.p, cb.off.p, n, k, nullptr, totals.p, nleaves.p, cb.status.p, s, nullptr, nullptr, nullptr, nullptr);
   launch_scan(r, totals.p, n, hit_off.p, scratch.p, s);
   uint64_t total = 0, nleaf = 0;
   HIP_CHECK(hipMemcpyAsync(&total, hit_off.p + n, 8, hipMemcpyDeviceToHost, s));
@@ -81,7 +85,7 @@ bool locate_mismatch_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qo
   HIP_CHECK(hipMemcpyAsync(out.counts.data() + at_q, totals.p, n * 8, hipMemcpyDeviceToHost, s));
   if (total) {
     DevBuf<uint64_t> key(nleaf), val(nleaf), key2(nleaf), val2(nleaf), width(nleaf), leaf_hit_off(nleaf + 1), lscratch(scan_tiles(nleaf) + 1);
-    launch_count_mismatch(r, cb.q.p, cb.off.p, n, k, nullptr, nullptr, nullptr, nullptr, s, nullptr, leaf_off.p, key.p, val.p);
+    launch_leaves(r, cb.q.p, cb.off.p, n, k, nullptr, nullptr, nullptr, nullptr, s, nullptr, leaf_off.p, key.p, val.p);
     // DFS from the right end does not visit the leaves in row order: sort each query's leaves by their first row
     unsigned end_bit = 1;
     while (end_bit < 64 && (r.dev.bwt_len >> end_bit)) end_bit++;
@@ -110,12 +114,58 @@ bool locate_mismatch_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qo
 }
 
 void locate_mismatch_range(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, bool want_pos, bool want_gpos, bool want_mm,
-                           MismatchHits& out) {
+                           MismatchHits& out, LeafLaunch launch_leaves) {
   if (c.hi <= c.lo) return;
-  if (locate_mismatch_chunk(r, qbytes, qoff, c, k, want_pos, want_gpos, want_mm, out)) return;
+  if (locate_mismatch_chunk(r, qbytes, qoff, c, k, want_pos, want_gpos, want_mm, out, launch_leaves)) return;
   const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order
-  locate_mismatch_range(r, qbytes, qoff, Shard{c.lo, mid}, k, want_pos, want_gpos, want_mm, out);
-  locate_mismatch_range(r, qbytes, qoff, Shard{mid, c.hi}, k, want_pos, want_gpos, want_mm, out);
+  locate_mismatch_range(r, qbytes, qoff, Shard{c.lo, mid}, k, want_pos, want_gpos, want_mm, out, launch_leaves);
+  locate_mismatch_range(r, qbytes, qoff, Shard{mid, c.hi}, k, want_pos, want_gpos, want_mm, out, launch_leaves);
+}
+
+// the host batch drivers of both leaf-producing kernels (awry_count_mismatch_batch / awry_count_pattern_batch, and the locate pair)
+void count_leaves_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int k, uint64_t* counts_out, LeafLaunch launch_leaves) {
+  require(idx && qoff && (counts_out || n == 0), "null argument");
+  require(qbytes || qoff[n] == qoff[0], "null query bytes");
+  require_mismatches(k);
+  for_each_replica(idx, n, [&](Replica& r, Shard sh, int) { count_mismatch_shard(r, qbytes, qoff, sh, k, counts_out, launch_leaves); });
+}
+
+void locate_leaves_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int k, uint64_t** hit_off_out,
+                         awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** mismatches_out, LeafLaunch launch_leaves) {
+  require(idx && qoff && hit_off_out, "null argument");
+  require(qbytes || qoff[n] == qoff[0], "null query bytes");
+  require_mismatches(k);
+  std::vector<MismatchHits> res(std::max<size_t>(1, idx->reps.size()));
+  for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
+    HIP_CHECK(hipSetDevice(r.device));
+    for (Shard c : chunk_queries(qoff, sh.lo, sh.hi))
+      locate_mismatch_range(r, qbytes, qoff, c, k, hits_out != nullptr, global_pos_out != nullptr, mismatches_out != nullptr, res[g], launch_leaves);
+  });
+  // shards are contiguous in query order: the result arrays are their concatenation
+  MBuf<uint64_t> off, gp;
+  MBuf<awry_pos_t> hits;
+  MBuf<uint8_t> mm;
+  off.grow(n + 1);
+  off.p[0] = 0;
+  uint64_t q = 0, total = 0;
+  for (auto& x : res)
+    for (uint64_t c : x.counts) { total += c; off.p[++q] = total; }
+  require(q == n, "internal: shard results do not cover the batch");
+  if (hits_out) hits.grow(std::max<uint64_t>(1, total));
+  if (global_pos_out) gp.grow(std::max<uint64_t>(1, total));
+  if (mismatches_out) mm.grow(std::max<uint64_t>(1, total));
+  uint64_t at = 0;
+  for (auto& x : res) {
+    const uint64_t t = x.counts.empty() ? 0 : std::max({x.gpos.size(), x.pos.size(), x.mm.size()});
+    if (hits_out && t) pool_memcpy(hits.p + at, x.pos.data(), t * sizeof(awry_pos_t));
+    if (global_pos_out && t) pool_memcpy(gp.p + at, x.gpos.data(), t * 8);
+    if (mismatches_out && t) pool_memcpy(mm.p + at, x.mm.data(), t);
+    at += t;
+  }
+  *hit_off_out = off.release();
+  if (hits_out) *hits_out = hits.release();
+  if (global_pos_out) *global_pos_out = gp.release();
+  if (mismatches_out) *mismatches_out = mm.release();
 }
 
 }  // namespace

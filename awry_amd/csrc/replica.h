@@ -124,6 +124,8 @@ struct Replica {
     DevBuf<uint64_t> u_words;
     DevBuf<uint32_t> u_list;
     DevBuf<unsigned long long> u_bad;
+    // count_pattern_kernel: the DFS frames below the two a lane keeps in registers, [level][field][grid lane]
+    DevBuf<uint64_t> pat_stack;
     // work-queue heads of the chunk / locate kernels launched on this stream: launches on one stream are ordered, so a
     // head is free again by the time the ring comes back to it, however many launches other streams have in flight
     DevBuf<unsigned long long> counters;

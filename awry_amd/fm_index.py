@@ -129,6 +129,13 @@ def read_query_file(path):
     return qb, off
 
 
+def pattern_class(alphabet: int, letter) -> int:
+    """class mask of a pattern letter (parallel_count_pattern): bit s = symbol index s belongs to the class, 0 = the byte is
+    no class letter of that alphabet.  Needs no GPU."""
+    b = letter if isinstance(letter, int) else _as_bytes(letter)[0]
+    return int(_lib.load_library().awry_pattern_class(int(alphabet), b))
+
+
 class FmIndex:
     def __init__(self, handle):
         self._L = _lib.load_library()
@@ -405,6 +412,61 @@ class FmIndex:
     def dev_count_mismatch_tally(self, d_qbytes, d_qoff, n, k, d_counts, d_tally, d_status=None, stream=None, slot=0):
         """dev_count_mismatch + census: d_tally[2] += (expansions, queries searched)"""
         _check(self._L.awry_dev_count_mismatch_tally(self._h, slot, d_qbytes, d_qoff, n, int(k), d_counts, d_status, d_tally, stream))
+
+    # ------------------------------------------------------------------ class patterns (IUPAC / residue classes, <= k mismatches)
+    def parallel_count_pattern_csr(self, qbytes: np.ndarray, qoff: np.ndarray, k: int = 0, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """-> uint64[n, k + 1]: row i holds the occurrences of pattern i at exactly 0, 1, .., k mismatches.  A pattern is a string
+        of class letters (nucleotide IUPAC codes, amino B / Z / J / X; include/awry_hip.h states the definition and limits);
+        `out` (contiguous uint64[n, k + 1]) is filled and returned when given"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        w = max(int(k), 0) + 1
+        if out is None:
+            out = np.empty((n, w), dtype=np.uint64)
+        elif out.dtype != np.uint64 or out.shape != (n, w) or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous uint64 array of shape (n, k + 1)")
+        _check(self._L.awry_count_pattern_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(k), out.ctypes.data_as(_u64p)))
+        return out
+
+    def parallel_count_pattern(self, patterns: Iterable, k: int = 0) -> np.ndarray:
+        """counts per pattern and distance, uint64[n, k + 1], in input order"""
+        return self.parallel_count_pattern_csr(*pack_queries(patterns), k)
+
+    def parallel_locate_pattern_csr(self, qbytes: np.ndarray, qoff: np.ndarray, k: int = 0, want_pos: bool = True):
+        """-> (hit_off uint64[n+1], global_pos uint64[total], pos uint64[total, 2], mismatches uint8[total]): hits of pattern i
+        in ascending BWT-row order (the matched strings in symbol-index order) with the distance of each; want_pos=False
+        leaves pos empty"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        off, hits, gp, mm = _u64p(), C.POINTER(_lib.Pos)(), _u64p(), C.POINTER(C.c_uint8)()
+        _check(self._L.awry_locate_pattern_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(k), C.byref(off),
+                                                 C.byref(hits) if want_pos else None, C.byref(gp), C.byref(mm)))
+        offs = _adopt(self._L, off, n + 1, np.uint64)
+        tot = int(offs[-1])
+        g = _adopt(self._L, gp, tot, np.uint64)
+        p = _adopt(self._L, hits, 2 * tot, np.uint64).reshape(-1, 2) if want_pos else np.zeros((0, 2), np.uint64)
+        d = _adopt(self._L, mm, tot, np.uint8)
+        return offs, g, p, d
+
+    def count_string_pattern(self, pattern, k: int = 0) -> int:
+        """occurrences of one class pattern with at most k mismatches"""
+        return int(self.parallel_count_pattern([pattern], k).sum())
+
+    def locate_string_pattern(self, pattern, k: int = 0):
+        """-> [(LocalizedSequencePosition, distance)] of one class pattern, ascending BWT-row order"""
+        off, _, p, d = self.parallel_locate_pattern_csr(*pack_queries([pattern]), k)
+        return [(LocalizedSequencePosition(int(a), int(b)), int(m)) for (a, b), m in zip(p, d)]
+
+    def dev_count_pattern(self, d_qbytes, d_qoff, n, k, d_counts, d_status=None, stream=None, slot=0):
+        """device-resident pattern count: d_counts[n * (k + 1)] (u64), optional d_status[n] bytes (0 ok, 1 empty, 2 sentinel,
+        3 byte >= 0x80, 4 no class letter, 5 too many class positions, 6 abandoned at the expansion cap)"""
+        _check(self._L.awry_dev_count_pattern(self._h, slot, d_qbytes, d_qoff, n, int(k), d_counts, d_status, stream))
+
+    def dev_count_pattern_tally(self, d_qbytes, d_qoff, n, k, d_counts, d_tally, d_status=None, stream=None, slot=0):
+        """dev_count_pattern + census: d_tally[3]: [0] += expansions, [1] += patterns searched, [2] = max(deepest stack, frames)"""
+        _check(self._L.awry_dev_count_pattern_tally(self._h, slot, d_qbytes, d_qoff, n, int(k), d_counts, d_status, d_tally, stream))
 
     # ------------------------------------------------------------------ anchors (greedy longest-match factorisation)
     def parallel_anchors_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 1, skip: int = 0):

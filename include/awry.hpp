@@ -170,6 +170,32 @@ class FmIndex {
     awry_free_buffer(hoff); awry_free_buffer(hits); awry_free_buffer(mm);
     return out;
   }
+  // class patterns (no counterpart in the reference; the definition and the limits are in awry_hip.h): IUPAC / residue-class
+  // letters with up to k mismatches.  counts[i * (k + 1) + d] = occurrences of pattern i at exactly d mismatches
+  template <class StrRange>
+  std::vector<uint64_t> parallel_count_pattern(const StrRange& patterns, int k = 0) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(patterns, bytes, off);
+    std::vector<uint64_t> out((off.size() - 1) * (size_t)(k >= 0 ? k + 1 : 1));
+    check(awry_count_pattern_batch(h_, bytes.data(), off.data(), off.size() - 1, k, out.data()));
+    return out;
+  }
+  // hits of each pattern in ascending BWT-row order (the matched strings in symbol-index order), with their distances
+  template <class StrRange>
+  std::vector<std::vector<MismatchHit>> parallel_locate_pattern(const StrRange& patterns, int k = 0) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(patterns, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* hoff = nullptr; awry_pos_t* hits = nullptr; uint8_t* mm = nullptr;
+    check(awry_locate_pattern_batch(h_, bytes.data(), off.data(), n, k, &hoff, &hits, nullptr, &mm));
+    std::vector<std::vector<MismatchHit>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = hoff[i]; j < hoff[i + 1]; j++) out[i].push_back({{hits[j].seq_idx, hits[j].local_pos}, mm[j]});
+    awry_free_buffer(hoff); awry_free_buffer(hits); awry_free_buffer(mm);
+    return out;
+  }
+  // class mask of a pattern letter: bit s = symbol index s belongs to the class, 0 = not a class letter (needs no GPU)
+  static uint32_t pattern_class(int alphabet, char letter) { return awry_pattern_class(alphabet, (uint8_t)letter); }
   // anchors (no counterpart in the reference; the definition is in awry_hip.h): the greedy longest-match factorisation of
   // every query, found right to left -- q[q_begin .. q_begin + q_len) occupies the BWT rows `rows`
   struct Anchor {

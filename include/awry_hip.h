@@ -172,6 +172,52 @@ int awry_locate_mismatch_batch(awry_index_t *idx, const uint8_t *qbytes, const u
                                int max_mismatches, uint64_t **hit_off_out, awry_pos_t **hits_out,
                                uint64_t **global_pos_out, uint8_t **mismatches_out);
 
+/* ---- class patterns: IUPAC / residue-class search with up to k mismatches (no counterpart in the reference) ----
+ * A pattern is a string of class letters, case-insensitive, each a set of symbol indices (the indices of the alphabet):
+ *   nucleotide  A C G T are themselves, U = T; R={A,G} Y={C,T} S={C,G} W={A,T} K={G,T} M={A,C} B={C,G,T} D={A,G,T}
+ *               H={A,C,T} V={A,C,G}; N={A,C,G,T}.  No class holds the text's ambiguity symbol (index 4, the N that also joins
+ *               records).
+ *   amino       the 20 standard residues are themselves; B={D,N} Z={E,Q} J={I,L}; X = the 20 standard residues.  No class
+ *               holds the text's X (index 20).
+ * Any other byte is rejected.  A class of more than one symbol is a class position.
+ * For a pattern of L positions with classes S_0 .. S_{L-1} the distance of text position p is the number of j with
+ * text[p + j] not in S_j; p is an occurrence with <= k mismatches when text[p .. p + L) holds no '$' and its distance is <= k.
+ * A mismatching text symbol may be any non-sentinel symbol outside the class, the ambiguity symbol included (the rule of
+ * awry_count_mismatch_batch): at k = 0 no hit spans a record join or a text N / X, at k >= 1 one may, at one mismatch per
+ * such symbol.  max_mismatches is 0..AWRY_MAX_MISMATCHES, else AWRY_ERR_ARG.  For a pattern of unambiguous letters only,
+ * counts, hits, order and distances are exactly those of the mismatch entry points at the same k, and at k = 0 exactly those
+ * of awry_count_batch / awry_locate_batch.  (Those paths keep mapping a query N / X to the text's ambiguity symbol.)
+ * Order: distinct matched strings have disjoint row ranges; the hits of one pattern are in ascending BWT-row order, that is
+ * the matched strings in lexicographic order of symbol indices and within a string the order of awry_locate_batch.
+ * Limits: at most AWRY_MAX_CLASS_POSITIONS class positions per pattern (the search then holds at most min(L - 1, class
+ * positions + k) <= AWRY_PATTERN_MAX_FRAMES stack frames), and at most AWRY_PATTERN_DEFAULT_MAX_EXPANSIONS expansions (one
+ * expansion = the Occ of every symbol at the two rows of one node) per pattern; env AWRY_PATTERN_MAX_EXPANSIONS, read per
+ * call, replaces the latter.  A pattern whose search needs more is abandoned, not run to the end: the default, 2^19, is what one
+ * lane of a fully occupied MI355X works through in about 2 s on a 3.1 Gbp text (DESIGN.md 5d has the measurement), so that no
+ * pattern keeps a launch busy for longer on a shared card.  This is the one case in which a plain-letter pattern and the
+ * mismatch entry points differ: those have no cap.
+ * Rejected, as on the other paths: an empty pattern, '$' / '#', a byte >= 0x80; and: a byte that is no class letter, more than
+ * AWRY_MAX_CLASS_POSITIONS class positions, the expansion cap exceeded.  Host batch calls then fail the whole batch with
+ * AWRY_ERR_INVALID_QUERY (the message names the query index and the reason) and leave the out-pointers untouched; device calls
+ * write the status byte (AWRY_Q_*) and zero counts. */
+enum { AWRY_MAX_CLASS_POSITIONS = 16, AWRY_PATTERN_MAX_FRAMES = 18, AWRY_PATTERN_DEFAULT_MAX_EXPANSIONS = 1 << 19 };
+/* status byte of the device-resident query calls (d_status) */
+enum {
+  AWRY_Q_OK = 0, AWRY_Q_EMPTY = 1, AWRY_Q_SENTINEL = 2, AWRY_Q_NON_ASCII = 3,
+  AWRY_Q_NOT_CLASS_LETTER = 4, AWRY_Q_CLASS_POSITIONS = 5, AWRY_Q_EXPANSION_CAP = 6 /* patterns only */
+};
+/* class mask of an ASCII byte as a pattern letter: bit s = symbol index s belongs to the class, 0 = not a class letter (or
+ * an unknown alphabet id).  The one table of host and device; needs no GPU. */
+uint32_t awry_pattern_class(int alphabet, uint8_t ascii);
+/* counts_out[n * (k + 1)]: row i holds the occurrences of pattern i at exactly 0, 1, .., k mismatches */
+int awry_count_pattern_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n,
+                             int max_mismatches, uint64_t *counts_out);
+/* arrays as awry_locate_mismatch_batch takes and returns them, nullable likewise; the leaf capacity and its env var
+ * (AWRY_MISMATCH_LEAF_CAP) are shared with it */
+int awry_locate_pattern_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n,
+                              int max_mismatches, uint64_t **hit_off_out, awry_pos_t **hits_out,
+                              uint64_t **global_pos_out, uint8_t **mismatches_out);
+
 /* ---- anchors: greedy longest-match factorisation of a query (no counterpart in the reference) ---------------
  * What a mapper does with a read that does not occur as a whole: cut it into maximal exact matches and chain those.
  * Queries are mapped to symbol indices exactly as on the exact path (letters case-insensitive, U = T, any other byte N /
@@ -324,6 +370,15 @@ int awry_dev_count_mismatch(awry_index_t *idx, int slot, const void *d_qbytes, c
  * node, two block lines --, queries searched}; per-lane atomics at the end of the launch only */
 int awry_dev_count_mismatch_tally(awry_index_t *idx, int slot, const void *d_qbytes, const void *d_qoff, uint64_t n,
                                   int max_mismatches, void *d_counts, void *d_status, void *d_tally, void *stream);
+/* class-pattern count (see awry_count_pattern_batch), device-resident form (no synchronisation; the stack workspace is owned
+ * by the replica, per stream, and grows on first use): ASCII patterns + u64 offsets[n+1] -> d_counts[n * (k + 1)], optional
+ * d_status[n] bytes (AWRY_Q_*; non-zero: rejected or abandoned pattern, counts 0) */
+int awry_dev_count_pattern(awry_index_t *idx, int slot, const void *d_qbytes, const void *d_qoff, uint64_t n,
+                           int max_mismatches, void *d_counts, void *d_status, void *stream);
+/* the same with a work census: d_tally[3] (u64, caller-zeroed): [0] += expansions, [1] += patterns searched, [2] = max with
+ * the deepest stack of the launch, in frames; per-lane atomics at the end of the launch only */
+int awry_dev_count_pattern_tally(awry_index_t *idx, int slot, const void *d_qbytes, const void *d_qoff, uint64_t n,
+                                 int max_mismatches, void *d_counts, void *d_status, void *d_tally, void *stream);
 /* anchors (see awry_anchor_batch), device-resident form: no synchronisation, no allocation, any stream.  Two calls with the
  * caller's scan between them: d_anchor_off == NULL is the count pass -- ASCII queries + u64 offsets[n+1] -> d_n_anchors[n]
  * (u64) and optional d_status[n] bytes (non-zero: rejected query, 0 anchors); awry_dev_scan_counts turns d_n_anchors into

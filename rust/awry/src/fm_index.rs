@@ -455,6 +455,58 @@ impl FmIndex {
         Ok(out)
     }
 
+    /// Class-pattern counts (no counterpart in the reference; the definition and the limits are in include/awry_hip.h): a pattern
+    /// is a string of class letters (nucleotide IUPAC codes, amino B / Z / J / X); row i of the result holds the occurrences of
+    /// pattern i at exactly 0, 1, .., `max_mismatches` mismatches (a position mismatches when the text symbol is outside the
+    /// letter's class); `max_mismatches` must be 0, 1 or 2.
+    pub fn parallel_count_pattern<'a>(&self, patterns: impl ParallelIterator<Item = &'a str>, max_mismatches: u32) -> Result<Vec<Vec<u64>>, AwryError> {
+        let csr = to_csr(patterns);
+        let n = csr.offsets.len() - 1;
+        let w = max_mismatches as usize + 1;
+        let mut counts = vec![0u64; n * w];
+        check(unsafe {
+            sys::awry_count_pattern_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, max_mismatches as i32, counts.as_mut_ptr())
+        })?;
+        Ok(counts.chunks(w).map(|c| c.to_vec()).collect())
+    }
+
+    /// Class-pattern locations: per pattern, `(position, distance)` in ascending BWT-row order (the matched strings in
+    /// symbol-index order).
+    pub fn parallel_locate_pattern<'a>(
+        &self,
+        patterns: impl ParallelIterator<Item = &'a str>,
+        max_mismatches: u32,
+    ) -> Result<Vec<Vec<(LocalizedSequencePosition, u8)>>, AwryError> {
+        let csr = to_csr(patterns);
+        let n = csr.offsets.len() - 1;
+        let mut hit_off: *mut u64 = std::ptr::null_mut();
+        let mut hits: *mut sys::awry_pos_t = std::ptr::null_mut();
+        let mut mm: *mut u8 = std::ptr::null_mut();
+        check(unsafe {
+            sys::awry_locate_pattern_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, max_mismatches as i32, &mut hit_off,
+                                           &mut hits, std::ptr::null_mut(), &mut mm)
+        })?;
+        let out = unsafe {
+            let off = std::slice::from_raw_parts(hit_off, n + 1);
+            let total = off[n] as usize;
+            let flat: &[sys::awry_pos_t] = if total == 0 { &[] } else { std::slice::from_raw_parts(hits, total) };
+            let dist: &[u8] = if total == 0 { &[] } else { std::slice::from_raw_parts(mm, total) };
+            (0..n)
+                .map(|i| {
+                    (off[i] as usize..off[i + 1] as usize)
+                        .map(|j| (LocalizedSequencePosition::new(flat[j].seq_idx as usize, flat[j].local_pos as usize), dist[j]))
+                        .collect::<Vec<_>>()
+                })
+                .collect::<Vec<_>>()
+        };
+        unsafe {
+            sys::awry_free_buffer(hit_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(hits as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(mm as *mut std::os::raw::c_void);
+        }
+        Ok(out)
+    }
+
     /// Anchors (no counterpart in the reference; the definition is in include/awry_hip.h): per query, its greedy longest-match
     /// factorisation found right to left, as `(q_begin, q_len, SearchRange)` -- the maximal exact matches a mapper chains when a
     /// read does not occur as a whole.  Anchors shorter than `min_len` (>= 1) are left out; `skip_failed_letter` leaves the
