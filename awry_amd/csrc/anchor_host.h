@@ -1,10 +1,11 @@
-// anchor_host.h -- shard drivers of anchors (greedy longest-match factorisation) and of locating them
+// anchor_host.h -- shard drivers of anchors (greedy longest-match factorisation), of SMEMs (all super-maximal exact matches) and
+// of locating either: one driver over awry_anchor_t records, parameterised over the launcher that finds them
 // A part of awry_hip.hip (one translation unit): included there, in order, and not on its own.
 #pragma once
 
 namespace {
 
-// ---- anchors (kernels_anchor.hip.h) -------------------------------------------------------------------------
+// ---- anchors (kernels_anchor.hip.h) and SMEMs (kernels_smem.hip.h) -------------------------------------------------
 
 static_assert(sizeof(Anchor) == sizeof(awry_anchor_t) && sizeof(awry_anchor_t) == 24 && offsetof(Anchor, q_len) == offsetof(awry_anchor_t, q_len) &&
                   offsetof(Anchor, start_row) == offsetof(awry_anchor_t, start_row) && offsetof(Anchor, count) == offsetof(awry_anchor_t, count),
@@ -23,6 +24,21 @@ uint64_t anchor_hit_cap() {
   return v ? std::min<uint64_t>(v, 1ull << 31) : (1ull << 26);
 }
 
+void require_smem_args(uint32_t min_len) {
+  if (min_len < 1) throw ArgError("min_len must be at least 1");
+}
+
+// what finds the records: find(r, d_q, d_off, n, d_n, d_rec_off, d_rec, d_status, stream) -- d_rec_off == nullptr is the count
+// pass, else the fill pass (launch_anchors' protocol)
+auto anchor_finder(uint32_t min_len, int skip) {
+  return [=](Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, uint64_t* d_n, const uint64_t* d_rec_off, Anchor* d_rec, uint8_t* d_status,
+             hipStream_t s) { launch_anchors(r, d_q, d_off, n, min_len, skip, d_n, d_rec_off, d_rec, d_status, s); };
+}
+auto smem_finder(uint32_t min_len) {
+  return [=](Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, uint64_t* d_n, const uint64_t* d_rec_off, Anchor* d_rec, uint8_t* d_status,
+             hipStream_t s) { launch_smems(r, d_q, d_off, n, min_len, d_n, d_rec_off, d_rec, d_status, s); };
+}
+
 struct AnchorHits {  // one shard's result, in query order
   std::vector<uint64_t> n_anchors;     // per query
   std::vector<awry_anchor_t> anchors;
@@ -34,8 +50,9 @@ struct AnchorHits {  // one shard's result, in query order
 
 // count pass, scan, fill pass; with max_hits != 0 also ranges, scan of the located counts and the locate pipeline over the
 // flat anchor list.  false: the chunk's located hits exceed the capacity and it holds more than one query -- nothing appended
-bool anchor_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, uint32_t min_len, int skip, uint64_t max_hits, bool want_pos,
-                  bool want_gpos, AnchorHits& out) {
+template <class Find>
+bool anchor_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, const Find& find, uint64_t max_hits, bool want_pos, bool want_gpos,
+                  AnchorHits& out) {
   const hipStream_t s = r.stream;
   const uint64_t n = c.hi - c.lo;
   for (uint64_t i = c.lo; i < c.hi; i++)
@@ -43,7 +60,7 @@ bool anchor_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard
   ChunkBuffers cb;
   upload_chunk(r, cb, qbytes, qoff, c);
   DevBuf<uint64_t> na(n), aoff(n + 1), scratch(scan_tiles(n) + 1);
-  launch_anchors(r, cb.q.p, cb.off.p, n, min_len, skip, na.p, nullptr, nullptr, cb.status.p, s);
+  find(r, cb.q.p, cb.off.p, n, na.p, nullptr, nullptr, cb.status.p, s);
   launch_scan(r, na.p, n, aoff.p, scratch.p, s);
   uint64_t total = 0;
   HIP_CHECK(hipMemcpyAsync(&total, aoff.p + n, 8, hipMemcpyDeviceToHost, s));
@@ -52,7 +69,7 @@ bool anchor_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard
   check_status(cb, c.lo);
   if (total >= (1ull << 32)) throw ArgError("a chunk of queries with 2^32 anchors or more");
   DevBuf<Anchor> d_anchors(std::max<uint64_t>(total, 1));
-  launch_anchors(r, cb.q.p, cb.off.p, n, min_len, skip, nullptr, aoff.p, d_anchors.p, nullptr, s);
+  find(r, cb.q.p, cb.off.p, n, nullptr, aoff.p, d_anchors.p, nullptr, s);
   DevBuf<uint64_t> ranges, located, hoff, lscratch, d_gpos, d_pos;
   uint64_t nhits = 0;
   if (max_hits && total) {
@@ -84,23 +101,25 @@ bool anchor_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard
   return true;
 }
 
-void anchor_range(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, uint32_t min_len, int skip, uint64_t max_hits, bool want_pos,
-                  bool want_gpos, AnchorHits& out) {
+template <class Find>
+void anchor_range(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, const Find& find, uint64_t max_hits, bool want_pos, bool want_gpos,
+                  AnchorHits& out) {
   if (c.hi <= c.lo) return;
-  if (anchor_chunk(r, qbytes, qoff, c, min_len, skip, max_hits, want_pos, want_gpos, out)) return;
+  if (anchor_chunk(r, qbytes, qoff, c, find, max_hits, want_pos, want_gpos, out)) return;
   const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order
-  anchor_range(r, qbytes, qoff, Shard{c.lo, mid}, min_len, skip, max_hits, want_pos, want_gpos, out);
-  anchor_range(r, qbytes, qoff, Shard{mid, c.hi}, min_len, skip, max_hits, want_pos, want_gpos, out);
+  anchor_range(r, qbytes, qoff, Shard{c.lo, mid}, find, max_hits, want_pos, want_gpos, out);
+  anchor_range(r, qbytes, qoff, Shard{mid, c.hi}, find, max_hits, want_pos, want_gpos, out);
 }
 
 // the batch entry points' common body: shards over the replicas, results stitched in query order into pinned-pool arrays.
-// max_hits == 0: anchors only.  The out-pointers are written only when everything has succeeded.
-void anchor_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, int skip, uint64_t max_hits,
+// max_hits == 0: records only.  The out-pointers are written only when everything has succeeded.
+template <class Find>
+void anchor_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, const Find& find, uint64_t max_hits,
                   uint64_t** anchor_off_out, awry_anchor_t** anchors_out, uint64_t** hit_off_out, awry_pos_t** hits_out, uint64_t** global_pos_out) {
   std::vector<AnchorHits> res(std::max<size_t>(1, idx->reps.size()));
   for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
     HIP_CHECK(hipSetDevice(r.device));
-    for (Shard c : chunk_queries(qoff, sh.lo, sh.hi)) anchor_range(r, qbytes, qoff, c, min_len, skip, max_hits, hits_out != nullptr, global_pos_out != nullptr, res[g]);
+    for (Shard c : chunk_queries(qoff, sh.lo, sh.hi)) anchor_range(r, qbytes, qoff, c, find, max_hits, hits_out != nullptr, global_pos_out != nullptr, res[g]);
   });
   MBuf<uint64_t> aoff, hoff, gp;
   MBuf<awry_anchor_t> anchors;

@@ -371,7 +371,7 @@ int awry_anchor_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* 
     require(idx && qoff && anchor_off_out && anchors_out, "null argument");
     require(qbytes || qoff[n] == qoff[0], "null query bytes");
     require_anchor_args(min_len, skip);
-    anchor_batch(idx, qbytes, qoff, n, min_len, skip, 0, anchor_off_out, anchors_out, nullptr, nullptr, nullptr);
+    anchor_batch(idx, qbytes, qoff, n, anchor_finder(min_len, skip), 0, anchor_off_out, anchors_out, nullptr, nullptr, nullptr);
   });
 }
 
@@ -383,7 +383,29 @@ int awry_locate_anchors_batch(awry_index_t* idx, const uint8_t* qbytes, const ui
     require(qbytes || qoff[n] == qoff[0], "null query bytes");
     require_anchor_args(min_len, skip);
     require(max_hits != 0, "max_hits must be at least 1 (a one-letter anchor has a quarter of the text as hits)");
-    anchor_batch(idx, qbytes, qoff, n, min_len, skip, max_hits, anchor_off_out, anchors_out, hit_off_out, hits_out, global_pos_out);
+    anchor_batch(idx, qbytes, qoff, n, anchor_finder(min_len, skip), max_hits, anchor_off_out, anchors_out, hit_off_out, hits_out, global_pos_out);
+  });
+}
+
+int awry_smem_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t** smem_off_out,
+                    awry_anchor_t** smems_out) {
+  return guarded([&] {
+    require(idx && qoff && smem_off_out && smems_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_smem_args(min_len);
+    anchor_batch(idx, qbytes, qoff, n, smem_finder(min_len), 0, smem_off_out, smems_out, nullptr, nullptr, nullptr);
+  });
+}
+
+int awry_locate_smems_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits,
+                            uint64_t** smem_off_out, awry_anchor_t** smems_out, uint64_t** hit_off_out, awry_pos_t** hits_out,
+                            uint64_t** global_pos_out) {
+  return guarded([&] {
+    require(idx && qoff && smem_off_out && smems_out && hit_off_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_smem_args(min_len);
+    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
+    anchor_batch(idx, qbytes, qoff, n, smem_finder(min_len), max_hits, smem_off_out, smems_out, hit_off_out, hits_out, global_pos_out);
   });
 }
 
@@ -812,6 +834,22 @@ int awry_dev_anchors_tally(awry_index_t* idx, int slot, const void* d_qbytes, co
     require(n == 0 || (d_qbytes && d_qoff && (d_anchor_off ? d_anchors != nullptr : d_n_anchors != nullptr)), "null device pointer");
     launch_anchors(r, (const uint8_t*)d_qbytes, (const uint64_t*)d_qoff, n, min_len, skip, (uint64_t*)d_n_anchors, (const uint64_t*)d_anchor_off,
                    (Anchor*)d_anchors, (uint8_t*)d_status, (hipStream_t)stream, (unsigned long long*)d_tally);
+  });
+}
+
+int awry_dev_smems(awry_index_t* idx, int slot, const void* d_qbytes, const void* d_qoff, uint64_t n, uint32_t min_len, void* d_n_smems,
+                   const void* d_smem_off, void* d_smems, void* d_status, void* stream) {
+  return awry_dev_smems_tally(idx, slot, d_qbytes, d_qoff, n, min_len, d_n_smems, d_smem_off, d_smems, d_status, nullptr, stream);
+}
+
+int awry_dev_smems_tally(awry_index_t* idx, int slot, const void* d_qbytes, const void* d_qoff, uint64_t n, uint32_t min_len, void* d_n_smems,
+                         const void* d_smem_off, void* d_smems, void* d_status, void* d_tally, void* stream) {
+  return guarded([&] {
+    require_smem_args(min_len);
+    Replica& r = replica(idx, slot);
+    require(n == 0 || (d_qbytes && d_qoff && (d_smem_off ? d_smems != nullptr : d_n_smems != nullptr)), "null device pointer");
+    launch_smems(r, (const uint8_t*)d_qbytes, (const uint64_t*)d_qoff, n, min_len, (uint64_t*)d_n_smems, (const uint64_t*)d_smem_off, (Anchor*)d_smems,
+                 (uint8_t*)d_status, (hipStream_t)stream, (unsigned long long*)d_tally);
   });
 }
 

@@ -29,6 +29,9 @@
 //                         + LCX_QUAD_READS_KERNEL<R>         the listed reads as one pool, when the left-context index is resident [lcx_kernels]
 //   anchors, any query    ANCHOR_SCALAR_KERNEL<A, FILL>      greedy longest-match factorisation, one query per lane: count pass, scan, fill pass [kernels_anchor]
 //                         + ANCHOR_RANGES_KERNEL             anchor records -> row pairs and located counts for the locate kernels [kernels_anchor]
+//   SMEMs, any query      SMEM_SCALAR_KERNEL<A, FWD, FILL>   all super-maximal exact matches, one query per lane: forward extension by a search of
+//                                                            the dense SA against text8 (FWD = SA) or by bisection over backward searches (FWD = LF),
+//                                                            then the anchor walk; count pass, scan, fill pass, ANCHOR_RANGES_KERNEL [kernels_smem]
 //   count, wide rows      count_nt2_wide_kernel, count_nt2_wide_probe_kernel   64-bit rows [kernels_wide]
 //   locate                LOCATE_TILE_KERNEL<A>              hit -> row, sampled / verified hits finished [this file]
 //                         + LOCATE_WALK_NT_LANE_KERNEL       LF walks of the rest, one hit per lane, whole block per step [this file]
@@ -52,6 +55,7 @@
 #include "kernels_scan.hip.h"
 #include "kernels_count.hip.h"     // block_excl_scan
 #include "kernels_anchor.hip.h"    // step_scalar, ByteStream, seed_probe, tally_add
+#include "kernels_smem.hip.h"      // Anchor, ascii_query_status, seed_rows_ending_at, nt_indices8
 #include "kernels_aa_kmer.hip.h"   // QueryList, tally_add
 #include "kernels_quad.hip.h"      // slice_mask
 #include "lcx.hip.h"               // quad_sum, Text20

@@ -17,6 +17,66 @@ namespace awry {
 
 struct Anchor { uint32_t q_begin, q_len; uint64_t start_row, count; };  // == awry_anchor_t (checked in anchor_host.h)
 
+// Status of the ASCII query bytes[qb .. qb + L): Q_EMPTY, Q_NON_ASCII (a byte >= 0x80), Q_SENTINEL ('$' / '#'), else Q_OK --
+// the prologue of every kernel of this file and of kernels_smem.hip.h.  `ascii` is the lane's stream over `bytes`.
+template <int A>
+__device__ __forceinline__ uint8_t ascii_query_status(const uint8_t* __restrict__ bytes, ByteStream& ascii, const uint8_t* lut, uint64_t qb, uint32_t L) {
+  uint8_t st = L ? Q_OK : Q_EMPTY;
+  if (A == NUCLEOTIDE) {  // eight bytes at a time: any byte >= 0x80, any '$' or '#'
+    constexpr uint64_t K7F = 0x7F7F7F7F7F7F7F7Full, K80 = 0x8080808080808080ull;
+    uint64_t high = 0, sent = 0;
+    for (uint32_t j = 0; j < L; j += 8) {
+      uint64_t x;
+      __builtin_memcpy(&x, bytes + qb + j, 8);
+      if (L - j < 8) x &= (1ull << (8 * (L - j))) - 1;  // bytes past the query read as 0: neither test fires
+      high |= x & K80;
+      const uint64_t t1 = x ^ 0x2424242424242424ull, t2 = x ^ 0x2323232323232323ull;
+      sent |= (((((t1 & K7F) + K7F) | t1) & K80) ^ K80) | (((((t2 & K7F) + K7F) | t2) & K80) ^ K80);
+    }
+    if (high) st = Q_NON_ASCII;
+    else if (sent && st == Q_OK) st = Q_SENTINEL;
+  } else {
+    for (uint32_t j = 0; j < L; j++) {
+      const uint8_t s = lut[ascii[qb + j]];
+      if (s == 0xFF) st = Q_NON_ASCII;
+      else if (s == 0 && st == Q_OK) st = Q_SENTINEL;
+    }
+  }
+  return st;
+}
+
+// The table jump of a backward search that starts at e (needs e >= k = seed_k > 0): true, with [sp, ep] = the rows of
+// q[e-k..e), when those k letters are all table digits and their entry states a row interval of count > 0 -- not when it is
+// saturated, a position seed (.sp is a text position), an amino context entry, or empty.
+template <int A>
+__device__ __forceinline__ bool seed_rows_ending_at(const DevIndex& ix, ByteStream& ascii, const uint8_t* lut, uint64_t qb, uint32_t e, uint32_t k,
+                                                    uint64_t& sp, uint64_t& ep) {
+  uint64_t sidx = 0;
+  bool digits = true;
+  if (A == NUCLEOTIDE) {
+    for (uint32_t j = 0; j < k; j++) {  // leftmost letter of the window least significant
+      const int letter = nt_letter_of_index(lut[ascii[qb + e - k + j]]);
+      digits = digits && letter >= 0;
+      sidx |= (uint64_t)(letter & 3) << (2 * j);
+    }
+  } else {
+    for (int j = (int)k - 1; j >= 0; j--) {
+      const int letter = aa_letter_of_index(lut[ascii[qb + e - k + j]]);
+      digits = digits && letter >= 0;
+      sidx = sidx * AA_SEED_SIGMA + (uint64_t)(letter < 0 ? 0 : letter);
+    }
+  }
+  if (!digits) return false;
+  const SeedEntry se = seed_probe(ix.seed + sidx);
+  const uint32_t cnt = A == NUCLEOTIDE ? seed_cnt(se) : aa_seed_cnt(se);
+  const bool rows = cnt != 0 && cnt != (A == NUCLEOTIDE ? SEED_CNT_SAT : AA_SEED_CNT_SAT) && !(ix.seed_pos && cnt == 1) &&
+                    !(A == NUCLEOTIDE ? seed_has_ctx(se) : aa_seed_is_ctx(se));
+  if (!rows) return false;
+  sp = se.sp;
+  ep = (uint64_t)se.sp + cnt - 1;
+  return true;
+}
+
 // Each lane runs a FLAT state machine over its query: one loop iteration either starts an anchor at e (the initial range
 // from prefix_sums, or from one seed-table probe that states a row interval) or takes ONE step_scalar with the next letter
 // to the left, into a second range, so that a step that empties the range is simply not committed.  There is no loop per
@@ -49,27 +109,7 @@ void anchor_scalar_kernel(DevIndex ix, const uint8_t* __restrict__ ascii, const 
     const uint64_t qb = off[q];
     const uint32_t L = (uint32_t)(off[q + 1] - qb);
     ByteStream ascii(ascii_bytes);  // shadows the pointer: same indexing, 8 bytes per load
-    uint8_t st = L ? Q_OK : Q_EMPTY;
-    if (A == NUCLEOTIDE) {  // eight bytes at a time: any byte >= 0x80, any '$' or '#'
-      constexpr uint64_t K7F = 0x7F7F7F7F7F7F7F7Full, K80 = 0x8080808080808080ull;
-      uint64_t high = 0, sent = 0;
-      for (uint32_t j = 0; j < L; j += 8) {
-        uint64_t x;
-        __builtin_memcpy(&x, ascii_bytes + qb + j, 8);
-        if (L - j < 8) x &= (1ull << (8 * (L - j))) - 1;  // bytes past the query read as 0: neither test fires
-        high |= x & K80;
-        const uint64_t t1 = x ^ 0x2424242424242424ull, t2 = x ^ 0x2323232323232323ull;
-        sent |= (((((t1 & K7F) + K7F) | t1) & K80) ^ K80) | (((((t2 & K7F) + K7F) | t2) & K80) ^ K80);
-      }
-      if (high) st = Q_NON_ASCII;
-      else if (sent && st == Q_OK) st = Q_SENTINEL;
-    } else {
-      for (uint32_t j = 0; j < L; j++) {
-        const uint8_t s = lut[ascii[qb + j]];
-        if (s == 0xFF) st = Q_NON_ASCII;
-        else if (s == 0 && st == Q_OK) st = Q_SENTINEL;
-      }
-    }
+    const uint8_t st = ascii_query_status<A>(ascii_bytes, ascii, lut, qb, L);
     uint32_t na = 0, t_steps = 0, t_probes = 0;
     if (st == Q_OK) {
       Anchor* const out = FILL ? anchors + anchor_off[q] : nullptr;                     // this query's slots,
@@ -80,37 +120,8 @@ void anchor_scalar_kernel(DevIndex ix, const uint8_t* __restrict__ ascii, const 
         bool ended = false;  // the anchor in hand cannot grow: its next letter empties the range, or it has reached letter 0
         if (i == e) {        // ---- start an anchor at e
           if (e == 0) break;
-          bool jumped = false;
-          if (k && e >= k) {
-            uint64_t sidx = 0;
-            bool digits = true;
-            if (A == NUCLEOTIDE) {
-              for (uint32_t j = 0; j < k; j++) {  // leftmost letter of the window least significant
-                const int letter = nt_letter_of_index(lut[ascii[qb + e - k + j]]);
-                digits = digits && letter >= 0;
-                sidx |= (uint64_t)(letter & 3) << (2 * j);
-              }
-            } else {
-              for (int j = (int)k - 1; j >= 0; j--) {
-                const int letter = aa_letter_of_index(lut[ascii[qb + e - k + j]]);
-                digits = digits && letter >= 0;
-                sidx = sidx * AA_SEED_SIGMA + (uint64_t)(letter < 0 ? 0 : letter);
-              }
-            }
-            if (digits) {
-              const SeedEntry se = seed_probe(ix.seed + sidx);
-              const uint32_t cnt = A == NUCLEOTIDE ? seed_cnt(se) : aa_seed_cnt(se);
-              const bool rows = cnt != 0 && cnt != (A == NUCLEOTIDE ? SEED_CNT_SAT : AA_SEED_CNT_SAT) && !(ix.seed_pos && cnt == 1) &&
-                                !(A == NUCLEOTIDE ? seed_has_ctx(se) : aa_seed_is_ctx(se));
-              if (rows) {
-                sp = se.sp;
-                ep = (uint64_t)se.sp + cnt - 1;
-                i = e - k;
-                jumped = true;
-                t_probes++;
-              }
-            }
-          }
+          const bool jumped = k && e >= k && seed_rows_ending_at<A>(ix, ascii, lut, qb, e, k, sp, ep);
+          if (jumped) { i = e - k; t_probes++; }
           if (!jumped) {
             const int idx = lut[ascii[qb + e - 1]];
             sp = ix.prefix_sums[idx];

@@ -462,6 +462,23 @@ void launch_anchors(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint6
   HIP_CHECK(hipGetLastError());
 }
 
+// SMEMs (kernels_smem.hip.h) on a resident grid, with launch_anchors' two passes.  The forward form is the replica's: the
+// suffix-array search where the dense SA at ratio 1 and text8 are resident, else bisection over backward searches.
+bool smem_sa_form(const Replica& r) { return r.dev.dense_sa && r.dev.dense_ratio == 1 && r.dev.text8; }
+void launch_smems(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, uint32_t min_len, uint64_t* d_n_smems, const uint64_t* d_smem_off,
+                  Anchor* d_smems, uint8_t* d_status, hipStream_t s, unsigned long long* d_tally = nullptr) {
+  if (n == 0) return;
+  const uint64_t want = (n + 255) / 256;
+  with_alphabet(r.dev.alphabet, [&](auto A) {
+    with_flags(smem_sa_form(r), d_smem_off != nullptr, [&](auto SA, auto F) {
+      auto kernel = smem_scalar_kernel<decltype(A)::value, SA() ? SMEM_FWD_SA : SMEM_FWD_LF, F() ? 1 : 0>;
+      const dim3 g((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, resident_grid(r, kernel)))), b(256);
+      hipLaunchKernelGGL(kernel, g, b, 0, s, r.dev, d_q, d_off, n, min_len, d_n_smems, d_smem_off, d_smems, d_status, d_tally);
+    });
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 // anchor records -> (start_row, end_row) pairs and located counts (0 for anchors of more than max_hits rows)
 void launch_anchor_ranges(Replica& r, const Anchor* d_anchors, uint64_t n, uint64_t max_hits, uint64_t* d_ranges, uint64_t* d_located, hipStream_t s) {
   if (n == 0) return;

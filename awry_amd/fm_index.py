@@ -519,6 +519,55 @@ class FmIndex:
         _check(self._L.awry_dev_anchors_tally(self._h, slot, d_qbytes, d_qoff, n, int(min_len), int(skip), d_n_anchors, d_anchor_off, d_anchors,
                                               d_status, d_tally, stream))
 
+    # ------------------------------------------------------------------ SMEMs (all super-maximal exact matches)
+    def parallel_smems_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 1):
+        """-> (smem_off uint64[n+1], smems ANCHOR_DTYPE[total]): every super-maximal exact match of every query (include/awry_hip.h
+        states the definition), in descending q_begin; SMEMs of query i are smems[smem_off[i]:smem_off[i+1]]"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        off, an = _u64p(), C.POINTER(_lib.Anchor)()
+        _check(self._L.awry_smem_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), C.byref(off), C.byref(an)))
+        offs = _adopt(self._L, off, n + 1, np.uint64)
+        return offs, _adopt(self._L, an, 24 * int(offs[-1]), np.uint8).view(ANCHOR_DTYPE)
+
+    def parallel_smems(self, queries: Iterable, min_len: int = 1):
+        """-> per query, its SMEMs as (q_begin, q_len, start_row, count) tuples in descending q_begin"""
+        off, an = self.parallel_smems_csr(*pack_queries(queries), min_len)
+        return [[tuple(int(v) for v in a) for a in an[off[i]:off[i + 1]]] for i in range(len(off) - 1)]
+
+    def smems_string(self, query, min_len: int = 1):
+        """SMEMs of one query"""
+        return self.parallel_smems([query], min_len)[0]
+
+    def parallel_locate_smems_csr(self, qbytes: np.ndarray, qoff: np.ndarray, max_hits: int, min_len: int = 1, want_pos: bool = True):
+        """-> (smem_off, smems, hit_off uint64[total+1], global_pos uint64[hits], pos uint64[hits, 2]): hits of record s are
+        [hit_off[s], hit_off[s+1]) in ascending BWT-row order; a record of more than max_hits rows gets none"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        off, an, hoff, hits, gp = _u64p(), C.POINTER(_lib.Anchor)(), _u64p(), C.POINTER(_lib.Pos)(), _u64p()
+        _check(self._L.awry_locate_smems_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(max_hits),
+                                               C.byref(off), C.byref(an), C.byref(hoff), C.byref(hits) if want_pos else None, C.byref(gp)))
+        offs = _adopt(self._L, off, n + 1, np.uint64)
+        tot = int(offs[-1])
+        smems = _adopt(self._L, an, 24 * tot, np.uint8).view(ANCHOR_DTYPE)
+        hit_off = _adopt(self._L, hoff, tot + 1, np.uint64)
+        nh = int(hit_off[-1])
+        g = _adopt(self._L, gp, nh, np.uint64)
+        p = _adopt(self._L, hits, 2 * nh, np.uint64).reshape(-1, 2) if want_pos else np.zeros((0, 2), np.uint64)
+        return offs, smems, hit_off, g, p
+
+    def dev_smems(self, d_qbytes, d_qoff, n, min_len, d_n_smems, d_smem_off=None, d_smems=None, d_status=None, stream=None, slot=0):
+        """device-resident SMEMs: d_smem_off None = the count pass (d_n_smems[n] u64, optional d_status[n]); else the fill pass
+        writing 24-byte records at d_smems[d_smem_off[q] ...); scan d_n_smems with dev_scan_counts in between"""
+        _check(self._L.awry_dev_smems(self._h, slot, d_qbytes, d_qoff, n, int(min_len), d_n_smems, d_smem_off, d_smems, d_status, stream))
+
+    def dev_smems_tally(self, d_qbytes, d_qoff, n, min_len, d_n_smems, d_tally, d_smem_off=None, d_smems=None, d_status=None, stream=None, slot=0):
+        """dev_smems + census: d_tally[4] += (LF steps executed, suffixes compared by the SA search, forward extensions, SMEMs reported)"""
+        _check(self._L.awry_dev_smems_tally(self._h, slot, d_qbytes, d_qoff, n, int(min_len), d_n_smems, d_smem_off, d_smems, d_status, d_tally,
+                                            stream))
+
     def debug_rank_all(self, rows: np.ndarray, slot=0) -> np.ndarray:
         """Occ of every non-sentinel symbol at each row through the kernels' all-symbol rank -> uint64[len(rows), S]
         (column s - 1 = symbol index s; S = 5 nucleotide, 21 amino)"""

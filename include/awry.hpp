@@ -239,6 +239,39 @@ class FmIndex {
     awry_free_buffer(aoff); awry_free_buffer(an); awry_free_buffer(hoff); awry_free_buffer(hits);
     return out;
   }
+  // SMEMs (no counterpart in the reference; the definition is in awry_hip.h): every super-maximal exact match of every query
+  // of at least min_len letters, in descending q_begin -- the same record as an anchor
+  template <class StrRange>
+  std::vector<std::vector<Anchor>> parallel_smems(const StrRange& queries, uint32_t min_len = 1) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* soff = nullptr; awry_anchor_t* sm = nullptr;
+    check(awry_smem_batch(h_, bytes.data(), off.data(), n, min_len, &soff, &sm));
+    std::vector<std::vector<Anchor>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = soff[i]; j < soff[i + 1]; j++) out[i].push_back({sm[j].q_begin, sm[j].q_len, {sm[j].start_row, sm[j].start_row + sm[j].count - 1}});
+    awry_free_buffer(soff); awry_free_buffer(sm);
+    return out;
+  }
+  // the same with every SMEM of at most max_hits (>= 1) occurrences located, in ascending BWT-row order
+  template <class StrRange>
+  std::vector<std::vector<LocatedAnchor>> parallel_locate_smems(const StrRange& queries, uint64_t max_hits, uint32_t min_len = 1) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* soff = nullptr; awry_anchor_t* sm = nullptr; uint64_t* hoff = nullptr; awry_pos_t* hits = nullptr;
+    check(awry_locate_smems_batch(h_, bytes.data(), off.data(), n, min_len, max_hits, &soff, &sm, &hoff, &hits, nullptr));
+    std::vector<std::vector<LocatedAnchor>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = soff[i]; j < soff[i + 1]; j++) {
+        LocatedAnchor la{{sm[j].q_begin, sm[j].q_len, {sm[j].start_row, sm[j].start_row + sm[j].count - 1}}, {}};
+        for (uint64_t h = hoff[j]; h < hoff[j + 1]; h++) la.hits.push_back({hits[h].seq_idx, hits[h].local_pos});
+        out[i].push_back(std::move(la));
+      }
+    awry_free_buffer(soff); awry_free_buffer(sm); awry_free_buffer(hoff); awry_free_buffer(hits);
+    return out;
+  }
   // src/fm_index.rs:559-582, 585-593
   SearchRange update_range_with_symbol(SearchRange r, char symbol) {
     awry_range_t o;

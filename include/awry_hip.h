@@ -252,6 +252,32 @@ int awry_locate_anchors_batch(awry_index_t *idx, const uint8_t *qbytes, const ui
                               int skip, uint64_t max_hits, uint64_t **anchor_off_out, awry_anchor_t **anchors_out,
                               uint64_t **hit_off_out, awry_pos_t **hits_out, uint64_t **global_pos_out);
 
+/* ---- SMEMs: all super-maximal exact matches of a query (no counterpart in the reference) ---------------------
+ * The seeds of an FM-index read mapper: the substrings of the query that occur in the text and cannot be extended by one
+ * letter on either side and still occur.  Queries are mapped to symbol indices and rejected exactly as for
+ * awry_anchor_batch.  With occurs(b, e) = "q[b..e) has at least one occurrence (awry_count > 0)", an SMEM of a query q of L
+ * letters is a pair (b, e), 0 <= b < e <= L, such that
+ *     occurs(b, e)   and   (b == 0 or not occurs(b-1, e))   and   (e == L or not occurs(b, e+1))
+ * Because occurs is about the whole text, this is the same as "a match contained in no other match of the query": the set
+ * does not depend on any order of search.  Begins and ends are both strictly monotone over the set, so a query has at
+ * most L SMEMs.  Each is reported as an awry_anchor_t: q_begin = b, q_len = e - b, and start_row / count = the row interval of
+ * q[b..e), as awry_search_range gives it.  The SMEMs of one query are reported in descending q_begin (so also descending
+ * end); only those with q_len >= min_len are reported.  A query that occurs as a whole yields exactly one record, (0, L); a
+ * letter absent from the text belongs to no SMEM.  (Anchors, above, are left-maximal but mostly not right-maximal, and a
+ * longer match that overlaps two anchors is not among them; the first SMEM of a query equals its first skip = 0 anchor.)
+ * No accelerator, table length, row width or replica count changes any output.  min_len == 0 => AWRY_ERR_ARG; a rejected
+ * query fails the whole batch with AWRY_ERR_INVALID_QUERY and leaves the out-pointers untouched; no replica =>
+ * AWRY_ERR_NO_DEVICE; a query of 2^32 letters or more => AWRY_ERR_ARG.
+ * CSR output, library-allocated (awry_free_buffer): SMEMs of query i are smems[smem_off[i] .. smem_off[i+1]) */
+int awry_smem_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len,
+                    uint64_t **smem_off_out, awry_anchor_t **smems_out);
+/* the same, and every SMEM located, with the semantics of awry_locate_anchors_batch: hits of record s are [hit_off[s],
+ * hit_off[s+1]) in ascending BWT-row order; a record with count > max_hits keeps its place and gets no hits; max_hits == 0
+ * => AWRY_ERR_ARG; hits_out / global_pos_out nullable; the device hit capacity (AWRY_ANCHOR_HIT_CAP) is the anchors' */
+int awry_locate_smems_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len,
+                            uint64_t max_hits, uint64_t **smem_off_out, awry_anchor_t **smems_out, uint64_t **hit_off_out,
+                            awry_pos_t **hits_out, uint64_t **global_pos_out);
+
 /* releases an array one of the calls above (or awry_locate / awry_read_query_file) returned.  Result arrays are pinned
  * host memory recycled through a process-wide pool (the device writes results straight into them); never pass them to
  * free().  AWRY_PINNED_CACHE_GB (default 4) bounds what the pool keeps between calls. */
@@ -392,6 +418,18 @@ int awry_dev_anchors(awry_index_t *idx, int slot, const void *d_qbytes, const vo
 int awry_dev_anchors_tally(awry_index_t *idx, int slot, const void *d_qbytes, const void *d_qoff, uint64_t n, uint32_t min_len,
                            int skip, void *d_n_anchors, const void *d_anchor_off, void *d_anchors, void *d_status,
                            void *d_tally, void *stream);
+/* SMEMs (see awry_smem_batch), device-resident form: the two-call protocol of awry_dev_anchors, without skip -- d_smem_off ==
+ * NULL is the count pass (d_n_smems[n] u64, optional d_status[n]); awry_dev_scan_counts; the fill pass writes the records of
+ * query q at d_smems[d_smem_off[q] ...) and never a slot at or beyond d_smem_off[q+1].  The forward extension runs as a
+ * search of the dense suffix array against the text where the replica keeps both (the verify accelerators), else as a
+ * bisection over backward searches; the records are the same. */
+int awry_dev_smems(awry_index_t *idx, int slot, const void *d_qbytes, const void *d_qoff, uint64_t n, uint32_t min_len,
+                   void *d_n_smems, const void *d_smem_off, void *d_smems, void *d_status, void *stream);
+/* the same with a work census: d_tally[4] (u64, caller-zeroed) += {LF steps executed (the ones that emptied the range
+ * included), suffixes compared by the suffix-array search, forward extensions performed, SMEMs reported}; one atomic per
+ * query and counter */
+int awry_dev_smems_tally(awry_index_t *idx, int slot, const void *d_qbytes, const void *d_qoff, uint64_t n, uint32_t min_len,
+                         void *d_n_smems, const void *d_smem_off, void *d_smems, void *d_status, void *d_tally, void *stream);
 /* test hook of the all-symbol rank primitive: d_occ[i * S + s - 1] = Occ(s, d_rows[i]) for every non-sentinel symbol index s
  * (S = 5 nucleotide, 21 amino; inclusive of the row, as awry_update_range uses it); rows >= bwt_len give zeros */
 int awry_debug_rank_all(awry_index_t *idx, int slot, const void *d_rows, uint64_t n, void *d_occ, void *stream);

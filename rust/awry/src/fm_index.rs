@@ -545,6 +545,39 @@ impl FmIndex {
         Ok(out)
     }
 
+    /// SMEMs (no counterpart in the reference; the definition is in include/awry_hip.h): per query, every super-maximal exact
+    /// match -- a substring that occurs and cannot be extended by one letter on either side and still occur -- of at least
+    /// `min_len` (>= 1) letters, in descending begin, as `(q_begin, q_len, SearchRange)`: the seeds of a read mapper.
+    pub fn parallel_smems<'a>(
+        &self,
+        queries: impl ParallelIterator<Item = &'a str>,
+        min_len: u32,
+    ) -> Result<Vec<Vec<(usize, usize, SearchRange)>>, AwryError> {
+        let csr = to_csr(queries);
+        let n = csr.offsets.len() - 1;
+        let mut smem_off: *mut u64 = std::ptr::null_mut();
+        let mut smems: *mut RawAnchor = std::ptr::null_mut();
+        check(unsafe { sys::awry_smem_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, min_len, &mut smem_off, &mut smems) })?;
+        let out = unsafe {
+            let off = std::slice::from_raw_parts(smem_off, n + 1);
+            let total = off[n] as usize;
+            let flat: &[RawAnchor] = if total == 0 { &[] } else { std::slice::from_raw_parts(smems, total) };
+            (0..n)
+                .map(|i| {
+                    flat[off[i] as usize..off[i + 1] as usize]
+                        .iter()
+                        .map(|a| (a.q_begin as usize, a.q_len as usize, SearchRange { start_ptr: a.start_row, end_ptr: a.start_row + a.count - 1 }))
+                        .collect::<Vec<_>>()
+                })
+                .collect::<Vec<_>>()
+        };
+        unsafe {
+            sys::awry_free_buffer(smem_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(smems as *mut std::os::raw::c_void);
+        }
+        Ok(out)
+    }
+
     /// Locations of a batch as flat arrays: `(hit_offsets[n + 1], global text positions)`; the hits of query i are
     /// `positions[hit_offsets[i]..hit_offsets[i + 1]]`, `(SA sample + steps) % bwt_len` of src/fm_index.rs:534.
     /// Passes `hits_out = NULL`: 8 bytes per hit cross PCIe instead of 24.
