@@ -112,6 +112,10 @@ def load_library():
     sig("awry_locate_smems_batch", i32, vp, vp, u64p, u64, u32, u64, C.POINTER(u64p), app, C.POINTER(u64p), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p))
     sig("awry_dev_smems", i32, vp, i32, vp, vp, u64, u32, vp, vp, vp, vp, vp)
     sig("awry_dev_smems_tally", i32, vp, i32, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp)
+    sig("awry_locate_edit_batch", i32, vp, vp, u64p, u64, i32, u64, C.POINTER(u64p), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(u8p),
+        C.POINTER(u8p))
+    sig("awry_dev_edit_windows", i32, vp, i32, vp, vp, vp, vp, vp, u64, i32, vp, vp, vp, vp, vp)
+    sig("awry_dev_edit_windows_tally", i32, vp, i32, vp, vp, vp, vp, vp, u64, i32, vp, vp, vp, vp, vp, vp)
     sig("awry_debug_rank_all", i32, vp, i32, vp, u64, vp, vp)
     sig("awry_count", i32, vp, vp, u64, u64p)
     sig("awry_search_range", i32, vp, vp, u64, C.POINTER(Range))

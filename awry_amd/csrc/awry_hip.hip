@@ -9,6 +9,7 @@
 #include "mismatch_host.h"
 #include "pattern_host.h"
 #include "anchor_host.h"
+#include "edit_host.h"
 #include "prewarm.h"
 
 namespace {
@@ -406,6 +407,17 @@ int awry_locate_smems_batch(awry_index_t* idx, const uint8_t* qbytes, const uint
     require_smem_args(min_len);
     require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
     anchor_batch(idx, qbytes, qoff, n, smem_finder(min_len), max_hits, smem_off_out, smems_out, hit_off_out, hits_out, global_pos_out);
+  });
+}
+
+int awry_locate_edit_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_edits, uint64_t max_candidates,
+                           uint64_t** hit_off_out, awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** edits_out, uint8_t** status_out) {
+  return guarded([&] {
+    require(idx && qoff && hit_off_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_edits(max_edits);
+    require(max_candidates != 0, "max_candidates must be at least 1 (a cap is mandatory: the pieces of a read from a repeat family occur everywhere)");
+    locate_edit_batch(idx, qbytes, qoff, n, max_edits, max_candidates, hit_off_out, hits_out, global_pos_out, edits_out, status_out);
   });
 }
 
@@ -850,6 +862,26 @@ int awry_dev_smems_tally(awry_index_t* idx, int slot, const void* d_qbytes, cons
     require(n == 0 || (d_qbytes && d_qoff && (d_smem_off ? d_smems != nullptr : d_n_smems != nullptr)), "null device pointer");
     launch_smems(r, (const uint8_t*)d_qbytes, (const uint64_t*)d_qoff, n, min_len, (uint64_t*)d_n_smems, (const uint64_t*)d_smem_off, (Anchor*)d_smems,
                  (uint8_t*)d_status, (hipStream_t)stream, (unsigned long long*)d_tally);
+  });
+}
+
+int awry_dev_edit_windows(awry_index_t* idx, int slot, const uint8_t* d_qbytes, const uint64_t* d_qoff, const uint32_t* d_win_query,
+                          const uint64_t* d_win_first, const uint32_t* d_win_count, uint64_t m, int max_edits, uint64_t* d_n_hits, const uint64_t* d_hit_off,
+                          uint64_t* d_gpos, uint8_t* d_edits, void* stream) {
+  return awry_dev_edit_windows_tally(idx, slot, d_qbytes, d_qoff, d_win_query, d_win_first, d_win_count, m, max_edits, d_n_hits, d_hit_off, d_gpos, d_edits,
+                                     nullptr, stream);
+}
+
+int awry_dev_edit_windows_tally(awry_index_t* idx, int slot, const uint8_t* d_qbytes, const uint64_t* d_qoff, const uint32_t* d_win_query,
+                                const uint64_t* d_win_first, const uint32_t* d_win_count, uint64_t m, int max_edits, uint64_t* d_n_hits,
+                                const uint64_t* d_hit_off, uint64_t* d_gpos, uint8_t* d_edits, uint64_t* d_tally, void* stream) {
+  return guarded([&] {
+    require_edits(max_edits);
+    Replica& r = replica(idx, slot);
+    require(m == 0 || (d_qbytes && d_qoff && d_win_query && d_win_first && d_win_count && (d_hit_off ? d_gpos && d_edits : d_n_hits != nullptr)),
+            "null device pointer");
+    launch_edit_windows(r, edit_text(r), d_qbytes, d_qoff, d_win_query, d_win_first, d_win_count, m, max_edits, EDIT_MAX_W, 0, d_n_hits, d_hit_off, d_gpos,
+                        d_edits, (hipStream_t)stream, (unsigned long long*)d_tally);
   });
 }
 

@@ -1,0 +1,197 @@
+// edit_host.h -- the chunk driver of locate within k edits: pigeonhole pieces, their located hits as diagonals, windows, the scan
+// A part of awry_hip.hip (one translation unit): included there, in order, and not on its own.
+#pragma once
+
+namespace {
+
+// ---- locate within k edits (edit_kernels.hip.h) ---------------------------------------------------------------------
+
+static_assert(Q_CANDIDATE_CAP == AWRY_Q_CANDIDATE_CAP && EDIT_MAX_K == AWRY_MAX_EDITS && EDIT_MAX_LEN == AWRY_EDIT_MAX_LEN,
+              "the kernels' limits are the header's");
+
+void require_edits(int k) {
+  if (k < 0 || k > EDIT_MAX_K) throw ArgError("max_edits must be in 0..8 (AWRY_MAX_EDITS)");
+}
+
+// Candidates (located piece hits) a chunk may hold on the device; a chunk with more, and more than one query, is split in
+// halves and each half redone in query order.  Read per call: AWRY_EDIT_CANDIDATE_CAP (tests shrink it).
+uint64_t edit_candidate_cap() {
+  const char* e = getenv("AWRY_EDIT_CANDIDATE_CAP");
+  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
+  return v ? std::min<uint64_t>(v, 1ull << 31) : (1ull << 26);
+}
+
+// The text as symbol indices for the scan: the replica's text8 while the verify accelerators keep it, else a copy of the
+// replica's own, recovered from the index on first use (one LF chain per file SA sample) and kept with the replica.  Nothing
+// else of the replica changes.
+const uint8_t* edit_text(Replica& r) {
+  if (r.wide || r.dev.bwt_len >= (1ull << 32)) throw ArgError("locate within k edits needs an index with 32-bit rows (bwt_len < 2^32)");
+  if (r.dev.text8) return r.dev.text8;
+  std::lock_guard<std::mutex> lock(r.edit_mu);
+  if (r.edit_text8.p) return r.edit_text8.p;
+  DevBuf<uint8_t> t;
+  try {
+    t.alloc(r.dev.bwt_len + 16);
+  } catch (const HipError&) {
+    (void)hipGetLastError();
+    throw std::bad_alloc();  // AWRY_ERR_OOM
+  }
+  HIP_CHECK(hipMemsetAsync(t.p, 0, r.dev.bwt_len + 16, r.stream));
+  const uint64_t nsamples = (r.dev.bwt_len + r.dev.sa_ratio - 1) / r.dev.sa_ratio;
+  with_alphabet(r.dev.alphabet, [&](auto A) {
+    hipLaunchKernelGGL(text8_chains_kernel<A()>, dim3(grid_for(r, nsamples, 256, 64)), dim3(256), 0, r.stream, r.dev, nsamples, t.p);
+  });
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(r.stream));
+  r.edit_text8 = std::move(t);
+  return r.edit_text8.p;
+}
+
+struct EditHits {  // one shard's result, in query order
+  std::vector<uint64_t> counts;  // hits per query
+  std::vector<uint8_t> status;   // per query: Q_OK or Q_CANDIDATE_CAP
+  std::vector<uint64_t> gpos;
+  std::vector<awry_pos_t> pos;
+  std::vector<uint8_t> edits;
+  uint64_t nhits = 0;
+};
+
+template <class K, class... Args>
+void edit_launch(Replica& r, hipStream_t s, uint64_t items, K kernel, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid_for(r, items, 256)), dim3(256), 0, s, args...);
+  HIP_CHECK(hipGetLastError());
+}
+
+// One chunk: (1) count the pieces -- the piece CSR is a finer offsets array over the chunk's own bytes -- (2) apply the cap,
+// (3) scan and locate the pieces' text positions, (4) diagonals, (5) segmented sort per query, (6) runs of diagonals ->
+// windows, (7) scan count pass, (8) scan and fill pass.  false: the chunk holds more candidates than the capacity and more than
+// one query -- nothing appended.
+bool edit_chunk(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, uint64_t max_candidates, bool want_pos,
+                bool want_gpos, bool want_edits, EditHits& out) {
+  const hipStream_t s = r.stream;
+  const uint64_t n = c.hi - c.lo, w = (uint64_t)k + 1, np = n * w, n_text = r.dev.bwt_len - 1;
+  ChunkBuffers cb;
+  upload_chunk(r, cb, qbytes, qoff, c);
+  std::vector<uint64_t> h_poff(np + 1);
+  uint64_t Lmax = 1;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint64_t L = cb.h_off[i + 1] - cb.h_off[i];
+    if (L == 0) raise_bad_query(c.lo + i, Q_EMPTY);
+    if (L > (uint64_t)EDIT_MAX_LEN) throw QueryError("query " + std::to_string(c.lo + i) + ": longer than 256 letters (AWRY_EDIT_MAX_LEN)");
+    if (L <= (uint64_t)k) throw QueryError("query " + std::to_string(c.lo + i) + ": not longer than max_edits");
+    for (uint64_t t = 0; t < w; t++) h_poff[i * w + t] = cb.h_off[i] + t * L / w;
+    Lmax = std::max(Lmax, L);
+  }
+  h_poff[np] = cb.h_off[n];
+  const int W = (int)((Lmax + 63) / 64);
+  DevBuf<uint64_t> poff(np + 1), pcounts(np), pranges(2 * np), phoff(np + 1), pscratch(scan_tiles(np) + 1), cand_off(n + 1);
+  DevBuf<uint8_t> pstatus(np);
+  HIP_CHECK(hipMemcpyAsync(poff.p, h_poff.data(), (np + 1) * 8, hipMemcpyHostToDevice, s));
+  launch_count_ascii(r, cb.q.p, poff.p, np, pcounts.p, pranges.p, pstatus.p, s, true);
+  edit_launch(r, s, n, edit_cap_kernel, pcounts.p, pstatus.p, n, k, max_candidates, cb.status.p);
+  launch_scan(r, pcounts.p, np, phoff.p, pscratch.p, s);
+  uint64_t total = 0;
+  HIP_CHECK(hipMemcpyAsync(&total, phoff.p + np, 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  for (uint64_t i = 0; i < n; i++)
+    if (cb.h_status[i] != Q_OK && cb.h_status[i] != Q_CANDIDATE_CAP) raise_bad_query(c.lo + i, cb.h_status[i]);
+  if (total > edit_candidate_cap() && n > 1) return false;
+  require(total < (1ull << 32), "one query has 2^32 or more candidates: lower max_candidates");
+  std::vector<uint64_t> h_qhoff(n + 1, 0);
+  uint64_t m = 0, nhits = 0;
+  const size_t at_h = (size_t)out.nhits;
+  if (total) {
+    DevBuf<uint64_t> cand_gpos(total), key(total), key2(total), heads(total), head_off(total + 1), hscratch(scan_tiles(total) + 1);
+    launch_locate(r, pranges.p, 2, phoff.p, np, total, cand_gpos.p, nullptr, s);
+    edit_launch(r, s, total, edit_diagonals_kernel, cand_gpos.p, phoff.p, np, total, cb.off.p, k, key.p);
+    edit_launch(r, s, n + 1, edit_every_nth_kernel, phoff.p, n + 1, w, cand_off.p);
+    unsigned end_bit = 1;
+    while (end_bit < 64 && ((r.dev.bwt_len + 2 * (uint64_t)EDIT_MAX_LEN) >> end_bit)) end_bit++;
+    size_t tmp_bytes = 0;
+    HIP_CHECK(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, key.p, key2.p, (unsigned)total, (unsigned)n, cand_off.p, cand_off.p + 1, 0, end_bit, s));
+    DevBuf<uint8_t> tmp(std::max<size_t>(tmp_bytes, 8));
+    HIP_CHECK(rocprim::segmented_radix_sort_keys(tmp.p, tmp_bytes, key.p, key2.p, (unsigned)total, (unsigned)n, cand_off.p, cand_off.p + 1, 0, end_bit, s));
+    edit_launch(r, s, total, edit_run_heads_kernel, key2.p, cand_off.p, n, total, k, heads.p);
+    launch_scan(r, heads.p, total, head_off.p, hscratch.p, s);
+    HIP_CHECK(hipMemcpyAsync(&m, head_off.p + total, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    DevBuf<uint32_t> win_query(m), win_count(m);
+    DevBuf<uint64_t> run_lo(m), run_hi(m), win_first(m), win_hits(m), win_hit_off(m + 1), wscratch(scan_tiles(m) + 1), q_hit_off(n + 1);
+    edit_launch(r, s, total, edit_run_ends_kernel, key2.p, cand_off.p, n, total, k, head_off.p, win_query.p, run_lo.p, run_hi.p);
+    edit_launch(r, s, m, edit_windows_kernel, win_query.p, run_lo.p, run_hi.p, m, cb.off.p, k, n_text, win_first.p, win_count.p);
+    launch_edit_windows(r, text8, cb.q.p, cb.off.p, win_query.p, win_first.p, win_count.p, m, k, W, n, win_hits.p, nullptr, nullptr, nullptr, s);
+    launch_scan(r, win_hits.p, m, win_hit_off.p, wscratch.p, s);
+    HIP_CHECK(hipMemcpyAsync(&nhits, win_hit_off.p + m, 8, hipMemcpyDeviceToHost, s));
+    edit_launch(r, s, n + 1, edit_query_hit_off_kernel, cand_off.p, head_off.p, win_hit_off.p, n, q_hit_off.p);
+    HIP_CHECK(hipMemcpyAsync(h_qhoff.data(), q_hit_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (nhits) {
+      DevBuf<uint64_t> d_gpos(nhits), d_pos(want_pos ? 2 * nhits : 0);
+      DevBuf<uint8_t> d_edits(nhits);
+      launch_edit_windows(r, text8, cb.q.p, cb.off.p, win_query.p, win_first.p, win_count.p, m, k, W, n, nullptr, win_hit_off.p, d_gpos.p, d_edits.p, s);
+      if (want_pos) edit_launch(r, s, nhits, edit_localise_kernel, r.dev, nhits, d_gpos.p, d_pos.p);
+      if (want_gpos) { out.gpos.resize(at_h + nhits); HIP_CHECK(hipMemcpyAsync(out.gpos.data() + at_h, d_gpos.p, nhits * 8, hipMemcpyDeviceToHost, s)); }
+      if (want_pos) { out.pos.resize(at_h + nhits); HIP_CHECK(hipMemcpyAsync(out.pos.data() + at_h, d_pos.p, nhits * 16, hipMemcpyDeviceToHost, s)); }
+      if (want_edits) { out.edits.resize(at_h + nhits); HIP_CHECK(hipMemcpyAsync(out.edits.data() + at_h, d_edits.p, nhits, hipMemcpyDeviceToHost, s)); }
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+  }
+  require(h_qhoff[n] == nhits, "internal: the queries' hit offsets do not cover the windows'");
+  for (uint64_t i = 0; i < n; i++) out.counts.push_back(h_qhoff[i + 1] - h_qhoff[i]);
+  out.status.insert(out.status.end(), cb.h_status.begin(), cb.h_status.begin() + n);
+  out.nhits += nhits;
+  return true;
+}
+
+void edit_range(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, uint64_t max_candidates, bool want_pos,
+                bool want_gpos, bool want_edits, EditHits& out) {
+  if (c.hi <= c.lo) return;
+  if (edit_chunk(r, text8, qbytes, qoff, c, k, max_candidates, want_pos, want_gpos, want_edits, out)) return;
+  const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order
+  edit_range(r, text8, qbytes, qoff, Shard{c.lo, mid}, k, max_candidates, want_pos, want_gpos, want_edits, out);
+  edit_range(r, text8, qbytes, qoff, Shard{mid, c.hi}, k, max_candidates, want_pos, want_gpos, want_edits, out);
+}
+
+// awry_locate_edit_batch: shards over the replicas, results stitched in query order.  The out-pointers are written only when
+// everything has succeeded.
+void locate_edit_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int k, uint64_t max_candidates, uint64_t** hit_off_out,
+                       awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** edits_out, uint8_t** status_out) {
+  std::vector<EditHits> res(std::max<size_t>(1, idx->reps.size()));
+  for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
+    HIP_CHECK(hipSetDevice(r.device));
+    const uint8_t* text8 = edit_text(r);
+    for (Shard c : chunk_queries(qoff, sh.lo, sh.hi))
+      edit_range(r, text8, qbytes, qoff, c, k, max_candidates, hits_out != nullptr, global_pos_out != nullptr, edits_out != nullptr, res[g]);
+  });
+  MBuf<uint64_t> off, gp;
+  MBuf<awry_pos_t> hits;
+  MBuf<uint8_t> ed, st;
+  off.grow(n + 1);
+  off.p[0] = 0;
+  if (status_out) st.grow(std::max<uint64_t>(1, n));
+  uint64_t q = 0, total = 0;
+  for (auto& x : res) {
+    if (status_out && !x.status.empty()) memcpy(st.p + q, x.status.data(), x.status.size());
+    for (uint64_t cnt : x.counts) { total += cnt; off.p[++q] = total; }
+  }
+  require(q == n, "internal: shard results do not cover the batch");
+  if (hits_out) hits.grow(std::max<uint64_t>(1, total));
+  if (global_pos_out) gp.grow(std::max<uint64_t>(1, total));
+  if (edits_out) ed.grow(std::max<uint64_t>(1, total));
+  uint64_t at = 0;
+  for (auto& x : res) {
+    if (hits_out && x.nhits) pool_memcpy(hits.p + at, x.pos.data(), x.nhits * sizeof(awry_pos_t));
+    if (global_pos_out && x.nhits) pool_memcpy(gp.p + at, x.gpos.data(), x.nhits * 8);
+    if (edits_out && x.nhits) pool_memcpy(ed.p + at, x.edits.data(), x.nhits);
+    at += x.nhits;
+  }
+  require(at == total, "internal: shard results do not cover the hits");
+  *hit_off_out = off.release();
+  if (hits_out) *hits_out = hits.release();
+  if (global_pos_out) *global_pos_out = gp.release();
+  if (edits_out) *edits_out = ed.release();
+  if (status_out) *status_out = st.release();
+}
+
+}  // namespace

@@ -32,13 +32,19 @@
 //   SMEMs, any query      SMEM_SCALAR_KERNEL<A, FWD, FILL>   all super-maximal exact matches, one query per lane: forward extension by a search of
 //                                                            the dense SA against text8 (FWD = SA) or by bisection over backward searches (FWD = LF),
 //                                                            then the anchor walk; count pass, scan, fill pass, ANCHOR_RANGES_KERNEL [kernels_smem]
+//   locate within k edits EDIT_SCAN_KERNEL<A, W, FILL>       Myers / Hyyro bit-vector scan of text windows, one window per lane, W = 1..4 words of
+//                                                            64 query letters: count pass, scan, fill pass [edit_kernels]
+//                         + EDIT_MASKS_KERNEL<A>             pattern masks of the queries, into the stream's workspace [edit_kernels]
+//                         + edit_cap / diagonals / run_heads / run_ends / windows / query_hit_off / localise kernels: located pieces ->
+//                                                            sorted diagonals -> windows, and the hits' records [edit_kernels]
 //   count, wide rows      count_nt2_wide_kernel, count_nt2_wide_probe_kernel   64-bit rows [kernels_wide]
 //   locate                LOCATE_TILE_KERNEL<A>              hit -> row, sampled / verified hits finished [this file]
 //                         + LOCATE_WALK_NT_LANE_KERNEL       LF walks of the rest, one hit per lane, whole block per step [this file]
 //                         + LOCALISE_WALKED_KERNEL           record / offset of the walked hits [this file]
 //                         LOCATE_WALK_KERNEL<AMINO>          generic walk, the amino indexes' second pass [this file]
 //   accelerators          seed_level1/extend<Entry>, seed_finalize, seed64_finalize (+aa_seed_*), seed_rows_to_positions_kernel [kernels_seed];
-//                         densify_sa_kernel, nblock_sa_kernel, text4_scatter_kernel, text8_scatter_kernel [this file]
+//                         densify_sa_kernel, nblock_sa_kernel, text4_scatter_kernel, text8_scatter_kernel [this file];
+//                         text8_chains_kernel (the text without the dense SA, for the edit scan) [edit_kernels]
 //   glue                  pack_nt2_tile_kernel<R> [kernels_pack]; scan_*_kernel, stream_copy_kernel, phase_marker_kernel,
 //                         narrow_counts_kernel, status_first_bad_kernel [kernels_scan]; ref_kmer_table_kernel, scalar_ops_kernel [kernels_count]
 //   device helpers        scalar rank / step / backstep, ByteStream, text_equals_query [kernels_rank]; wave / block scans [kernels_scan];
@@ -547,3 +553,5 @@ __global__ __launch_bounds__(256) void locate_walk_nt_lane_kernel(DevIndex ix, u
 }
 
 }  // namespace awry
+
+#include "edit_kernels.hip.h"      // localise, backstep_scalar, symbol_at, ByteStream

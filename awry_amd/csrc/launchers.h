@@ -479,6 +479,47 @@ void launch_smems(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_
   HIP_CHECK(hipGetLastError());
 }
 
+// The edit scan (edit_kernels.hip.h) over m windows, one per lane.  d_hit_off == nullptr: the count pass (d_n_hits[m]); else the
+// fill pass (d_gpos / d_edits at [d_hit_off[w], d_hit_off[w + 1])).  W = words of 64 query letters per column, for the launch:
+// the chunk's longest query decides it (a shorter query leaves its upper words idle); nqueries != 0: the windows' queries are
+// 0 .. nqueries - 1 and the pattern masks are built per query; nqueries == 0 (the device entry point, which knows neither the
+// number of queries nor their lengths on the host): per window, at W = 4.  The masks live in the stream's scratch and are
+// rebuilt by every launch, in front of the scan: two host threads on one stream never read each other's.
+void launch_edit_windows(Replica& r, const uint8_t* text8, const uint8_t* d_q, const uint64_t* d_off, const uint32_t* d_win_query,
+                         const uint64_t* d_win_first, const uint32_t* d_win_count, uint64_t m, int k, int W, uint64_t nqueries, uint64_t* d_n_hits,
+                         const uint64_t* d_hit_off, uint64_t* d_gpos, uint8_t* d_edits, hipStream_t s, unsigned long long* d_tally = nullptr) {
+  if (m == 0) return;
+  require(W >= 1 && W <= EDIT_MAX_W, "internal: words per column out of range");
+  const ScratchLock scratch_lock(r, s);
+  Replica::SurvScratch* sc = surv_scratch(r, s);
+  const uint64_t nslots = nqueries ? nqueries : m;
+  const size_t need = (size_t)nslots * (size_t)edit_symbols(r.dev.alphabet) * (size_t)W;
+  if (sc->edit_masks.n < need) {
+    HIP_CHECK(hipStreamSynchronize(s));
+    sc->edit_masks.alloc(need + need / 4);
+  }
+  const bool fill = d_hit_off != nullptr;
+  with_alphabet(r.dev.alphabet, [&](auto A) {
+    constexpr int AL = decltype(A)::value;
+    hipLaunchKernelGGL(edit_masks_kernel<AL>, dim3(grid_for(r, need, 256)), dim3(256), 0, s, d_q, d_off, nqueries ? nullptr : d_win_query, nslots, W,
+                       sc->edit_masks.p);
+    const dim3 g(grid_for(r, m, 256)), b(256);
+    auto scan = [&](auto WW, auto F) {
+      hipLaunchKernelGGL((edit_scan_kernel<AL, decltype(WW)::value, decltype(F)::value>), g, b, 0, s, text8, r.dev.bwt_len - 1, d_off, d_win_query,
+                         d_win_first, d_win_count, m, k, sc->edit_masks.p, nqueries ? 0 : 1, d_n_hits, d_hit_off, d_gpos, d_edits, d_tally);
+    };
+    with_flags(fill, [&](auto F) {
+      switch (W) {
+        case 1: scan(std::integral_constant<int, 1>{}, F); break;
+        case 2: scan(std::integral_constant<int, 2>{}, F); break;
+        case 3: scan(std::integral_constant<int, 3>{}, F); break;
+        default: scan(std::integral_constant<int, 4>{}, F); break;
+      }
+    });
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 // anchor records -> (start_row, end_row) pairs and located counts (0 for anchors of more than max_hits rows)
 void launch_anchor_ranges(Replica& r, const Anchor* d_anchors, uint64_t n, uint64_t max_hits, uint64_t* d_ranges, uint64_t* d_located, hipStream_t s) {
   if (n == 0) return;

@@ -107,6 +107,8 @@ struct Replica {
   DevBuf<uint32_t> dense_sa;                  // SA[j * dense_ratio] as u32 (device-only accelerator for locate)
   DevBuf<uint32_t> sa_nblock;                 // SA of the rows whose suffix starts with N (kept while locate has to walk)
   DevBuf<uint64_t> lcx_key, lcx_rowpos, lcx_inner;  // left-context index (layout.h, DevIndex::lcx_key); kept with position seeds
+  DevBuf<uint8_t> edit_text8;                 // the edit scan's own copy of the text while text8 is not resident (built on first use, edit_host.h)
+  std::mutex edit_mu;
   uint32_t dense_ratio = 0;                   // 0 = use the file's bit-packed samples
   bool verify_kmers = false;                  // also use seed-and-verify in the k-mer (L <= 32) kernel
   // survivor lists of the two-phase count schedule, one per stream (launches on one stream are ordered, so reuse is safe)
@@ -126,6 +128,8 @@ struct Replica {
     DevBuf<unsigned long long> u_bad;
     // count_pattern_kernel: the DFS frames below the two a lane keeps in registers, [level][field][grid lane]
     DevBuf<uint64_t> pat_stack;
+    // edit_scan_kernel: the pattern masks edit_masks_kernel writes in front of it, per query or per window
+    DevBuf<uint64_t> edit_masks;
     // work-queue heads of the chunk / locate kernels launched on this stream: launches on one stream are ordered, so a
     // head is free again by the time the ring comes back to it, however many launches other streams have in flight
     DevBuf<unsigned long long> counters;
@@ -158,7 +162,7 @@ struct Replica {
       if (ev1) (void)hipEventDestroy(ev1);
       blocks.reset(); sa_words.reset(); seq_starts.reset(); seed.reset(); seed64.reset(); rungs.clear(); dense_sa.reset(); text4.reset();
       scratch.clear();
-      sa_nblock.reset(); text8.reset();
+      sa_nblock.reset(); text8.reset(); edit_text8.reset();
       lcx_key.reset(); lcx_rowpos.reset(); lcx_inner.reset();
     }
   }

@@ -28,6 +28,7 @@ class AwryError(RuntimeError):
 
 ERR_IO, ERR_FORMAT, ERR_INVALID_QUERY, ERR_HIP, ERR_OOM, ERR_ARG, ERR_NO_DEVICE = -1, -2, -3, -4, -5, -6, -7
 MAX_MISMATCHES = 2  # AWRY_MAX_MISMATCHES
+MAX_EDITS, EDIT_MAX_LEN, Q_CANDIDATE_CAP = 8, 256, 7  # AWRY_MAX_EDITS, AWRY_EDIT_MAX_LEN, AWRY_Q_CANDIDATE_CAP
 
 
 @dataclass
@@ -567,6 +568,51 @@ class FmIndex:
         """dev_smems + census: d_tally[4] += (LF steps executed, suffixes compared by the SA search, forward extensions, SMEMs reported)"""
         _check(self._L.awry_dev_smems_tally(self._h, slot, d_qbytes, d_qoff, n, int(min_len), d_n_smems, d_smem_off, d_smems, d_status, d_tally,
                                             stream))
+
+    # ------------------------------------------------------------------ locate within k edits (substitutions, insertions, deletions)
+    def parallel_locate_edit_csr(self, qbytes: np.ndarray, qoff: np.ndarray, k: int, max_candidates: int, want_pos: bool = True):
+        """-> (hit_off uint64[n+1], global_pos uint64[total], pos uint64[total, 2], edits uint8[total], status uint8[n]): the
+        locally best starts of every query within k edits (include/awry_hip.h states the definition), ascending text position;
+        status[i] == Q_CANDIDATE_CAP marks a query abandoned because its k + 1 pieces occur more than max_candidates times in all
+        (it has no hits); want_pos=False leaves pos empty"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        off, hits, gp, ed, st = _u64p(), C.POINTER(_lib.Pos)(), _u64p(), C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint8)()
+        _check(self._L.awry_locate_edit_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(k), int(max_candidates), C.byref(off),
+                                              C.byref(hits) if want_pos else None, C.byref(gp), C.byref(ed), C.byref(st)))
+        offs = _adopt(self._L, off, n + 1, np.uint64)
+        tot = int(offs[-1])
+        g = _adopt(self._L, gp, tot, np.uint64)
+        p = _adopt(self._L, hits, 2 * tot, np.uint64).reshape(-1, 2) if want_pos else np.zeros((0, 2), np.uint64)
+        return offs, g, p, _adopt(self._L, ed, tot, np.uint8), _adopt(self._L, st, n, np.uint8)
+
+    def parallel_locate_edit(self, queries: Iterable, k: int, max_candidates: int):
+        """-> per query, [(LocalizedSequencePosition, distance)] in ascending text position (empty for an abandoned query)"""
+        off, _, p, d, _ = self.parallel_locate_edit_csr(*pack_queries(queries), k, max_candidates)
+        return [[(LocalizedSequencePosition(int(a), int(b)), int(e)) for (a, b), e in zip(p[off[i]:off[i + 1]], d[off[i]:off[i + 1]])]
+                for i in range(len(off) - 1)]
+
+    def locate_string_edit(self, query, k: int, max_candidates: int):
+        """-> [(LocalizedSequencePosition, distance)] of one query"""
+        return self.parallel_locate_edit([query], k, max_candidates)[0]
+
+    def count_string_edit(self, query, k: int, max_candidates: int) -> int:
+        """hits of one query within k edits (0 for an abandoned query)"""
+        return int(self.parallel_locate_edit_csr(*pack_queries([query]), k, max_candidates, want_pos=False)[0][-1])
+
+    def dev_edit_windows(self, d_qbytes, d_qoff, d_win_query, d_win_first, d_win_count, m, k, d_n_hits, d_hit_off=None, d_gpos=None, d_edits=None,
+                         stream=None, slot=0):
+        """device-resident verify of candidate windows: d_hit_off None = the count pass (d_n_hits[m] u64); else the fill pass writing
+        window w's hits at d_gpos (u64) / d_edits (u8) [d_hit_off[w], d_hit_off[w+1]); scan d_n_hits with dev_scan_counts in between"""
+        _check(self._L.awry_dev_edit_windows(self._h, slot, d_qbytes, d_qoff, d_win_query, d_win_first, d_win_count, m, int(k), d_n_hits, d_hit_off,
+                                             d_gpos, d_edits, stream))
+
+    def dev_edit_windows_tally(self, d_qbytes, d_qoff, d_win_query, d_win_first, d_win_count, m, k, d_n_hits, d_tally, d_hit_off=None, d_gpos=None,
+                               d_edits=None, stream=None, slot=0):
+        """dev_edit_windows + census: d_tally[2] += (text columns scanned, windows scanned)"""
+        _check(self._L.awry_dev_edit_windows_tally(self._h, slot, d_qbytes, d_qoff, d_win_query, d_win_first, d_win_count, m, int(k), d_n_hits,
+                                                   d_hit_off, d_gpos, d_edits, d_tally, stream))
 
     def debug_rank_all(self, rows: np.ndarray, slot=0) -> np.ndarray:
         """Occ of every non-sentinel symbol at each row through the kernels' all-symbol rank -> uint64[len(rows), S]

@@ -170,6 +170,29 @@ class FmIndex {
     awry_free_buffer(hoff); awry_free_buffer(hits); awry_free_buffer(mm);
     return out;
   }
+  // locate within k edits (no counterpart in the reference; the definition is in awry_hip.h): per query, the starts whose best
+  // alignment has at most k substitutions, insertions and deletions and is not beaten by a neighbouring start, in ascending
+  // text position.  A query whose k + 1 pieces occur more than max_candidates times in all is abandoned: no hits, and
+  // (*status)[i] == AWRY_Q_CANDIDATE_CAP where the caller asks for the status bytes.
+  struct EditHit {
+    LocalizedSequencePosition position;
+    uint64_t global_position;
+    uint8_t edits;
+  };
+  template <class StrRange>
+  std::vector<std::vector<EditHit>> parallel_locate_edit(const StrRange& queries, int k, uint64_t max_candidates, std::vector<uint8_t>* status = nullptr) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* hoff = nullptr; awry_pos_t* hits = nullptr; uint64_t* gp = nullptr; uint8_t* ed = nullptr; uint8_t* st = nullptr;
+    check(awry_locate_edit_batch(h_, bytes.data(), off.data(), n, k, max_candidates, &hoff, &hits, &gp, &ed, &st));
+    std::vector<std::vector<EditHit>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = hoff[i]; j < hoff[i + 1]; j++) out[i].push_back({{hits[j].seq_idx, hits[j].local_pos}, gp[j], ed[j]});
+    if (status) status->assign(st, st + n);
+    awry_free_buffer(hoff); awry_free_buffer(hits); awry_free_buffer(gp); awry_free_buffer(ed); awry_free_buffer(st);
+    return out;
+  }
   // class patterns (no counterpart in the reference; the definition and the limits are in awry_hip.h): IUPAC / residue-class
   // letters with up to k mismatches.  counts[i * (k + 1) + d] = occurrences of pattern i at exactly d mismatches
   template <class StrRange>

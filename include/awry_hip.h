@@ -204,7 +204,8 @@ enum { AWRY_MAX_CLASS_POSITIONS = 16, AWRY_PATTERN_MAX_FRAMES = 18, AWRY_PATTERN
 /* status byte of the device-resident query calls (d_status) */
 enum {
   AWRY_Q_OK = 0, AWRY_Q_EMPTY = 1, AWRY_Q_SENTINEL = 2, AWRY_Q_NON_ASCII = 3,
-  AWRY_Q_NOT_CLASS_LETTER = 4, AWRY_Q_CLASS_POSITIONS = 5, AWRY_Q_EXPANSION_CAP = 6 /* patterns only */
+  AWRY_Q_NOT_CLASS_LETTER = 4, AWRY_Q_CLASS_POSITIONS = 5, AWRY_Q_EXPANSION_CAP = 6 /* patterns only */,
+  AWRY_Q_CANDIDATE_CAP = 7 /* awry_locate_edit_batch only: the query was abandoned, not rejected */
 };
 /* class mask of an ASCII byte as a pattern letter: bit s = symbol index s belongs to the class, 0 = not a class letter (or
  * an unknown alphabet id).  The one table of host and device; needs no GPU. */
@@ -277,6 +278,37 @@ int awry_smem_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qo
 int awry_locate_smems_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len,
                             uint64_t max_hits, uint64_t **smem_off_out, awry_anchor_t **smems_out, uint64_t **hit_off_out,
                             awry_pos_t **hits_out, uint64_t **global_pos_out);
+
+/* ---- locate within k edits: pigeonhole seeds and a bit-vector verify (no counterpart in the reference) --------
+ * Where a read matches the text with at most k substitutions, insertions and deletions, and at what distance.
+ * Text model: queries are mapped to symbol indices and rejected exactly as on the exact path -- letters case-insensitive,
+ * U = T, any other byte N / X, query N equals text N; empty queries, '$' / '#' and bytes >= 0x80 are rejected.
+ * Let T be the text without its final '$', n = bwt_len - 1 symbols; q a query of L symbols, 1 <= L <= AWRY_EDIT_MAX_LEN;
+ * k = max_edits, 0 <= k <= AWRY_MAX_EDITS and k < L.
+ *     D(s) = min over e in [s, n] of  edit_distance(q, T[s..e))      for 0 <= s < n      (unit costs; D(-1) = D(n) = +inf)
+ *     s is a hit with distance D(s)  iff  D(s) <= k  and  D(s-1) >= D(s)  and  D(s+1) >= D(s)
+ * A hit is a START position whose best alignment is within k edits and is not beaten by either neighbouring start: a local
+ * minimum; plateaus are reported whole.  So at k = 0 the hits of a query are exactly the positions awry_locate_batch returns
+ * for it; an exact occurrence at s under k = 3 is reported once, not seven times; a record join or a text N costs one edit
+ * unless the query has N there (the rule of the mismatch path).  Hits of one query are in ascending text position.
+ * Piece rule (part of the contract: the cap depends on it): piece t of a query is q[floor(t L / (k+1)) .. floor((t+1) L /
+ * (k+1))), t = 0..k; c(q) is the sum of the exact occurrence counts of its k + 1 pieces.  If c(q) > max_candidates the query
+ * is abandoned: status byte AWRY_Q_CANDIDATE_CAP, no hits.  An abandoned query does not fail the batch (reads from a
+ * 10^5-copy family are ordinary input).  max_candidates == 0 => AWRY_ERR_ARG: a cap is mandatory, as max_hits is for anchors.
+ * Malformed queries fail the whole batch with AWRY_ERR_INVALID_QUERY and leave the out-pointers untouched: the reasons of the
+ * exact path, and L > AWRY_EDIT_MAX_LEN, and L <= k.  max_edits outside 0..AWRY_MAX_EDITS => AWRY_ERR_ARG; no replica =>
+ * AWRY_ERR_NO_DEVICE; an index with bwt_len >= 2^32 or a wide-row replica => AWRY_ERR_ARG; no HBM for the text copy (below)
+ * => AWRY_ERR_OOM.  No accelerator, table length, replica count or chunk capacity changes any output; c(q) is a sum of exact
+ * counts, so it does not either.  The scan reads the text as symbol indices: the verify accelerators' copy while it is
+ * resident, else a copy of its own (1 B per symbol) that the replica recovers from the index on first use and keeps until
+ * the replicas are replaced; nothing else of the replica changes.  A chunk of queries with more candidates than the device
+ * capacity (2^26; env AWRY_EDIT_CANDIDATE_CAP, read per call) and more than one query is split and redone.
+ * CSR output, library-allocated (awry_free_buffer): hits of query i are [hit_off[i], hit_off[i+1]) of hits (record, offset),
+ * global_pos (text position), edits (distance); status[n] is AWRY_Q_OK or AWRY_Q_CANDIDATE_CAP.  All but hit_off_out nullable. */
+enum { AWRY_MAX_EDITS = 8, AWRY_EDIT_MAX_LEN = 256 };
+int awry_locate_edit_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, int max_edits,
+                           uint64_t max_candidates, uint64_t **hit_off_out, awry_pos_t **hits_out, uint64_t **global_pos_out,
+                           uint8_t **edits_out, uint8_t **status_out);
 
 /* releases an array one of the calls above (or awry_locate / awry_read_query_file) returned.  Result arrays are pinned
  * host memory recycled through a process-wide pool (the device writes results straight into them); never pass them to
@@ -430,6 +462,26 @@ int awry_dev_smems(awry_index_t *idx, int slot, const void *d_qbytes, const void
  * query and counter */
 int awry_dev_smems_tally(awry_index_t *idx, int slot, const void *d_qbytes, const void *d_qoff, uint64_t n, uint32_t min_len,
                          void *d_n_smems, const void *d_smem_off, void *d_smems, void *d_status, void *d_tally, void *stream);
+/* The device primitive under awry_locate_edit_batch, for a caller who seeds with SMEMs and verifies candidate loci of their
+ * own.  Window w asks for the hits of query d_win_query[w] (u32 index into the CSR d_qbytes / d_qoff) among the starts
+ * [d_win_first[w], d_win_first[w] + d_win_count[w]), cut to [0, n); the kernel reads the text it needs around them itself
+ * (T[max(first - 1, 0) .. min(last + L + k + 3, n)), last = the last owned start).  Two calls with the caller's scan between
+ * them: d_hit_off == NULL is the count pass -> d_n_hits[m] (u64); awry_dev_scan_counts turns it into d_hit_off[m+1]; the
+ * fill pass writes window w's hits in ascending position at d_gpos (u64) / d_edits (u8) [d_hit_off[w], d_hit_off[w+1]).
+ * Windows of one query must own disjoint starts; keep them adjacent and ascending and the hits of a query are ascending.
+ * Values are exact whatever the window cut.  A window whose query is empty, longer than AWRY_EDIT_MAX_LEN or not longer than
+ * max_edits has no hits; bytes are mapped as on the exact path ('$' / '#' and bytes >= 0x80 equal no text symbol).  No
+ * synchronisation except where the pattern-mask workspace (owned by the replica, per stream) grows, or the text copy is built,
+ * on first use; the masks are per window here, at 4 words per column. */
+int awry_dev_edit_windows(awry_index_t *idx, int slot, const uint8_t *d_qbytes, const uint64_t *d_qoff, const uint32_t *d_win_query,
+                          const uint64_t *d_win_first, const uint32_t *d_win_count, uint64_t m, int max_edits, uint64_t *d_n_hits,
+                          const uint64_t *d_hit_off, uint64_t *d_gpos, uint8_t *d_edits, void *stream);
+/* the same with a work census: d_tally[2] (u64, caller-zeroed) += {text columns scanned, windows scanned}; a window without
+ * owned starts or without a query the scan takes counts as neither; per-lane atomics at the end of the launch only */
+int awry_dev_edit_windows_tally(awry_index_t *idx, int slot, const uint8_t *d_qbytes, const uint64_t *d_qoff,
+                                const uint32_t *d_win_query, const uint64_t *d_win_first, const uint32_t *d_win_count, uint64_t m,
+                                int max_edits, uint64_t *d_n_hits, const uint64_t *d_hit_off, uint64_t *d_gpos, uint8_t *d_edits,
+                                uint64_t *d_tally, void *stream);
 /* test hook of the all-symbol rank primitive: d_occ[i * S + s - 1] = Occ(s, d_rows[i]) for every non-sentinel symbol index s
  * (S = 5 nucleotide, 21 amino; inclusive of the row, as awry_update_range uses it); rows >= bwt_len give zeros */
 int awry_debug_rank_all(awry_index_t *idx, int slot, const void *d_rows, uint64_t n, void *d_occ, void *stream);

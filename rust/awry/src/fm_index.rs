@@ -578,6 +578,50 @@ impl FmIndex {
         Ok(out)
     }
 
+    /// Locate within k edits (no counterpart in the reference; the definition is in include/awry_hip.h): per query, `(position,
+    /// distance)` of every start whose best alignment has at most `max_edits` (0..=8) substitutions, insertions and deletions
+    /// and is not beaten by a neighbouring start, in ascending text position; and per query whether it was abandoned because
+    /// its `max_edits + 1` pieces occur more than `max_candidates` (>= 1) times in all.
+    pub fn parallel_locate_edit<'a>(
+        &self,
+        queries: impl ParallelIterator<Item = &'a str>,
+        max_edits: u32,
+        max_candidates: u64,
+    ) -> Result<(Vec<Vec<(LocalizedSequencePosition, u8)>>, Vec<bool>), AwryError> {
+        let csr = to_csr(queries);
+        let n = csr.offsets.len() - 1;
+        let mut hit_off: *mut u64 = std::ptr::null_mut();
+        let mut hits: *mut sys::awry_pos_t = std::ptr::null_mut();
+        let mut ed: *mut u8 = std::ptr::null_mut();
+        let mut st: *mut u8 = std::ptr::null_mut();
+        check(unsafe {
+            sys::awry_locate_edit_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, max_edits as i32, max_candidates, &mut hit_off,
+                                        &mut hits, std::ptr::null_mut(), &mut ed, &mut st)
+        })?;
+        let out = unsafe {
+            let off = std::slice::from_raw_parts(hit_off, n + 1);
+            let total = off[n] as usize;
+            let flat: &[sys::awry_pos_t] = if total == 0 { &[] } else { std::slice::from_raw_parts(hits, total) };
+            let dist: &[u8] = if total == 0 { &[] } else { std::slice::from_raw_parts(ed, total) };
+            let status: &[u8] = if n == 0 { &[] } else { std::slice::from_raw_parts(st, n) };
+            let per = (0..n)
+                .map(|i| {
+                    (off[i] as usize..off[i + 1] as usize)
+                        .map(|j| (LocalizedSequencePosition::new(flat[j].seq_idx as usize, flat[j].local_pos as usize), dist[j]))
+                        .collect::<Vec<_>>()
+                })
+                .collect::<Vec<_>>();
+            (per, status.iter().map(|&s| s == 7).collect::<Vec<_>>())  // AWRY_Q_CANDIDATE_CAP
+        };
+        unsafe {
+            sys::awry_free_buffer(hit_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(hits as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(ed as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(st as *mut std::os::raw::c_void);
+        }
+        Ok(out)
+    }
+
     /// Locations of a batch as flat arrays: `(hit_offsets[n + 1], global text positions)`; the hits of query i are
     /// `positions[hit_offsets[i]..hit_offsets[i + 1]]`, `(SA sample + steps) % bwt_len` of src/fm_index.rs:534.
     /// Passes `hits_out = NULL`: 8 bytes per hit cross PCIe instead of 24.
