@@ -13,6 +13,7 @@ from .fm_index import (  # noqa: F401
     LocalizedSequencePosition,
     SearchRange,
     SymbolAlphabet,
+    cigar_string,
     pattern_class,
 )
 from ._lib import lib_path, load_library  # noqa: F401

@@ -116,6 +116,10 @@ def load_library():
         C.POINTER(u8p))
     sig("awry_dev_edit_windows", i32, vp, i32, vp, vp, vp, vp, vp, u64, i32, vp, vp, vp, vp, vp)
     sig("awry_dev_edit_windows_tally", i32, vp, i32, vp, vp, vp, vp, vp, u64, i32, vp, vp, vp, vp, vp, vp)
+    sig("awry_align_edit_batch", i32, vp, vp, u64p, u64, i32, u64, C.POINTER(u64p), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(u8p),
+        C.POINTER(u8p), C.POINTER(C.POINTER(u32)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)))
+    sig("awry_dev_edit_align", i32, vp, i32, vp, vp, vp, vp, vp, u64, i32, vp, vp, vp, vp)
+    sig("awry_dev_edit_align_tally", i32, vp, i32, vp, vp, vp, vp, vp, u64, i32, vp, vp, vp, vp, vp)
     sig("awry_debug_rank_all", i32, vp, i32, vp, u64, vp, vp)
     sig("awry_count", i32, vp, vp, u64, u64p)
     sig("awry_search_range", i32, vp, vp, u64, C.POINTER(Range))

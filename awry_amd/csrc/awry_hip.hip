@@ -421,6 +421,20 @@ int awry_locate_edit_batch(awry_index_t* idx, const uint8_t* qbytes, const uint6
   });
 }
 
+int awry_align_edit_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_edits, uint64_t max_candidates,
+                          uint64_t** hit_off_out, awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** edits_out, uint8_t** status_out,
+                          uint32_t** text_len_out, uint64_t** cigar_off_out, uint32_t** cigar_out) {
+  return guarded([&] {
+    require(idx && qoff && hit_off_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_edits(max_edits);
+    require(max_candidates != 0, "max_candidates must be at least 1 (a cap is mandatory: the pieces of a read from a repeat family occur everywhere)");
+    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
+    locate_edit_batch(idx, qbytes, qoff, n, max_edits, max_candidates, hit_off_out, hits_out, global_pos_out, edits_out, status_out, text_len_out,
+                      cigar_off_out, cigar_out);
+  });
+}
+
 namespace {
 // one query through the replica's pinned mailbox; want_rows: the range must be a row interval (no text shortcut)
 // (the caller holds r.mailbox_mu)
@@ -882,6 +896,25 @@ int awry_dev_edit_windows_tally(awry_index_t* idx, int slot, const uint8_t* d_qb
             "null device pointer");
     launch_edit_windows(r, edit_text(r), d_qbytes, d_qoff, d_win_query, d_win_first, d_win_count, m, max_edits, EDIT_MAX_W, 0, d_n_hits, d_hit_off, d_gpos,
                         d_edits, (hipStream_t)stream, (unsigned long long*)d_tally);
+  });
+}
+
+int awry_dev_edit_align(awry_index_t* idx, int slot, const uint8_t* d_qbytes, const uint64_t* d_qoff, const uint32_t* d_hit_query,
+                        const uint64_t* d_hit_gpos, const uint8_t* d_hit_edits, uint64_t m, int max_edits, uint32_t* d_text_len, uint8_t* d_n_ops,
+                        uint32_t* d_ops, void* stream) {
+  return awry_dev_edit_align_tally(idx, slot, d_qbytes, d_qoff, d_hit_query, d_hit_gpos, d_hit_edits, m, max_edits, d_text_len, d_n_ops, d_ops, nullptr,
+                                   stream);
+}
+
+int awry_dev_edit_align_tally(awry_index_t* idx, int slot, const uint8_t* d_qbytes, const uint64_t* d_qoff, const uint32_t* d_hit_query,
+                              const uint64_t* d_hit_gpos, const uint8_t* d_hit_edits, uint64_t m, int max_edits, uint32_t* d_text_len, uint8_t* d_n_ops,
+                              uint32_t* d_ops, uint64_t* d_tally, void* stream) {
+  return guarded([&] {
+    require_edits(max_edits);
+    Replica& r = replica(idx, slot);
+    require(m == 0 || (d_qbytes && d_qoff && d_hit_query && d_hit_gpos && d_hit_edits && d_text_len && d_n_ops && d_ops), "null device pointer");
+    launch_edit_align(r, edit_text(r), d_qbytes, d_qoff, d_hit_query, d_hit_gpos, d_hit_edits, m, max_edits, EDIT_MAX_LEN, d_text_len, d_n_ops, d_ops,
+                      (hipStream_t)stream, (unsigned long long*)d_tally);
   });
 }
 

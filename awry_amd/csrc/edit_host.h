@@ -1,4 +1,5 @@
-// edit_host.h -- the chunk driver of locate within k edits: pigeonhole pieces, their located hits as diagonals, windows, the scan
+// edit_host.h -- the chunk driver of locate within k edits: pigeonhole pieces, their located hits as diagonals, windows, the scan,
+// and on request the alignment pass over the hits (awry_align_edit_batch)
 // A part of awry_hip.hip (one translation unit): included there, in order, and not on its own.
 #pragma once
 
@@ -6,7 +7,8 @@ namespace {
 
 // ---- locate within k edits (edit_kernels.hip.h) ---------------------------------------------------------------------
 
-static_assert(Q_CANDIDATE_CAP == AWRY_Q_CANDIDATE_CAP && EDIT_MAX_K == AWRY_MAX_EDITS && EDIT_MAX_LEN == AWRY_EDIT_MAX_LEN,
+static_assert(Q_CANDIDATE_CAP == AWRY_Q_CANDIDATE_CAP && EDIT_MAX_K == AWRY_MAX_EDITS && EDIT_MAX_LEN == AWRY_EDIT_MAX_LEN &&
+                  ALIGN_MAX_OPS == AWRY_ALIGN_MAX_OPS,
               "the kernels' limits are the header's");
 
 void require_edits(int k) {
@@ -19,6 +21,15 @@ uint64_t edit_candidate_cap() {
   const char* e = getenv("AWRY_EDIT_CANDIDATE_CAP");
   const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
   return v ? std::min<uint64_t>(v, 1ull << 31) : (1ull << 26);
+}
+
+// Hits the alignment pass takes per launch: its fixed-stride staging (text_len, n_ops, ops, and the scan of the run counts: 89 B
+// per hit) is bounded by the sub-batch whatever the hit count -- 89 MiB at the default 2^20.  Read per call:
+// AWRY_ALIGN_SUB_BATCH (tests shrink it).
+uint64_t align_sub_batch() {
+  const char* e = getenv("AWRY_ALIGN_SUB_BATCH");
+  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
+  return v ? std::min<uint64_t>(v, 1ull << 24) : (1ull << 20);
 }
 
 // The text as symbol indices for the scan: the replica's text8 while the verify accelerators keep it, else a copy of the
@@ -53,7 +64,13 @@ struct EditHits {  // one shard's result, in query order
   std::vector<uint64_t> gpos;
   std::vector<awry_pos_t> pos;
   std::vector<uint8_t> edits;
+  std::vector<uint32_t> text_len, cigar;  // the alignment pass: per hit the text span and n_ops runs, the runs back to back
+  std::vector<uint8_t> n_ops;
   uint64_t nhits = 0;
+};
+
+struct EditWants {  // what the caller asked for: the chunk driver copies back nothing else
+  bool pos, gpos, edits, align;
 };
 
 template <class K, class... Args>
@@ -62,12 +79,48 @@ void edit_launch(Replica& r, hipStream_t s, uint64_t items, K kernel, Args... ar
   HIP_CHECK(hipGetLastError());
 }
 
+// The alignment pass over the nhits hits of a chunk, which lie on the device in window order: their queries out of the windows',
+// then per sub-batch the kernel at a fixed stride, a scan of the run counts and the compaction to CSR, appended to `out`.
+void align_chunk_hits(Replica& r, const uint8_t* text8, const ChunkBuffers& cb, const uint32_t* win_query, const uint64_t* win_hit_off, uint64_t m,
+                      const uint64_t* d_gpos, const uint8_t* d_edits, uint64_t nhits, int k, uint32_t Lmax, EditHits& out) {
+  const hipStream_t s = r.stream;
+  const uint64_t sub = std::min(align_sub_batch(), nhits);
+  DevBuf<uint32_t> hit_query(nhits), text_len(sub), ops(sub * ALIGN_MAX_OPS);
+  DevBuf<uint8_t> n_ops(sub);
+  DevBuf<uint64_t> counts(sub), cigar_off(sub + 1), scratch(scan_tiles(sub) + 1);
+  edit_launch(r, s, nhits, align_hit_query_kernel, win_hit_off, win_query, m, nhits, hit_query.p);
+  const size_t at_h = out.text_len.size();
+  out.text_len.resize(at_h + nhits);
+  out.n_ops.resize(at_h + nhits);
+  for (uint64_t at = 0; at < nhits; at += sub) {
+    const uint64_t c = std::min(sub, nhits - at);
+    launch_edit_align(r, text8, cb.q.p, cb.off.p, hit_query.p + at, d_gpos + at, d_edits + at, c, k, Lmax, text_len.p, n_ops.p, ops.p, s);
+    edit_launch(r, s, c, align_counts_kernel, n_ops.p, c, counts.p);
+    launch_scan(r, counts.p, c, cigar_off.p, scratch.p, s);
+    uint64_t runs = 0;
+    HIP_CHECK(hipMemcpyAsync(&runs, cigar_off.p + c, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(out.text_len.data() + at_h + at, text_len.p, c * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(out.n_ops.data() + at_h + at, n_ops.p, c, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    require(runs <= c * (uint64_t)ALIGN_MAX_OPS, "internal: more CIGAR runs than the bound allows");
+    if (runs) {
+      DevBuf<uint32_t> cigar(runs);
+      edit_launch(r, s, c, align_compact_kernel, ops.p, n_ops.p, cigar_off.p, c, cigar.p);
+      const size_t at_c = out.cigar.size();
+      out.cigar.resize(at_c + runs);
+      HIP_CHECK(hipMemcpyAsync(out.cigar.data() + at_c, cigar.p, runs * 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+  }
+}
+
 // One chunk: (1) count the pieces -- the piece CSR is a finer offsets array over the chunk's own bytes -- (2) apply the cap,
 // (3) scan and locate the pieces' text positions, (4) diagonals, (5) segmented sort per query, (6) runs of diagonals ->
-// windows, (7) scan count pass, (8) scan and fill pass.  false: the chunk holds more candidates than the capacity and more than
-// one query -- nothing appended.
-bool edit_chunk(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, uint64_t max_candidates, bool want_pos,
-                bool want_gpos, bool want_edits, EditHits& out) {
+// windows, (7) scan count pass, (8) scan and fill pass, (9) on request the alignment pass over the hits.  false: the chunk holds
+// more candidates than the capacity and more than one query -- nothing appended.
+bool edit_chunk(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, uint64_t max_candidates, EditWants want,
+                EditHits& out) {
+  const bool want_pos = want.pos, want_gpos = want.gpos, want_edits = want.edits;
   const hipStream_t s = r.stream;
   const uint64_t n = c.hi - c.lo, w = (uint64_t)k + 1, np = n * w, n_text = r.dev.bwt_len - 1;
   ChunkBuffers cb;
@@ -135,6 +188,7 @@ bool edit_chunk(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const u
       if (want_pos) { out.pos.resize(at_h + nhits); HIP_CHECK(hipMemcpyAsync(out.pos.data() + at_h, d_pos.p, nhits * 16, hipMemcpyDeviceToHost, s)); }
       if (want_edits) { out.edits.resize(at_h + nhits); HIP_CHECK(hipMemcpyAsync(out.edits.data() + at_h, d_edits.p, nhits, hipMemcpyDeviceToHost, s)); }
       HIP_CHECK(hipStreamSynchronize(s));
+      if (want.align) align_chunk_hits(r, text8, cb, win_query.p, win_hit_off.p, m, d_gpos.p, d_edits.p, nhits, k, (uint32_t)Lmax, out);
     }
   }
   require(h_qhoff[n] == nhits, "internal: the queries' hit offsets do not cover the windows'");
@@ -144,29 +198,34 @@ bool edit_chunk(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const u
   return true;
 }
 
-void edit_range(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, uint64_t max_candidates, bool want_pos,
-                bool want_gpos, bool want_edits, EditHits& out) {
+void edit_range(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, uint64_t max_candidates, EditWants want,
+                EditHits& out) {
   if (c.hi <= c.lo) return;
-  if (edit_chunk(r, text8, qbytes, qoff, c, k, max_candidates, want_pos, want_gpos, want_edits, out)) return;
+  if (edit_chunk(r, text8, qbytes, qoff, c, k, max_candidates, want, out)) return;
   const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order
-  edit_range(r, text8, qbytes, qoff, Shard{c.lo, mid}, k, max_candidates, want_pos, want_gpos, want_edits, out);
-  edit_range(r, text8, qbytes, qoff, Shard{mid, c.hi}, k, max_candidates, want_pos, want_gpos, want_edits, out);
+  edit_range(r, text8, qbytes, qoff, Shard{c.lo, mid}, k, max_candidates, want, out);
+  edit_range(r, text8, qbytes, qoff, Shard{mid, c.hi}, k, max_candidates, want, out);
 }
 
-// awry_locate_edit_batch: shards over the replicas, results stitched in query order.  The out-pointers are written only when
-// everything has succeeded.
+// awry_locate_edit_batch and awry_align_edit_batch (which passes the last three: text_len_out alone, the two cigar arrays together,
+// or all): shards over the replicas, results stitched in query order.  The out-pointers are written only when everything has
+// succeeded.
 void locate_edit_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int k, uint64_t max_candidates, uint64_t** hit_off_out,
-                       awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** edits_out, uint8_t** status_out) {
+                       awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** edits_out, uint8_t** status_out, uint32_t** text_len_out = nullptr,
+                       uint64_t** cigar_off_out = nullptr, uint32_t** cigar_out = nullptr) {
+  const EditWants want{hits_out != nullptr, global_pos_out != nullptr, edits_out != nullptr, text_len_out != nullptr || cigar_out != nullptr};
   std::vector<EditHits> res(std::max<size_t>(1, idx->reps.size()));
   for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
     HIP_CHECK(hipSetDevice(r.device));
     const uint8_t* text8 = edit_text(r);
     for (Shard c : chunk_queries(qoff, sh.lo, sh.hi))
-      edit_range(r, text8, qbytes, qoff, c, k, max_candidates, hits_out != nullptr, global_pos_out != nullptr, edits_out != nullptr, res[g]);
+      edit_range(r, text8, qbytes, qoff, c, k, max_candidates, want, res[g]);
   });
   MBuf<uint64_t> off, gp;
   MBuf<awry_pos_t> hits;
   MBuf<uint8_t> ed, st;
+  MBuf<uint32_t> tl, cg;
+  MBuf<uint64_t> coff;
   off.grow(n + 1);
   off.p[0] = 0;
   if (status_out) st.grow(std::max<uint64_t>(1, n));
@@ -179,19 +238,35 @@ void locate_edit_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* q
   if (hits_out) hits.grow(std::max<uint64_t>(1, total));
   if (global_pos_out) gp.grow(std::max<uint64_t>(1, total));
   if (edits_out) ed.grow(std::max<uint64_t>(1, total));
-  uint64_t at = 0;
+  if (text_len_out) tl.grow(std::max<uint64_t>(1, total));
+  uint64_t runs = 0;
+  for (auto& x : res) runs += x.cigar.size();
+  if (cigar_out) { coff.grow(total + 1); cg.grow(std::max<uint64_t>(1, runs)); }
+  uint64_t at = 0, at_c = 0;
   for (auto& x : res) {
     if (hits_out && x.nhits) pool_memcpy(hits.p + at, x.pos.data(), x.nhits * sizeof(awry_pos_t));
     if (global_pos_out && x.nhits) pool_memcpy(gp.p + at, x.gpos.data(), x.nhits * 8);
     if (edits_out && x.nhits) pool_memcpy(ed.p + at, x.edits.data(), x.nhits);
+    if (want.align) require(x.text_len.size() == x.nhits && x.n_ops.size() == x.nhits, "internal: the alignment pass does not cover the hits");
+    if (text_len_out && x.nhits) pool_memcpy(tl.p + at, x.text_len.data(), x.nhits * 4);
+    if (cigar_out) {
+      if (!x.cigar.empty()) pool_memcpy(cg.p + at_c, x.cigar.data(), x.cigar.size() * 4);
+      for (uint64_t h = 0; h < x.nhits; h++) { coff.p[at + h] = at_c; at_c += x.n_ops[h]; }
+    }
     at += x.nhits;
   }
   require(at == total, "internal: shard results do not cover the hits");
+  if (cigar_out) {
+    require(at_c == runs, "internal: the run counts do not cover the CIGAR runs");
+    coff.p[total] = runs;
+  }
   *hit_off_out = off.release();
   if (hits_out) *hits_out = hits.release();
   if (global_pos_out) *global_pos_out = gp.release();
   if (edits_out) *edits_out = ed.release();
   if (status_out) *status_out = st.release();
+  if (text_len_out) *text_len_out = tl.release();
+  if (cigar_out) { *cigar_off_out = coff.release(); *cigar_out = cg.release(); }
 }
 
 }  // namespace

@@ -37,6 +37,10 @@
 //                         + EDIT_MASKS_KERNEL<A>             pattern masks of the queries, into the stream's workspace [edit_kernels]
 //                         + edit_cap / diagonals / run_heads / run_ends / windows / query_hit_off / localise kernels: located pieces ->
 //                                                            sorted diagonals -> windows, and the hits' records [edit_kernels]
+//   align edit hits       EDIT_ALIGN_KERNEL<A, H>          banded table (half-width H = 2, 4, 6, 8 in registers) with a traceback through per-row
+//                                                            direction words in a lane-interleaved workspace, one hit per lane: text span and
+//                                                            CIGAR runs at a fixed stride [kernels_align]
+//                         + align_hit_query / counts / compact kernels: the hits' queries, and fixed stride -> CSR [kernels_align]
 //   count, wide rows      count_nt2_wide_kernel, count_nt2_wide_probe_kernel   64-bit rows [kernels_wide]
 //   locate                LOCATE_TILE_KERNEL<A>              hit -> row, sampled / verified hits finished [this file]
 //                         + LOCATE_WALK_NT_LANE_KERNEL       LF walks of the rest, one hit per lane, whole block per step [this file]
@@ -555,3 +559,4 @@ __global__ __launch_bounds__(256) void locate_walk_nt_lane_kernel(DevIndex ix, u
 }  // namespace awry
 
 #include "edit_kernels.hip.h"      // localise, backstep_scalar, symbol_at, ByteStream
+#include "kernels_align.hip.h"     // edit_symbols, edit_owner, ByteStream

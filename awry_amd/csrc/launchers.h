@@ -520,6 +520,41 @@ void launch_edit_windows(Replica& r, const uint8_t* text8, const uint8_t* d_q, c
   HIP_CHECK(hipGetLastError());
 }
 
+// The alignment pass (kernels_align.hip.h) over m hits, one per lane: text_len[m], n_ops[m] and ops[m * ALIGN_MAX_OPS].  The band
+// half-width of the launch is the smallest of 2, 4, 6, 8 that holds k; max_rows = the longest query the launch takes (the chunk's
+// longest, or EDIT_MAX_LEN for the device entry point).  The direction words live in the stream's scratch, one per row and grid
+// lane: the grid is cut so that they stay within ALIGN_TRACE_BYTES (at 256 rows and 8-byte words 256 blocks: one per CU).
+constexpr size_t ALIGN_TRACE_BYTES = 128u << 20;
+void launch_edit_align(Replica& r, const uint8_t* text8, const uint8_t* d_q, const uint64_t* d_off, const uint32_t* d_hit_query,
+                       const uint64_t* d_hit_gpos, const uint8_t* d_hit_edits, uint64_t m, int k, uint32_t max_rows, uint32_t* d_text_len, uint8_t* d_n_ops,
+                       uint32_t* d_ops, hipStream_t s, unsigned long long* d_tally = nullptr) {
+  if (m == 0) return;
+  require(max_rows >= 1 && max_rows <= (uint32_t)EDIT_MAX_LEN && k >= 0 && k <= EDIT_MAX_K, "internal: alignment launch out of range");
+  const ScratchLock scratch_lock(r, s);
+  Replica::SurvScratch* sc = surv_scratch(r, s);
+  with_alphabet(r.dev.alphabet, [&](auto A) {
+    constexpr int AL = decltype(A)::value;
+    auto align = [&](auto HH) {
+      constexpr int H = decltype(HH)::value;
+      using TW = typename AlignTrace<H>::word;
+      const uint64_t fit = ALIGN_TRACE_BYTES / ((size_t)max_rows * sizeof(TW) * 256);
+      const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)grid_for(r, m, 256), fit));
+      const size_t need = ((size_t)blocks * 256 * max_rows * sizeof(TW) + 7) / 8;
+      if (sc->align_trace.n < need) {
+        HIP_CHECK(hipStreamSynchronize(s));
+        sc->align_trace.alloc(need);
+      }
+      hipLaunchKernelGGL((edit_align_kernel<AL, H>), dim3((unsigned)blocks), dim3(256), 0, s, text8, r.dev.bwt_len - 1, d_q, d_off, d_hit_query, d_hit_gpos,
+                         d_hit_edits, m, k, max_rows, reinterpret_cast<TW*>(sc->align_trace.p), d_text_len, d_n_ops, d_ops, d_tally);
+    };
+    if (k <= 2) align(std::integral_constant<int, 2>{});
+    else if (k <= 4) align(std::integral_constant<int, 4>{});
+    else if (k <= 6) align(std::integral_constant<int, 6>{});
+    else align(std::integral_constant<int, 8>{});
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 // anchor records -> (start_row, end_row) pairs and located counts (0 for anchors of more than max_hits rows)
 void launch_anchor_ranges(Replica& r, const Anchor* d_anchors, uint64_t n, uint64_t max_hits, uint64_t* d_ranges, uint64_t* d_located, hipStream_t s) {
   if (n == 0) return;

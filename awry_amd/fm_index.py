@@ -29,6 +29,13 @@ class AwryError(RuntimeError):
 ERR_IO, ERR_FORMAT, ERR_INVALID_QUERY, ERR_HIP, ERR_OOM, ERR_ARG, ERR_NO_DEVICE = -1, -2, -3, -4, -5, -6, -7
 MAX_MISMATCHES = 2  # AWRY_MAX_MISMATCHES
 MAX_EDITS, EDIT_MAX_LEN, Q_CANDIDATE_CAP = 8, 256, 7  # AWRY_MAX_EDITS, AWRY_EDIT_MAX_LEN, AWRY_Q_CANDIDATE_CAP
+ALIGN_MAX_OPS = 17  # AWRY_ALIGN_MAX_OPS
+CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}  # the BAM op codes the alignment pass produces
+
+
+def cigar_string(ops) -> str:
+    """runs (len << 4 | BAM op) -> the CIGAR string, "57=1X43=" """
+    return "".join("%d%s" % (int(v) >> 4, CIGAR_OPS[int(v) & 15]) for v in ops)
 
 
 @dataclass
@@ -613,6 +620,50 @@ class FmIndex:
         """dev_edit_windows + census: d_tally[2] += (text columns scanned, windows scanned)"""
         _check(self._L.awry_dev_edit_windows_tally(self._h, slot, d_qbytes, d_qoff, d_win_query, d_win_first, d_win_count, m, int(k), d_n_hits,
                                                    d_hit_off, d_gpos, d_edits, d_tally, stream))
+
+    # ------------------------------------------------------------------ align the hits within k edits: text span and CIGAR per hit
+    def parallel_align_edit_csr(self, qbytes: np.ndarray, qoff: np.ndarray, k: int, max_candidates: int, want_pos: bool = True):
+        """-> (hit_off, global_pos, pos, edits, status) exactly as parallel_locate_edit_csr, then text_len uint32[total], cigar_off
+        uint64[total+1], cigar uint32[runs]: hit h matches T[global_pos[h] .. + text_len[h]) by the runs cigar[cigar_off[h] ..
+        cigar_off[h+1]), each len << 4 | BAM op (include/awry_hip.h states the canonical script)"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        off, hits, gp, ed, st = _u64p(), C.POINTER(_lib.Pos)(), _u64p(), C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint8)()
+        tl, coff, cg = C.POINTER(C.c_uint32)(), _u64p(), C.POINTER(C.c_uint32)()
+        _check(self._L.awry_align_edit_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(k), int(max_candidates), C.byref(off),
+                                             C.byref(hits) if want_pos else None, C.byref(gp), C.byref(ed), C.byref(st), C.byref(tl), C.byref(coff),
+                                             C.byref(cg)))
+        offs = _adopt(self._L, off, n + 1, np.uint64)
+        tot = int(offs[-1])
+        g = _adopt(self._L, gp, tot, np.uint64)
+        p = _adopt(self._L, hits, 2 * tot, np.uint64).reshape(-1, 2) if want_pos else np.zeros((0, 2), np.uint64)
+        d, status = _adopt(self._L, ed, tot, np.uint8), _adopt(self._L, st, n, np.uint8)
+        coffs = _adopt(self._L, coff, tot + 1, np.uint64)
+        return offs, g, p, d, status, _adopt(self._L, tl, tot, np.uint32), coffs, _adopt(self._L, cg, int(coffs[-1]), np.uint32)
+
+    def parallel_align_edit(self, queries: Iterable, k: int, max_candidates: int):
+        """-> per query, [(LocalizedSequencePosition, distance, text_len, "57=1X43=")] in ascending text position (empty for an
+        abandoned query)"""
+        off, _, p, d, _, tl, coff, cg = self.parallel_align_edit_csr(*pack_queries(queries), k, max_candidates)
+        return [[(LocalizedSequencePosition(int(p[h, 0]), int(p[h, 1])), int(d[h]), int(tl[h]), cigar_string(cg[coff[h]:coff[h + 1]]))
+                 for h in range(int(off[i]), int(off[i + 1]))] for i in range(len(off) - 1)]
+
+    def align_string_edit(self, query, k: int, max_candidates: int):
+        """-> [(LocalizedSequencePosition, distance, text_len, CIGAR string)] of one query"""
+        return self.parallel_align_edit([query], k, max_candidates)[0]
+
+    def dev_edit_align(self, d_qbytes, d_qoff, d_hit_query, d_hit_gpos, d_hit_edits, m, k, d_text_len, d_n_ops, d_ops, stream=None, slot=0):
+        """device-resident alignment of the triples (d_hit_query u32, d_hit_gpos u64, d_hit_edits u8)[m]: d_text_len[m] u32, d_n_ops[m] u8
+        and the runs d_ops[h * ALIGN_MAX_OPS ..] u32; a triple that is no alignment at that distance gets d_n_ops = 0"""
+        _check(self._L.awry_dev_edit_align(self._h, slot, d_qbytes, d_qoff, d_hit_query, d_hit_gpos, d_hit_edits, m, int(k), d_text_len, d_n_ops, d_ops,
+                                           stream))
+
+    def dev_edit_align_tally(self, d_qbytes, d_qoff, d_hit_query, d_hit_gpos, d_hit_edits, m, k, d_text_len, d_n_ops, d_ops, d_tally, stream=None,
+                             slot=0):
+        """dev_edit_align + census: d_tally[2] += (hits aligned, table cells computed)"""
+        _check(self._L.awry_dev_edit_align_tally(self._h, slot, d_qbytes, d_qoff, d_hit_query, d_hit_gpos, d_hit_edits, m, int(k), d_text_len, d_n_ops,
+                                                 d_ops, d_tally, stream))
 
     def debug_rank_all(self, rows: np.ndarray, slot=0) -> np.ndarray:
         """Occ of every non-sentinel symbol at each row through the kernels' all-symbol rank -> uint64[len(rows), S]

@@ -193,6 +193,42 @@ class FmIndex {
     awry_free_buffer(hoff); awry_free_buffer(hits); awry_free_buffer(gp); awry_free_buffer(ed); awry_free_buffer(st);
     return out;
   }
+  // the same hits aligned (awry_hip.h states the canonical script): the length of the text span each matches and its CIGAR,
+  // one run per entry, len << 4 | BAM op (I 1, D 2, = 7, X 8)
+  struct EditAlignment {
+    LocalizedSequencePosition position;
+    uint64_t global_position;
+    uint8_t edits;
+    uint32_t text_len;
+    std::vector<uint32_t> cigar;
+    std::string cigar_string() const {
+      std::string out;
+      for (uint32_t run : cigar) {
+        const uint32_t op = run & 15u;
+        out += std::to_string(run >> 4);
+        out += op == 7 ? '=' : op == 8 ? 'X' : op == 1 ? 'I' : 'D';
+      }
+      return out;
+    }
+  };
+  template <class StrRange>
+  std::vector<std::vector<EditAlignment>> parallel_align_edit(const StrRange& queries, int k, uint64_t max_candidates,
+                                                              std::vector<uint8_t>* status = nullptr) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* hoff = nullptr; awry_pos_t* hits = nullptr; uint64_t* gp = nullptr; uint8_t* ed = nullptr; uint8_t* st = nullptr;
+    uint32_t* tl = nullptr; uint64_t* coff = nullptr; uint32_t* cg = nullptr;
+    check(awry_align_edit_batch(h_, bytes.data(), off.data(), n, k, max_candidates, &hoff, &hits, &gp, &ed, &st, &tl, &coff, &cg));
+    std::vector<std::vector<EditAlignment>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = hoff[i]; j < hoff[i + 1]; j++)
+        out[i].push_back({{hits[j].seq_idx, hits[j].local_pos}, gp[j], ed[j], tl[j], std::vector<uint32_t>(cg + coff[j], cg + coff[j + 1])});
+    if (status) status->assign(st, st + n);
+    awry_free_buffer(hoff); awry_free_buffer(hits); awry_free_buffer(gp); awry_free_buffer(ed); awry_free_buffer(st);
+    awry_free_buffer(tl); awry_free_buffer(coff); awry_free_buffer(cg);
+    return out;
+  }
   // class patterns (no counterpart in the reference; the definition and the limits are in awry_hip.h): IUPAC / residue-class
   // letters with up to k mismatches.  counts[i * (k + 1) + d] = occurrences of pattern i at exactly d mismatches
   template <class StrRange>

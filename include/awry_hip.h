@@ -310,6 +310,44 @@ int awry_locate_edit_batch(awry_index_t *idx, const uint8_t *qbytes, const uint6
                            uint64_t max_candidates, uint64_t **hit_off_out, awry_pos_t **hits_out, uint64_t **global_pos_out,
                            uint8_t **edits_out, uint8_t **status_out);
 
+/* ---- align the hits of locate within k edits: text span and CIGAR per hit (no counterpart in the reference) ----
+ * What a mapping needs beyond a start and a distance: where the match ends in the text, and which letters were substituted,
+ * inserted or deleted.  T, n, q, L, k, D(s), the hit rule, the piece rule and the candidate cap are those of
+ * awry_locate_edit_batch.  For a hit (q, s, d), d = D(s):
+ *     C[i][j] = edit_distance(q[0..i), T[s..s+j))    0 <= i <= L, 0 <= j <= J = min(L + d, n - s)   (unit costs, symbol indices compared)
+ *     text_len = the smallest j with C[L][j] == d                                 (the match is T[s .. s + text_len))
+ *     traceback from (i, j) = (L, text_len) to (0, 0); at each cell take the first of these that holds:
+ *         1. i > 0 and j > 0 and C[i-1][j-1] + (q[i-1] != T[s+j-1]) == C[i][j]  ->  '=' if the symbols are equal, else 'X';  i--, j--
+ *         2. i > 0 and C[i-1][j] + 1 == C[i][j]                                 ->  'I' (a query letter with no text letter); i--
+ *         3. otherwise (j > 0 and C[i][j-1] + 1 == C[i][j])                     ->  'D' (a text letter with no query letter); j--
+ *     the operations, reversed into query order and run-length encoded, are the hit's CIGAR.
+ * Properties (proven below, and tested against the full table):
+ *   Banded table.  The table restricted to the band |i - j| <= d, cells outside it +infinity, gives the same text_len and the
+ *     same script: an optimal path to a cell whose true value is v <= d holds at most v insertions and deletions, so it never
+ *     leaves the band; hence a banded value <= d is exact (banded values are never below the true ones), and the equality tests
+ *     of the traceback -- each with a cell of the path, value <= d, on its right side -- come out the same.  2d + 1 <= 17
+ *     cells per row suffice.
+ *   No 'D' at either end.  A script never begins with 'D': dropping the leading text letter would align q at s + 1 with d - 1
+ *     edits, and s is a local minimum of D.  It never ends with 'D': dropping the last text letter would give C[L][text_len - 1]
+ *     = d - 1 < d = D(s).
+ *   Bounds.  The operations other than '=' number exactly d; |text_len - L| <= d; d operations separate at most d + 1 runs of
+ *     '=', so a script has at most 2d + 1 runs: AWRY_ALIGN_MAX_OPS = 2 AWRY_MAX_EDITS + 1 = 17 is a hard bound.
+ *   Where gaps fall.  Preferring the diagonal while walking from the end puts gaps as far left as the optimum allows (the
+ *     usual left-normalised form): in "AC" x 10 with one unit deleted the gap is at the array's left end.
+ * Encoding: one uint32_t per run, len << 4 | op, with BAM's op codes I = 1, D = 2, '=' = 7, X = 8; M is never produced.
+ * awry_align_edit_batch: hit_off, hits, global_pos, edits and status are exactly what awry_locate_edit_batch returns for the same
+ * arguments -- errors, the candidate cap, chunk splitting by AWRY_EDIT_CANDIDATE_CAP and sharding over replicas included; an
+ * abandoned query has no hits and no runs.  text_len[h] is hit h's span; its runs are cigar[cigar_off[h] .. cigar_off[h+1]),
+ * cigar_off has hit_off[n] + 1 entries.  All but hit_off_out nullable; cigar_off_out and cigar_out are given or omitted
+ * together (one without the other => AWRY_ERR_ARG).  Arrays are pinned (awry_free_buffer).  The script is computed on the
+ * device from the resident text copy, in sub-batches of 2^20 hits (env AWRY_ALIGN_SUB_BATCH, read per call), which bounds the
+ * device staging at 89 B x the sub-batch whatever the hit count. */
+enum { AWRY_ALIGN_MAX_OPS = 17 };
+int awry_align_edit_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, int max_edits,
+                          uint64_t max_candidates, uint64_t **hit_off_out, awry_pos_t **hits_out, uint64_t **global_pos_out,
+                          uint8_t **edits_out, uint8_t **status_out, uint32_t **text_len_out, uint64_t **cigar_off_out,
+                          uint32_t **cigar_out);
+
 /* releases an array one of the calls above (or awry_locate / awry_read_query_file) returned.  Result arrays are pinned
  * host memory recycled through a process-wide pool (the device writes results straight into them); never pass them to
  * free().  AWRY_PINNED_CACHE_GB (default 4) bounds what the pool keeps between calls. */
@@ -482,6 +520,25 @@ int awry_dev_edit_windows_tally(awry_index_t *idx, int slot, const uint8_t *d_qb
                                 const uint32_t *d_win_query, const uint64_t *d_win_first, const uint32_t *d_win_count, uint64_t m,
                                 int max_edits, uint64_t *d_n_hits, const uint64_t *d_hit_off, uint64_t *d_gpos, uint8_t *d_edits,
                                 uint64_t *d_tally, void *stream);
+/* The device primitive under awry_align_edit_batch (the definition is stated there), for a caller with hits of their own.
+ * Hit h is the triple (d_hit_query[h] (u32 index into the CSR d_qbytes / d_qoff), d_hit_gpos[h] (u64 start), d_hit_edits[h] (u8
+ * distance)); output at a fixed stride: d_text_len[m] (u32), d_n_ops[m] (u8) and the runs d_ops[h * AWRY_ALIGN_MAX_OPS ..
+ * + d_n_ops[h]) (u32, m * AWRY_ALIGN_MAX_OPS entries; the rest of a hit's slot is unspecified).  A triple that is no alignment
+ * at that distance gets d_n_ops = 0 and d_text_len = 0 and nothing else happens: the minimum of row L inside the band of
+ * half-width d_hit_edits[h] differs from d_hit_edits[h]; the start is >= n; the distance exceeds max_edits; the query is
+ * empty, longer than AWRY_EDIT_MAX_LEN or not longer than max_edits.  A start that is no local minimum of D but has D(s) = the
+ * given distance is aligned by the same rule (its script may begin with 'D').  Hits in query order read best.  No
+ * synchronisation except where the direction workspace (owned by the replica, per stream, at most 128 MiB) grows, or the text
+ * copy is built, on first use. */
+int awry_dev_edit_align(awry_index_t *idx, int slot, const uint8_t *d_qbytes, const uint64_t *d_qoff, const uint32_t *d_hit_query,
+                        const uint64_t *d_hit_gpos, const uint8_t *d_hit_edits, uint64_t m, int max_edits, uint32_t *d_text_len,
+                        uint8_t *d_n_ops, uint32_t *d_ops, void *stream);
+/* the same with a work census: d_tally[2] (u64, caller-zeroed) += {hits aligned (d_n_ops != 0), table cells computed (the cells
+ * of rows 0..L with |i - j| <= d and j <= J, of every triple whose query and start the kernel takes)} */
+int awry_dev_edit_align_tally(awry_index_t *idx, int slot, const uint8_t *d_qbytes, const uint64_t *d_qoff,
+                              const uint32_t *d_hit_query, const uint64_t *d_hit_gpos, const uint8_t *d_hit_edits, uint64_t m,
+                              int max_edits, uint32_t *d_text_len, uint8_t *d_n_ops, uint32_t *d_ops, uint64_t *d_tally,
+                              void *stream);
 /* test hook of the all-symbol rank primitive: d_occ[i * S + s - 1] = Occ(s, d_rows[i]) for every non-sentinel symbol index s
  * (S = 5 nucleotide, 21 amino; inclusive of the row, as awry_update_range uses it); rows >= bwt_len give zeros */
 int awry_debug_rank_all(awry_index_t *idx, int slot, const void *d_rows, uint64_t n, void *d_occ, void *stream);

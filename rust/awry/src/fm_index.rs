@@ -199,6 +199,21 @@ struct Csr {
     offsets: Vec<u64>,
 }
 
+/// The CIGAR string of the runs [`FmIndex::parallel_align_edit`] returns (`len << 4 | op`, BAM's op codes): `"57=1X43="`.
+pub fn cigar_string(runs: &[u32]) -> String {
+    let mut out = String::new();
+    for &run in runs {
+        out.push_str(&(run >> 4).to_string());
+        out.push(match run & 15 {
+            7 => '=',
+            8 => 'X',
+            1 => 'I',
+            _ => 'D',
+        });
+    }
+    out
+}
+
 fn to_csr<'a>(queries: impl ParallelIterator<Item = &'a str>) -> Csr {
     let list: Vec<&'a str> = queries.collect();
     let mut offsets = Vec::with_capacity(list.len() + 1);
@@ -618,6 +633,63 @@ impl FmIndex {
             sys::awry_free_buffer(hits as *mut std::os::raw::c_void);
             sys::awry_free_buffer(ed as *mut std::os::raw::c_void);
             sys::awry_free_buffer(st as *mut std::os::raw::c_void);
+        }
+        Ok(out)
+    }
+
+    /// The same hits aligned (the canonical script is defined in include/awry_hip.h): per query, `(position, distance, text_len,
+    /// cigar)` in ascending text position -- the hit matches `text_len` text letters from its start by the runs `cigar`, each
+    /// `len << 4 | op` with BAM's op codes (I = 1, D = 2, '=' = 7, X = 8; at most 17 runs) -- and per query whether it was
+    /// abandoned by the candidate cap.  [`cigar_string`] renders the runs.
+    #[allow(clippy::type_complexity)]
+    pub fn parallel_align_edit<'a>(
+        &self,
+        queries: impl ParallelIterator<Item = &'a str>,
+        max_edits: u32,
+        max_candidates: u64,
+    ) -> Result<(Vec<Vec<(LocalizedSequencePosition, u8, u32, Vec<u32>)>>, Vec<bool>), AwryError> {
+        let csr = to_csr(queries);
+        let n = csr.offsets.len() - 1;
+        let mut hit_off: *mut u64 = std::ptr::null_mut();
+        let mut hits: *mut sys::awry_pos_t = std::ptr::null_mut();
+        let mut ed: *mut u8 = std::ptr::null_mut();
+        let mut st: *mut u8 = std::ptr::null_mut();
+        let mut tl: *mut u32 = std::ptr::null_mut();
+        let mut cigar_off: *mut u64 = std::ptr::null_mut();
+        let mut cigar: *mut u32 = std::ptr::null_mut();
+        check(unsafe {
+            sys::awry_align_edit_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, max_edits as i32, max_candidates, &mut hit_off,
+                                       &mut hits, std::ptr::null_mut(), &mut ed, &mut st, &mut tl, &mut cigar_off, &mut cigar)
+        })?;
+        let out = unsafe {
+            let off = std::slice::from_raw_parts(hit_off, n + 1);
+            let total = off[n] as usize;
+            let flat: &[sys::awry_pos_t] = if total == 0 { &[] } else { std::slice::from_raw_parts(hits, total) };
+            let dist: &[u8] = if total == 0 { &[] } else { std::slice::from_raw_parts(ed, total) };
+            let span: &[u32] = if total == 0 { &[] } else { std::slice::from_raw_parts(tl, total) };
+            let coff = std::slice::from_raw_parts(cigar_off, total + 1);
+            let runs: &[u32] = if coff[total] == 0 { &[] } else { std::slice::from_raw_parts(cigar, coff[total] as usize) };
+            let status: &[u8] = if n == 0 { &[] } else { std::slice::from_raw_parts(st, n) };
+            let per = (0..n)
+                .map(|i| {
+                    (off[i] as usize..off[i + 1] as usize)
+                        .map(|j| {
+                            (LocalizedSequencePosition::new(flat[j].seq_idx as usize, flat[j].local_pos as usize), dist[j], span[j],
+                             runs[coff[j] as usize..coff[j + 1] as usize].to_vec())
+                        })
+                        .collect::<Vec<_>>()
+                })
+                .collect::<Vec<_>>();
+            (per, status.iter().map(|&s| s == 7).collect::<Vec<_>>())  // AWRY_Q_CANDIDATE_CAP
+        };
+        unsafe {
+            sys::awry_free_buffer(hit_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(hits as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(ed as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(st as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(tl as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(cigar_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(cigar as *mut std::os::raw::c_void);
         }
         Ok(out)
     }
