@@ -26,6 +26,15 @@ class Anchor(C.Structure):  # awry_anchor_t
     _fields_ = [("q_begin", C.c_uint32), ("q_len", C.c_uint32), ("start_row", C.c_uint64), ("count", C.c_uint64)]
 
 
+class Seed(C.Structure):  # awry_seed_t
+    _fields_ = [("q_begin", C.c_uint32), ("q_len", C.c_uint32), ("t_pos", C.c_uint64)]
+
+
+class Chain(C.Structure):  # awry_chain_t
+    _fields_ = [("score", C.c_uint32), ("n_seeds", C.c_uint32), ("q_begin", C.c_uint32), ("q_end", C.c_uint32), ("t_begin", C.c_uint64),
+                ("t_end", C.c_uint64)]
+
+
 class BuildArgs(C.Structure):
     _fields_ = [("input_path", C.c_char_p), ("sa_tmp_path", C.c_char_p), ("sa_ratio", C.c_uint64),
                 ("kmer_len", C.c_uint8), ("alphabet", C.c_uint8), ("max_query_len", C.c_uint64),
@@ -112,6 +121,10 @@ def load_library():
     sig("awry_locate_smems_batch", i32, vp, vp, u64p, u64, u32, u64, C.POINTER(u64p), app, C.POINTER(u64p), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p))
     sig("awry_dev_smems", i32, vp, i32, vp, vp, u64, u32, vp, vp, vp, vp, vp)
     sig("awry_dev_smems_tally", i32, vp, i32, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp)
+    sig("awry_chain_batch", i32, vp, vp, u64p, u64, u32, u64, u32, u32, u32, u32, u32, C.POINTER(u64p), C.POINTER(C.POINTER(Chain)), C.POINTER(u64p),
+        C.POINTER(C.POINTER(Seed)), C.POINTER(u8p))
+    sig("awry_dev_chain_seeds", i32, vp, i32, vp, vp, u64, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp)
+    sig("awry_dev_chain_seeds_tally", i32, vp, i32, vp, vp, u64, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp)
     sig("awry_locate_edit_batch", i32, vp, vp, u64p, u64, i32, u64, C.POINTER(u64p), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(u8p),
         C.POINTER(u8p))
     sig("awry_dev_edit_windows", i32, vp, i32, vp, vp, vp, vp, vp, u64, i32, vp, vp, vp, vp, vp)

@@ -9,6 +9,7 @@
 #include "mismatch_host.h"
 #include "pattern_host.h"
 #include "anchor_host.h"
+#include "chain_host.h"
 #include "edit_host.h"
 #include "prewarm.h"
 
@@ -407,6 +408,20 @@ int awry_locate_smems_batch(awry_index_t* idx, const uint8_t* qbytes, const uint
     require_smem_args(min_len);
     require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
     anchor_batch(idx, qbytes, qoff, n, smem_finder(min_len), max_hits, smem_off_out, smems_out, hit_off_out, hits_out, global_pos_out);
+  });
+}
+
+int awry_chain_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits, uint32_t max_seeds,
+                     uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score, uint64_t** chain_off_out, awry_chain_t** chains_out,
+                     uint64_t** seed_off_out, awry_seed_t** seeds_out, uint8_t** status_out) {
+  return guarded([&] {
+    require(idx && qoff && chain_off_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_smem_args(min_len);
+    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
+    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    require((seed_off_out == nullptr) == (seeds_out == nullptr), "seed_off_out and seeds_out are given or omitted together");
+    chain_batch(idx, qbytes, qoff, n, min_len, max_hits, P, chain_off_out, chains_out, seed_off_out, seeds_out, status_out);
   });
 }
 
@@ -915,6 +930,28 @@ int awry_dev_edit_align_tally(awry_index_t* idx, int slot, const uint8_t* d_qbyt
     require(m == 0 || (d_qbytes && d_qoff && d_hit_query && d_hit_gpos && d_hit_edits && d_text_len && d_n_ops && d_ops), "null device pointer");
     launch_edit_align(r, edit_text(r), d_qbytes, d_qoff, d_hit_query, d_hit_gpos, d_hit_edits, m, max_edits, EDIT_MAX_LEN, d_text_len, d_n_ops, d_ops,
                       (hipStream_t)stream, (unsigned long long*)d_tally);
+  });
+}
+
+int awry_dev_chain_seeds(awry_index_t* idx, int slot, const uint64_t* d_seed_off, const awry_seed_t* d_seeds, uint64_t n, uint32_t max_seeds,
+                         uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score, uint64_t* d_n_chains, uint64_t* d_n_members,
+                         const uint64_t* d_chain_off, const uint64_t* d_member_off, awry_chain_t* d_chains, awry_seed_t* d_members, uint8_t* d_status,
+                         void* stream) {
+  return awry_dev_chain_seeds_tally(idx, slot, d_seed_off, d_seeds, n, max_seeds, lookback, max_gap, max_skew, min_score, d_n_chains, d_n_members,
+                                    d_chain_off, d_member_off, d_chains, d_members, d_status, nullptr, stream);
+}
+
+int awry_dev_chain_seeds_tally(awry_index_t* idx, int slot, const uint64_t* d_seed_off, const awry_seed_t* d_seeds, uint64_t n, uint32_t max_seeds,
+                               uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score, uint64_t* d_n_chains, uint64_t* d_n_members,
+                               const uint64_t* d_chain_off, const uint64_t* d_member_off, awry_chain_t* d_chains, awry_seed_t* d_members,
+                               uint8_t* d_status, uint64_t* d_tally, void* stream) {
+  return guarded([&] {
+    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    Replica& r = replica(idx, slot);
+    require_chain_index(r.dev.bwt_len);
+    require(n == 0 || (d_seed_off && (d_chain_off ? d_member_off && d_chains && d_members : d_n_chains && d_n_members)), "null device pointer");
+    launch_chain(r, d_seed_off, reinterpret_cast<const Seed*>(d_seeds), n, P, d_n_chains, d_n_members, d_chain_off, d_member_off,
+                 reinterpret_cast<Chain*>(d_chains), reinterpret_cast<Seed*>(d_members), d_status, (hipStream_t)stream, (unsigned long long*)d_tally);
   });
 }
 

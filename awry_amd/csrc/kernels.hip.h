@@ -41,6 +41,10 @@
 //                                                            direction words in a lane-interleaved workspace, one hit per lane: text span and
 //                                                            CIGAR runs at a fixed stride [kernels_align]
 //                         + align_hit_query / counts / compact kernels: the hits' queries, and fixed stride -> CSR [kernels_align]
+//   chain located seeds   CHAIN_KERNEL<G, FILL>              sort, windowed dynamic programme and backtrack, one query per group of G = 64 or 16
+//                                                            lanes, lane l on predecessor i - 1 - l, DPP maximum: count pass, two scans, fill
+//                                                            pass [kernels_chain]
+//                         + chain_expand / chain_seed_off kernels: located SMEM records -> seeds and per-query seed offsets [kernels_chain]
 //   count, wide rows      count_nt2_wide_kernel, count_nt2_wide_probe_kernel   64-bit rows [kernels_wide]
 //   locate                LOCATE_TILE_KERNEL<A>              hit -> row, sampled / verified hits finished [this file]
 //                         + LOCATE_WALK_NT_LANE_KERNEL       LF walks of the rest, one hit per lane, whole block per step [this file]
@@ -560,3 +564,4 @@ __global__ __launch_bounds__(256) void locate_walk_nt_lane_kernel(DevIndex ix, u
 
 #include "edit_kernels.hip.h"      // localise, backstep_scalar, symbol_at, ByteStream
 #include "kernels_align.hip.h"     // edit_symbols, edit_owner, ByteStream
+#include "kernels_chain.hip.h"     // localise, tally_add, Anchor

@@ -555,6 +555,43 @@ void launch_edit_align(Replica& r, const uint8_t* text8, const uint8_t* d_q, con
   HIP_CHECK(hipGetLastError());
 }
 
+// Chaining (kernels_chain.hip.h) on n queries' seeds.  d_chain_off == nullptr: the count pass (d_n_chains, d_n_members); else the
+// fill pass.  A group of 16 lanes owns a query when lookback <= 16, else a wave (AWRY_CHAIN_GROUP=64, read per call: the wave there
+// too).  Queries beyond the group's LDS tile work in a slab of the stream's scratch, one per group of the grid: the grid is cut so
+// that the slabs stay within CHAIN_SLAB_BYTES (at max_seeds = 4096, 144 KiB a slab: 910 groups).
+constexpr size_t CHAIN_SLAB_BYTES = 128u << 20;
+int chain_group_width(uint32_t lookback) {
+  const char* e = getenv("AWRY_CHAIN_GROUP");
+  return lookback <= 16 && !(e && atoi(e) == 64) ? 16 : 64;
+}
+void launch_chain(Replica& r, const uint64_t* d_seed_off, const Seed* d_seeds, uint64_t n, const ChainParams& P, uint64_t* d_n_chains,
+                  uint64_t* d_n_members, const uint64_t* d_chain_off, const uint64_t* d_member_off, Chain* d_chains, Seed* d_members, uint8_t* d_status,
+                  hipStream_t s, unsigned long long* d_tally = nullptr) {
+  if (n == 0) return;
+  const ScratchLock scratch_lock(r, s);
+  Replica::SurvScratch* sc = surv_scratch(r, s);
+  auto chain = [&](auto GG, auto F) {
+    constexpr int G = decltype(GG)::value, GROUPS = 256 / G;
+    uint32_t slab_cap = 0;
+    if (P.max_seeds > (uint32_t)ChainTile<G>::value)
+      for (slab_cap = 1; slab_cap < P.max_seeds;) slab_cap <<= 1;
+    uint64_t blocks = (uint64_t)grid_for(r, n, GROUPS, 4);
+    const size_t slab = (size_t)slab_cap * CHAIN_SEED_BYTES * GROUPS;  // per block
+    if (slab) blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, CHAIN_SLAB_BYTES / slab));
+    if (sc->chain_slabs.n < blocks * slab) {
+      HIP_CHECK(hipStreamSynchronize(s));
+      sc->chain_slabs.alloc(blocks * slab);
+    }
+    hipLaunchKernelGGL((chain_kernel<G, decltype(F)::value ? 1 : 0>), dim3((unsigned)blocks), dim3(256), 0, s, r.dev, d_seed_off, d_seeds, n, P, d_n_chains,
+                       d_n_members, d_chain_off, d_member_off, d_chains, d_members, d_status, reinterpret_cast<char*>(sc->chain_slabs.p), slab_cap, d_tally);
+  };
+  with_flags(d_chain_off != nullptr, [&](auto F) {
+    if (chain_group_width(P.lookback) == 16) chain(std::integral_constant<int, 16>{}, F);
+    else chain(std::integral_constant<int, 64>{}, F);
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 // anchor records -> (start_row, end_row) pairs and located counts (0 for anchors of more than max_hits rows)
 void launch_anchor_ranges(Replica& r, const Anchor* d_anchors, uint64_t n, uint64_t max_hits, uint64_t* d_ranges, uint64_t* d_located, hipStream_t s) {
   if (n == 0) return;

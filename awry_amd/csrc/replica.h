@@ -132,6 +132,8 @@ struct Replica {
     DevBuf<uint64_t> edit_masks;
     // edit_align_kernel: one direction word per table row and grid lane, [row][grid lane] (sized by the grid, launchers.h)
     DevBuf<uint64_t> align_trace;
+    // chain_kernel: the working sets of queries beyond the LDS tile, one slab per group of the grid (sized by the grid, launchers.h)
+    DevBuf<uint8_t> chain_slabs;
     // work-queue heads of the chunk / locate kernels launched on this stream: launches on one stream are ordered, so a
     // head is free again by the time the ring comes back to it, however many launches other streams have in flight
     DevBuf<unsigned long long> counters;

@@ -30,6 +30,7 @@ ERR_IO, ERR_FORMAT, ERR_INVALID_QUERY, ERR_HIP, ERR_OOM, ERR_ARG, ERR_NO_DEVICE 
 MAX_MISMATCHES = 2  # AWRY_MAX_MISMATCHES
 MAX_EDITS, EDIT_MAX_LEN, Q_CANDIDATE_CAP = 8, 256, 7  # AWRY_MAX_EDITS, AWRY_EDIT_MAX_LEN, AWRY_Q_CANDIDATE_CAP
 ALIGN_MAX_OPS = 17  # AWRY_ALIGN_MAX_OPS
+CHAIN_MAX_SEEDS, CHAIN_MAX_LOOKBACK, Q_SEED_CAP = 4096, 64, 8  # AWRY_CHAIN_MAX_SEEDS, AWRY_CHAIN_MAX_LOOKBACK, AWRY_Q_SEED_CAP
 CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}  # the BAM op codes the alignment pass produces
 
 
@@ -101,6 +102,9 @@ _u64p = C.POINTER(C.c_uint64)
 
 # awry_anchor_t as a numpy record (24 bytes, the C layout)
 ANCHOR_DTYPE = np.dtype([("q_begin", np.uint32), ("q_len", np.uint32), ("start_row", np.uint64), ("count", np.uint64)])
+SEED_DTYPE = np.dtype([("q_begin", np.uint32), ("q_len", np.uint32), ("t_pos", np.uint64)])  # awry_seed_t
+CHAIN_DTYPE = np.dtype([("score", np.uint32), ("n_seeds", np.uint32), ("q_begin", np.uint32), ("q_end", np.uint32), ("t_begin", np.uint64),
+                        ("t_end", np.uint64)])  # awry_chain_t
 
 
 class _Owned:
@@ -575,6 +579,58 @@ class FmIndex:
         """dev_smems + census: d_tally[4] += (LF steps executed, suffixes compared by the SA search, forward extensions, SMEMs reported)"""
         _check(self._L.awry_dev_smems_tally(self._h, slot, d_qbytes, d_qoff, n, int(min_len), d_n_smems, d_smem_off, d_smems, d_status, d_tally,
                                             stream))
+
+    # ------------------------------------------------------------------ colinear chaining of the located SMEM seeds
+    def parallel_chains_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 12, max_hits: int = 50, max_seeds: int = 1024,
+                            lookback: int = 32, max_gap: int = 1000, max_skew: int = 100, min_score: int = 20, want_seeds: bool = True):
+        """-> (chain_off uint64[n+1], chains CHAIN_DTYPE[total], seed_off uint64[total+1], seeds SEED_DTYPE[members], status uint8[n]):
+        the chains of every query's located SMEM seeds (include/awry_hip.h states the definition), the primary chain first; the
+        members of chain c are seeds[seed_off[c]:seed_off[c+1]], first to last; status[i] == Q_SEED_CAP marks a query abandoned
+        because it has more than max_seeds seeds (it has no chains); want_seeds=False leaves seed_off and seeds empty"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        off, ch, soff, sd, st = _u64p(), C.POINTER(_lib.Chain)(), _u64p(), C.POINTER(_lib.Seed)(), C.POINTER(C.c_uint8)()
+        _check(self._L.awry_chain_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(max_hits), int(max_seeds),
+                                        int(lookback), int(max_gap), int(max_skew), int(min_score), C.byref(off), C.byref(ch),
+                                        C.byref(soff) if want_seeds else None, C.byref(sd) if want_seeds else None, C.byref(st)))
+        offs = _adopt(self._L, off, n + 1, np.uint64)
+        tot = int(offs[-1])
+        chains = _adopt(self._L, ch, 32 * tot, np.uint8).view(CHAIN_DTYPE)
+        status = _adopt(self._L, st, n, np.uint8)
+        if not want_seeds:
+            return offs, chains, np.zeros(0, np.uint64), np.zeros(0, SEED_DTYPE), status
+        seed_off = _adopt(self._L, soff, tot + 1, np.uint64)
+        return offs, chains, seed_off, _adopt(self._L, sd, 16 * int(seed_off[-1]), np.uint8).view(SEED_DTYPE), status
+
+    def parallel_chains(self, queries: Iterable, min_len: int = 12, max_hits: int = 50, **params):
+        """-> per query, its chains as (score, q_begin, q_end, t_begin, t_end, [(q_begin, q_len, t_pos), ...]), the primary chain
+        first (none for an abandoned query); params: max_seeds, lookback, max_gap, max_skew, min_score"""
+        off, ch, soff, sd, _ = self.parallel_chains_csr(*pack_queries(queries), min_len, max_hits, **params)
+        return [[(int(c["score"]), int(c["q_begin"]), int(c["q_end"]), int(c["t_begin"]), int(c["t_end"]),
+                  [tuple(int(v) for v in m) for m in sd[soff[j]:soff[j + 1]]]) for j, c in enumerate(ch[off[i]:off[i + 1]], int(off[i]))]
+                for i in range(len(off) - 1)]
+
+    def chains_string(self, query, min_len: int = 12, max_hits: int = 50, **params):
+        """chains of one query"""
+        return self.parallel_chains([query], min_len, max_hits, **params)[0]
+
+    def dev_chain_seeds(self, d_seed_off, d_seeds, n, max_seeds, lookback, max_gap, max_skew, min_score, d_n_chains, d_n_members,
+                        d_chain_off=None, d_member_off=None, d_chains=None, d_members=None, d_status=None, stream=None, slot=0):
+        """device-resident chaining of the caller's seeds (16-byte records, query q: d_seeds[d_seed_off[q] .. d_seed_off[q+1])):
+        d_chain_off None = the count pass (d_n_chains[n], d_n_members[n] u64, optional d_status[n]); else the fill pass writing
+        32-byte chain records at d_chains[d_chain_off[q] ...) and their members at d_members[d_member_off[q] ...); scan both
+        counts with dev_scan_counts in between"""
+        _check(self._L.awry_dev_chain_seeds(self._h, slot, d_seed_off, d_seeds, n, int(max_seeds), int(lookback), int(max_gap), int(max_skew),
+                                            int(min_score), d_n_chains, d_n_members, d_chain_off, d_member_off, d_chains, d_members, d_status,
+                                            stream))
+
+    def dev_chain_seeds_tally(self, d_seed_off, d_seeds, n, max_seeds, lookback, max_gap, max_skew, min_score, d_n_chains, d_n_members, d_tally,
+                              d_chain_off=None, d_member_off=None, d_chains=None, d_members=None, d_status=None, stream=None, slot=0):
+        """dev_chain_seeds + census: d_tally[3] += (seeds chained, predecessor pairs evaluated, chains reported)"""
+        _check(self._L.awry_dev_chain_seeds_tally(self._h, slot, d_seed_off, d_seeds, n, int(max_seeds), int(lookback), int(max_gap),
+                                                  int(max_skew), int(min_score), d_n_chains, d_n_members, d_chain_off, d_member_off, d_chains,
+                                                  d_members, d_status, d_tally, stream))
 
     # ------------------------------------------------------------------ locate within k edits (substitutions, insertions, deletions)
     def parallel_locate_edit_csr(self, qbytes: np.ndarray, qoff: np.ndarray, k: int, max_candidates: int, want_pos: bool = True):

@@ -331,6 +331,34 @@ class FmIndex {
     awry_free_buffer(soff); awry_free_buffer(sm); awry_free_buffer(hoff); awry_free_buffer(hits);
     return out;
   }
+  // colinear chaining of the located SMEM seeds (no counterpart in the reference; the definition is in awry_hip.h): per query, its
+  // chains, the primary chain first -- a score, the spans it covers in query and text, and its seeds first to last.  A query of
+  // more than p.max_seeds seeds is abandoned: no chains, and (*status)[i] == AWRY_Q_SEED_CAP where the caller asks for the status bytes.
+  struct ChainParams {
+    uint32_t max_seeds = 1024, lookback = 32, max_gap = 1000, max_skew = 100, min_score = 20;
+  };
+  struct Chain {
+    uint32_t score, q_begin, q_end;
+    uint64_t t_begin, t_end;
+    std::vector<awry_seed_t> seeds;
+  };
+  template <class StrRange>
+  std::vector<std::vector<Chain>> parallel_chains(const StrRange& queries, uint32_t min_len = 12, uint64_t max_hits = 50, ChainParams p = ChainParams(),
+                                                  std::vector<uint8_t>* status = nullptr) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* coff = nullptr; awry_chain_t* ch = nullptr; uint64_t* soff = nullptr; awry_seed_t* sd = nullptr; uint8_t* st = nullptr;
+    check(awry_chain_batch(h_, bytes.data(), off.data(), n, min_len, max_hits, p.max_seeds, p.lookback, p.max_gap, p.max_skew, p.min_score, &coff, &ch,
+                           &soff, &sd, &st));
+    std::vector<std::vector<Chain>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = coff[i]; j < coff[i + 1]; j++)
+        out[i].push_back({ch[j].score, ch[j].q_begin, ch[j].q_end, ch[j].t_begin, ch[j].t_end, std::vector<awry_seed_t>(sd + soff[j], sd + soff[j + 1])});
+    if (status) status->assign(st, st + n);
+    awry_free_buffer(coff); awry_free_buffer(ch); awry_free_buffer(soff); awry_free_buffer(sd); awry_free_buffer(st);
+    return out;
+  }
   // src/fm_index.rs:559-582, 585-593
   SearchRange update_range_with_symbol(SearchRange r, char symbol) {
     awry_range_t o;

@@ -205,7 +205,8 @@ enum { AWRY_MAX_CLASS_POSITIONS = 16, AWRY_PATTERN_MAX_FRAMES = 18, AWRY_PATTERN
 enum {
   AWRY_Q_OK = 0, AWRY_Q_EMPTY = 1, AWRY_Q_SENTINEL = 2, AWRY_Q_NON_ASCII = 3,
   AWRY_Q_NOT_CLASS_LETTER = 4, AWRY_Q_CLASS_POSITIONS = 5, AWRY_Q_EXPANSION_CAP = 6 /* patterns only */,
-  AWRY_Q_CANDIDATE_CAP = 7 /* awry_locate_edit_batch only: the query was abandoned, not rejected */
+  AWRY_Q_CANDIDATE_CAP = 7 /* awry_locate_edit_batch only: the query was abandoned, not rejected */,
+  AWRY_Q_SEED_CAP = 8 /* awry_chain_batch / awry_dev_chain_seeds only: more seeds than max_seeds; abandoned, not rejected */
 };
 /* class mask of an ASCII byte as a pattern letter: bit s = symbol index s belongs to the class, 0 = not a class letter (or
  * an unknown alphabet id).  The one table of host and device; needs no GPU. */
@@ -347,6 +348,51 @@ int awry_align_edit_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64
                           uint64_t max_candidates, uint64_t **hit_off_out, awry_pos_t **hits_out, uint64_t **global_pos_out,
                           uint8_t **edits_out, uint8_t **status_out, uint32_t **text_len_out, uint64_t **cigar_off_out,
                           uint32_t **cigar_out);
+
+/* ---- colinear chaining of the located SMEM seeds of a query (no counterpart in the reference) -------------------
+ * What a mapper puts between seeding and verification: seeds that lie in the same order, on nearly the same diagonal, in read
+ * and text are grouped into chains, each chain gets a score, and the best chain is where the read belongs.  Everything is
+ * integer and every tie is broken explicitly.
+ * Seeds.  A seed is an awry_seed_t: q[q_begin .. q_begin + q_len) matches the text at t_pos.  The seeds of a query are the records
+ *   of awry_locate_smems_batch(min_len, max_hits): every record with count <= max_hits gives one seed per hit (t_pos = that
+ *   hit's global_pos); a record over max_hits gives none (repeat masking, exactly as locate treats it).  rec(seed) is the record
+ *   index awry_get_seq_location(t_pos) returns.  With N the number of seeds of the query: N > max_seeds abandons the query --
+ *   status byte AWRY_Q_SEED_CAP, no chains -- and does not fail the batch (the rule of AWRY_Q_CANDIDATE_CAP).
+ * Order.  The seeds of a query are sorted ascending by (t_pos, q_begin, q_len, input index) and numbered 0 .. N-1.  SMEM begins
+ *   are strictly monotone, so seeds that come from SMEMs never tie on the first two keys; the last two exist for the seeds a
+ *   caller supplies (awry_dev_chain_seeds), which may.
+ * Score.  Parameters lookback (1 .. AWRY_CHAIN_MAX_LOOKBACK), max_gap >= 1, max_skew >= 0.  For j < i with i - j <= lookback let
+ *   dq = q_begin_i - q_begin_j, dt = t_pos_i - t_pos_j, g = |dq - dt|.  j may precede i iff rec_j == rec_i and 0 < dq <= max_gap
+ *   and 0 < dt <= max_gap and g <= max_skew.  Then
+ *       gain(j, i) = min(q_len_i, dq, dt) - g                                         (may be negative)
+ *       f_i = max( q_len_i , max over admissible j of f_j + gain(j, i) )
+ *       p_i = the admissible j with f_j + gain(j, i) == f_i, if f_i > q_len_i; among several the LARGEST j; else none
+ *   Consequence: gain(j, i) <= dq, so along the predecessors of i back to the seed c that has none, f_i <= q_len_c + (q_begin_i -
+ *   q_begin_c) <= q_begin_i + q_len_c; with seeds of one length (k-mers) that is f_i <= q_begin_i + q_len_i.  (For seeds of unequal
+ *   lengths that last form does not hold: a long seed followed by a short one that begins inside it scores more than the short
+ *   one's end.)  Seeds inside a query of L letters give f_i < 2 L: a query of 2^31 letters or more => AWRY_ERR_ARG, so every score
+ *   fits 32 bits.
+ * Chains (minimap2's backtrack rule).  Visit the seeds in descending f, ties in ascending sorted index.  An unvisited seed e ends
+ *   a chain: walk e, p_e, p_{p_e}, ... and mark each seed used; stop when there is no predecessor (base = 0) or the predecessor u
+ *   is already used (base = f_u; u is not a member).  Chain score = f_e - base; the chain is reported iff score >= min_score.
+ *   Seeds walked by an unreported chain stay used.  Chains of a query are reported in the order found: the first is the primary.
+ * Records.  awry_chain_t: q_begin / t_begin come from the chain's first member, q_end / t_end are the maxima of q_begin + q_len /
+ *   t_pos + q_len over its members, n_seeds counts them; the members are listed first to last, in sorted order.
+ * Scope.  Forward strand only.  Indexes with bwt_len >= 2^32 => AWRY_ERR_ARG, as on the edit path (a small index on wide-row
+ *   replicas works).  No accelerator, seed-table length, row width, replica count or chunk capacity changes any output.
+ * AWRY_ERR_ARG: max_seeds == 0 or > AWRY_CHAIN_MAX_SEEDS, lookback outside 1 .. AWRY_CHAIN_MAX_LOOKBACK, max_gap == 0, min_score
+ * == 0, min_len == 0, max_hits == 0.  Malformed queries fail the batch with AWRY_ERR_INVALID_QUERY, as for SMEMs, and leave the
+ * out-pointers untouched; no replica => AWRY_ERR_NO_DEVICE.  The hit capacity of a chunk (AWRY_ANCHOR_HIT_CAP) is the anchors'.
+ * CSR output, library-allocated (awry_free_buffer): chains of query i are chains[chain_off[i] .. chain_off[i+1]); the members of
+ * chain c are seeds[seed_off[c] .. seed_off[c+1]), seed_off has chain_off[n] + 1 entries; status[n] is AWRY_Q_OK or
+ * AWRY_Q_SEED_CAP.  All but chain_off_out nullable; seed_off_out and seeds_out are given or omitted together. */
+enum { AWRY_CHAIN_MAX_SEEDS = 4096, AWRY_CHAIN_MAX_LOOKBACK = 64 };
+typedef struct { uint32_t q_begin, q_len; uint64_t t_pos; } awry_seed_t;
+typedef struct { uint32_t score, n_seeds, q_begin, q_end; uint64_t t_begin, t_end; } awry_chain_t;
+int awry_chain_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len, uint64_t max_hits,
+                     uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score,
+                     uint64_t **chain_off_out, awry_chain_t **chains_out, uint64_t **seed_off_out, awry_seed_t **seeds_out,
+                     uint8_t **status_out);
 
 /* releases an array one of the calls above (or awry_locate / awry_read_query_file) returned.  Result arrays are pinned
  * host memory recycled through a process-wide pool (the device writes results straight into them); never pass them to
@@ -539,6 +585,28 @@ int awry_dev_edit_align_tally(awry_index_t *idx, int slot, const uint8_t *d_qbyt
                               const uint32_t *d_hit_query, const uint64_t *d_hit_gpos, const uint8_t *d_hit_edits, uint64_t m,
                               int max_edits, uint32_t *d_text_len, uint8_t *d_n_ops, uint32_t *d_ops, uint64_t *d_tally,
                               void *stream);
+/* Chaining (see awry_chain_batch), device-resident form, for the seeds of any seeder: query q has the seeds d_seeds[d_seed_off[q]
+ * .. d_seed_off[q+1]), in any order (the input index is the last sort key); a seed's t_pos at or past bwt_len counts as a position
+ * of the last record.  The two-call protocol of awry_dev_smems: d_chain_off == NULL is the count pass -> d_n_chains[n] and
+ * d_n_members[n] (u64 each: chains of the query, and seeds in all of them) and optional d_status[n]; awry_dev_scan_counts, twice,
+ * turns them into d_chain_off[n+1] and d_member_off[n+1]; the fill pass writes the chains of query q at d_chains[d_chain_off[q]
+ * ...) and their members, chain after chain (chain c of the query takes the next d_chains[c].n_seeds), at d_members[d_member_off[q]
+ * ...), and never a slot at or beyond the next query's offset (d_n_chains / d_n_members / d_status nullable there).  Each pass
+ * computes the chains anew: nothing is kept between the calls.  A group of lanes owns a query -- a wave of 64, or 16 lanes when
+ * lookback <= 16 (env AWRY_CHAIN_GROUP=64, read per call, takes the wave there too; the results are the same).  No
+ * synchronisation except where the workspace for queries beyond the LDS tile (owned by the replica, per stream, at most 128 MiB)
+ * grows, on first use. */
+int awry_dev_chain_seeds(awry_index_t *idx, int slot, const uint64_t *d_seed_off, const awry_seed_t *d_seeds, uint64_t n,
+                         uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score,
+                         uint64_t *d_n_chains, uint64_t *d_n_members, const uint64_t *d_chain_off, const uint64_t *d_member_off,
+                         awry_chain_t *d_chains, awry_seed_t *d_members, uint8_t *d_status, void *stream);
+/* the same with a work census: d_tally[3] (u64, caller-zeroed) += {seeds chained (of the queries not abandoned), predecessor
+ * pairs evaluated (sum over the seeds of min(sorted index, lookback)), chains reported}; one atomic per query and counter */
+int awry_dev_chain_seeds_tally(awry_index_t *idx, int slot, const uint64_t *d_seed_off, const awry_seed_t *d_seeds, uint64_t n,
+                               uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score,
+                               uint64_t *d_n_chains, uint64_t *d_n_members, const uint64_t *d_chain_off,
+                               const uint64_t *d_member_off, awry_chain_t *d_chains, awry_seed_t *d_members, uint8_t *d_status,
+                               uint64_t *d_tally, void *stream);
 /* test hook of the all-symbol rank primitive: d_occ[i * S + s - 1] = Occ(s, d_rows[i]) for every non-sentinel symbol index s
  * (S = 5 nucleotide, 21 amino; inclusive of the row, as awry_update_range uses it); rows >= bwt_len give zeros */
 int awry_debug_rank_all(awry_index_t *idx, int slot, const void *d_rows, uint64_t n, void *d_occ, void *stream);

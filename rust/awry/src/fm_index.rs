@@ -15,7 +15,7 @@ use std::os::raw::c_char;
 use std::path::{Path, PathBuf};
 use std::sync::Arc;
 
-use awry_hip_sys::{self as sys, awry_anchor_t as RawAnchor};
+use awry_hip_sys::{self as sys, awry_anchor_t as RawAnchor, awry_chain_t as RawChain, awry_seed_t as RawSeed};
 use rayon::iter::{IndexedParallelIterator, IntoParallelIterator, IntoParallelRefIterator, ParallelIterator};
 
 use crate::{
@@ -197,6 +197,35 @@ impl FmBuildArgs {
 struct Csr {
     bytes: Vec<u8>,
     offsets: Vec<u64>,
+}
+
+/// Parameters of [`FmIndex::parallel_chains`] (include/awry_hip.h, awry_chain_batch): `max_seeds` 1..=4096, `lookback` 1..=64,
+/// `max_gap` >= 1, `max_skew` >= 0, `min_score` >= 1.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct ChainParams {
+    pub max_seeds: u32,
+    pub lookback: u32,
+    pub max_gap: u32,
+    pub max_skew: u32,
+    pub min_score: u32,
+}
+
+impl Default for ChainParams {
+    fn default() -> Self {
+        ChainParams { max_seeds: 1024, lookback: 32, max_gap: 1000, max_skew: 100, min_score: 20 }
+    }
+}
+
+/// One chain of [`FmIndex::parallel_chains`]: its score, the spans it covers in query and text, and its seeds `(q_begin, q_len,
+/// t_pos)` first to last.
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct Chain {
+    pub score: u32,
+    pub q_begin: u32,
+    pub q_end: u32,
+    pub t_begin: u64,
+    pub t_end: u64,
+    pub seeds: Vec<(u32, u32, u64)>,
 }
 
 /// The CIGAR string of the runs [`FmIndex::parallel_align_edit`] returns (`len << 4 | op`, BAM's op codes): `"57=1X43="`.
@@ -589,6 +618,60 @@ impl FmIndex {
         unsafe {
             sys::awry_free_buffer(smem_off as *mut std::os::raw::c_void);
             sys::awry_free_buffer(smems as *mut std::os::raw::c_void);
+        }
+        Ok(out)
+    }
+
+    /// Colinear chaining of the located SMEM seeds (no counterpart in the reference; the definition is in include/awry_hip.h): per
+    /// query its chains, the primary chain first, each with its seeds first to last; and per query whether it was abandoned because
+    /// it has more than `params.max_seeds` seeds.
+    pub fn parallel_chains<'a>(
+        &self,
+        queries: impl ParallelIterator<Item = &'a str>,
+        min_len: u32,
+        max_hits: u64,
+        params: ChainParams,
+    ) -> Result<(Vec<Vec<Chain>>, Vec<bool>), AwryError> {
+        let csr = to_csr(queries);
+        let n = csr.offsets.len() - 1;
+        let mut chain_off: *mut u64 = std::ptr::null_mut();
+        let mut chains: *mut RawChain = std::ptr::null_mut();
+        let mut seed_off: *mut u64 = std::ptr::null_mut();
+        let mut seeds: *mut RawSeed = std::ptr::null_mut();
+        let mut st: *mut u8 = std::ptr::null_mut();
+        check(unsafe {
+            sys::awry_chain_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, min_len, max_hits, params.max_seeds, params.lookback,
+                                  params.max_gap, params.max_skew, params.min_score, &mut chain_off, &mut chains, &mut seed_off, &mut seeds, &mut st)
+        })?;
+        let out = unsafe {
+            let off = std::slice::from_raw_parts(chain_off, n + 1);
+            let total = off[n] as usize;
+            let flat: &[RawChain] = if total == 0 { &[] } else { std::slice::from_raw_parts(chains, total) };
+            let soff = std::slice::from_raw_parts(seed_off, total + 1);
+            let members: &[RawSeed] = if soff[total] == 0 { &[] } else { std::slice::from_raw_parts(seeds, soff[total] as usize) };
+            let status: &[u8] = if n == 0 { &[] } else { std::slice::from_raw_parts(st, n) };
+            let per = (0..n)
+                .map(|i| {
+                    (off[i] as usize..off[i + 1] as usize)
+                        .map(|j| Chain {
+                            score: flat[j].score,
+                            q_begin: flat[j].q_begin,
+                            q_end: flat[j].q_end,
+                            t_begin: flat[j].t_begin,
+                            t_end: flat[j].t_end,
+                            seeds: members[soff[j] as usize..soff[j + 1] as usize].iter().map(|m| (m.q_begin, m.q_len, m.t_pos)).collect(),
+                        })
+                        .collect::<Vec<_>>()
+                })
+                .collect::<Vec<_>>();
+            (per, status.iter().map(|&s| s == 8).collect::<Vec<_>>())  // AWRY_Q_SEED_CAP
+        };
+        unsafe {
+            sys::awry_free_buffer(chain_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(chains as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(seed_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(seeds as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(st as *mut std::os::raw::c_void);
         }
         Ok(out)
     }
