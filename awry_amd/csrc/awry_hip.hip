@@ -7,7 +7,6 @@
 #include "host_count.h"
 #include "host_locate.h"
 #include "mismatch_host.h"
-#include "pattern_host.h"
 #include "anchor_host.h"
 #include "chain_host.h"
 #include "edit_host.h"
@@ -341,13 +340,13 @@ void awry_free_buffer(void* p) { release_result(p); }
 
 int awry_count_mismatch_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_mismatches,
                               uint64_t* counts_out) {
-  return guarded([&] { count_leaves_batch(idx, qbytes, qoff, n, max_mismatches, counts_out, launch_count_mismatch); });
+  return guarded([&] { count_leaves_batch(idx, qbytes, qoff, n, max_mismatches, counts_out, false); });
 }
 
 int awry_locate_mismatch_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_mismatches,
                                uint64_t** hit_off_out, awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** mismatches_out) {
   return guarded([&] {
-    locate_leaves_batch(idx, qbytes, qoff, n, max_mismatches, hit_off_out, hits_out, global_pos_out, mismatches_out, launch_count_mismatch);
+    locate_leaves_batch(idx, qbytes, qoff, n, max_mismatches, hit_off_out, hits_out, global_pos_out, mismatches_out, false);
   });
 }
 
@@ -357,13 +356,13 @@ uint32_t awry_pattern_class(int alphabet, uint8_t ascii) {
 
 int awry_count_pattern_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_mismatches,
                              uint64_t* counts_out) {
-  return guarded([&] { count_pattern_batch(idx, qbytes, qoff, n, max_mismatches, counts_out); });
+  return guarded([&] { count_leaves_batch(idx, qbytes, qoff, n, max_mismatches, counts_out, true); });
 }
 
 int awry_locate_pattern_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_mismatches,
                               uint64_t** hit_off_out, awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** mismatches_out) {
   return guarded([&] {
-    locate_pattern_batch(idx, qbytes, qoff, n, max_mismatches, hit_off_out, hits_out, global_pos_out, mismatches_out);
+    locate_leaves_batch(idx, qbytes, qoff, n, max_mismatches, hit_off_out, hits_out, global_pos_out, mismatches_out, true);
   });
 }
 
@@ -837,13 +836,7 @@ int awry_dev_count_mismatch(awry_index_t* idx, int slot, const void* d_qbytes, c
 
 int awry_dev_count_mismatch_tally(awry_index_t* idx, int slot, const void* d_qbytes, const void* d_qoff, uint64_t n, int max_mismatches,
                                   void* d_counts, void* d_status, void* d_tally, void* stream) {
-  return guarded([&] {
-    require_mismatches(max_mismatches);
-    Replica& r = replica(idx, slot);
-    require(n == 0 || (d_qbytes && d_qoff && d_counts), "null argument");
-    launch_count_mismatch(r, (const uint8_t*)d_qbytes, (const uint64_t*)d_qoff, n, max_mismatches, (uint64_t*)d_counts, nullptr, nullptr,
-                          (uint8_t*)d_status, (hipStream_t)stream, (unsigned long long*)d_tally);
-  });
+  return guarded([&] { dev_count_leaves(idx, slot, false, d_qbytes, d_qoff, n, max_mismatches, d_counts, d_status, d_tally, stream); });
 }
 
 int awry_dev_count_pattern(awry_index_t* idx, int slot, const void* d_qbytes, const void* d_qoff, uint64_t n, int max_mismatches,
@@ -853,13 +846,7 @@ int awry_dev_count_pattern(awry_index_t* idx, int slot, const void* d_qbytes, co
 
 int awry_dev_count_pattern_tally(awry_index_t* idx, int slot, const void* d_qbytes, const void* d_qoff, uint64_t n, int max_mismatches,
                                  void* d_counts, void* d_status, void* d_tally, void* stream) {
-  return guarded([&] {
-    require_mismatches(max_mismatches);
-    Replica& r = replica(idx, slot);
-    require(n == 0 || (d_qbytes && d_qoff && d_counts), "null argument");
-    launch_count_pattern(r, (const uint8_t*)d_qbytes, (const uint64_t*)d_qoff, n, max_mismatches, (uint64_t*)d_counts, nullptr, nullptr,
-                         (uint8_t*)d_status, (hipStream_t)stream, (unsigned long long*)d_tally);
-  });
+  return guarded([&] { dev_count_leaves(idx, slot, true, d_qbytes, d_qoff, n, max_mismatches, d_counts, d_status, d_tally, stream); });
 }
 
 int awry_dev_anchors(awry_index_t* idx, int slot, const void* d_qbytes, const void* d_qoff, uint64_t n, uint32_t min_len, int skip,

@@ -22,6 +22,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -34,7 +35,6 @@
 #include "host_pack.h"
 #include "kernels.hip.h"
 #include "mismatch_kernels.hip.h"
-#include "pattern_kernels.hip.h"
 #include "sais.hpp"
 
 using namespace awry;

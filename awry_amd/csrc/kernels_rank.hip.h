@@ -100,7 +100,7 @@ __device__ __forceinline__ uint64_t sa_sample(const DevIndex& ix, uint64_t sampl
 
 // status of a query (counts' companion array): != Q_OK marks inputs the reference leaves undefined
 enum : uint8_t { Q_OK = 0, Q_EMPTY = 1, Q_SENTINEL = 2, Q_NON_ASCII = 3,
-                 // class patterns only (pattern_kernels.hip.h): a byte that is no class letter, more class positions than
+                 // class patterns only (mismatch_kernels.hip.h, CLASSES): a byte that is no class letter, more class positions than
                  // AWRY_MAX_CLASS_POSITIONS, a search abandoned at the expansion cap
                  Q_NOT_CLASS_LETTER = 4, Q_CLASS_POSITIONS = 5, Q_EXPANSION_CAP = 6 };
 

@@ -392,25 +392,6 @@ void launch_count_ascii_uniform(Replica& r, const uint8_t* d_q, uint64_t n, uint
   launch_aa_two_phase(r, d_q, nullptr, n, (int)L, d_counts, d_ranges, d_status, s, d_tally);
 }
 
-// the DFS kernel on a resident grid (lanes draw queries from the work-queue head).  EMIT: the locate pass that writes the
-// leaves of query q to key / val [leaf_off[q], leaf_off[q + 1])
-void launch_count_mismatch(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, int k, uint64_t* d_counts, uint64_t* d_totals,
-                           uint64_t* d_nleaves, uint8_t* d_status, hipStream_t s, unsigned long long* d_tally = nullptr,
-                           const uint64_t* d_leaf_off = nullptr, uint64_t* d_key = nullptr, uint64_t* d_val = nullptr) {
-  if (n == 0) return;
-  unsigned long long* ctr = next_counter(r, s);
-  const bool emit = d_leaf_off != nullptr;
-  const uint64_t want = (n + 255) / 256;
-  with_alphabet(r.dev.alphabet, [&](auto A) {
-    with_flags(emit, [&](auto E) {
-      auto kernel = count_mismatch_kernel<decltype(A)::value, E()>;  // (A is a capture here: its type names the value)
-      const dim3 g((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, resident_grid(r, kernel)))), b(256);
-      hipLaunchKernelGGL(kernel, g, b, 0, s, r.dev, d_q, d_off, n, k, d_counts, d_totals, d_nleaves, d_status, d_leaf_off, d_key, d_val, ctr, d_tally);
-    });
-  });
-  HIP_CHECK(hipGetLastError());
-}
-
 // Expansions (rank_all pairs) one pattern may take before its search is abandoned with Q_EXPANSION_CAP.  A safety bound for
 // a shared card (DESIGN.md 5d has its basis).  Read per call: AWRY_PATTERN_MAX_EXPANSIONS (tests shrink it).
 uint64_t pattern_max_expansions() {
@@ -419,28 +400,35 @@ uint64_t pattern_max_expansions() {
   return v ? v : (uint64_t)AWRY_PATTERN_DEFAULT_MAX_EXPANSIONS;
 }
 
-// the class-pattern DFS kernel (pattern_kernels.hip.h) on a resident grid; arguments as launch_count_mismatch.  The frames a
-// lane cannot keep in registers live in the stream's scratch, sized to the grid.
-void launch_count_pattern(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, int k, uint64_t* d_counts, uint64_t* d_totals,
-                          uint64_t* d_nleaves, uint8_t* d_status, hipStream_t s, unsigned long long* d_tally = nullptr,
-                          const uint64_t* d_leaf_off = nullptr, uint64_t* d_key = nullptr, uint64_t* d_val = nullptr) {
+// the DFS kernel (mismatch_kernels.hip.h) on a resident grid (lanes draw queries from the work-queue head).  classes: the
+// queries are class patterns; the frames a lane cannot keep in registers then live in the stream's scratch, sized to the
+// grid, and the expansion cap applies -- the letter mode has neither.  EMIT: the locate pass that writes the leaves of query
+// q to key / val [leaf_off[q], leaf_off[q + 1])
+void launch_count_leaves(Replica& r, bool classes, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, int k, uint64_t* d_counts,
+                         uint64_t* d_totals, uint64_t* d_nleaves, uint8_t* d_status, hipStream_t s, unsigned long long* d_tally = nullptr,
+                         const uint64_t* d_leaf_off = nullptr, uint64_t* d_key = nullptr, uint64_t* d_val = nullptr) {
   if (n == 0) return;
-  const ScratchLock scratch_lock(r, s);
-  Replica::SurvScratch* sc = surv_scratch(r, s);
+  std::optional<ScratchLock> scratch_lock;  // the workspace is the class mode's: the letter mode touches no scratch
+  if (classes) scratch_lock.emplace(r, s);
   unsigned long long* ctr = next_counter(r, s);
   const bool emit = d_leaf_off != nullptr;
-  const uint64_t want = (n + 255) / 256, max_exp = pattern_max_expansions();
+  const uint64_t want = (n + 255) / 256, max_exp = classes ? pattern_max_expansions() : 0;
   with_alphabet(r.dev.alphabet, [&](auto A) {
-    with_flags(emit, [&](auto E) {
-      auto kernel = count_pattern_kernel<decltype(A)::value, E()>;
+    with_flags(classes, emit, [&](auto C, auto E) {
+      auto kernel = count_dfs_kernel<decltype(A)::value, C(), E()>;  // (A is a capture here: its type names the value)
       const dim3 g((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, resident_grid(r, kernel)))), b(256);
-      const size_t need = (size_t)PT_WS_WORDS * g.x * b.x;
-      if (sc->pat_stack.n < need) {
-        HIP_CHECK(hipStreamSynchronize(s));
-        sc->pat_stack.alloc(need);
+      uint64_t* ws = nullptr;
+      if (C()) {
+        Replica::SurvScratch* sc = surv_scratch(r, s);
+        const size_t need = (size_t)PT_WS_WORDS * g.x * b.x;
+        if (sc->pat_stack.n < need) {
+          HIP_CHECK(hipStreamSynchronize(s));
+          sc->pat_stack.alloc(need);
+        }
+        ws = sc->pat_stack.p;
       }
-      hipLaunchKernelGGL(kernel, g, b, 0, s, r.dev, d_q, d_off, n, k, max_exp, d_counts, d_totals, d_nleaves, d_status, d_leaf_off, d_key, d_val,
-                         sc->pat_stack.p, ctr, d_tally);
+      hipLaunchKernelGGL(kernel, g, b, 0, s, r.dev, d_q, d_off, n, k, max_exp, d_counts, d_totals, d_nleaves, d_status, d_leaf_off, d_key, d_val, ws,
+                         ctr, d_tally);
     });
   });
   HIP_CHECK(hipGetLastError());

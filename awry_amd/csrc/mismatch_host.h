@@ -1,10 +1,18 @@
-// mismatch_host.h -- shard drivers of the substitution-tolerant count and locate
+// mismatch_host.h -- shard drivers of the substitution-tolerant and class-pattern count and locate
 // A part of awry_hip.hip (one translation unit): included there, in order, and not on its own.
 #pragma once
 
 namespace {
 
-// ---- substitution-tolerant count / locate (mismatch_kernels.hip.h) ----------------------------------------
+// ---- substitution-tolerant and class-pattern count / locate (mismatch_kernels.hip.h) ----------------------
+// `classes` selects the kernel's mode (launch_count_leaves); everything after the leaves is shared: chunking, the leaf cap,
+// segmented sort by first row, launch_locate, per-hit distance.  Queries are validated where they are searched (lane refill
+// of the kernel), and a rejected or abandoned one fails the batch through its status byte, before any result array is handed out.
+
+static_assert(PT_MAX_CLASS == AWRY_MAX_CLASS_POSITIONS && PT_MAX_FRAMES == AWRY_PATTERN_MAX_FRAMES && MM_MAX_K == AWRY_MAX_MISMATCHES,
+              "the kernel's limits are the header's");
+static_assert(Q_NOT_CLASS_LETTER == AWRY_Q_NOT_CLASS_LETTER && Q_CLASS_POSITIONS == AWRY_Q_CLASS_POSITIONS && Q_EXPANSION_CAP == AWRY_Q_EXPANSION_CAP,
+              "the kernel's status bytes are the header's");
 
 void require_mismatches(int k) {
   if (k < 0 || k > MM_MAX_K) throw ArgError("max_mismatches must be 0, 1 or 2");
@@ -26,18 +34,14 @@ void upload_chunk(Replica& r, ChunkBuffers& cb, const uint8_t* qbytes, const uin
   cb.h_status.resize(n);
 }
 
-// the launch that produces the leaves of a chunk (launch_count_mismatch, or launch_count_pattern with the same arguments)
-using LeafLaunch = void (*)(Replica&, const uint8_t*, const uint64_t*, uint64_t, int, uint64_t*, uint64_t*, uint64_t*, uint8_t*, hipStream_t,
-                            unsigned long long*, const uint64_t*, uint64_t*, uint64_t*);
-
-void count_mismatch_shard(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard sh, int k, uint64_t* counts_out, LeafLaunch launch_leaves) {
+void count_mismatch_shard(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard sh, int k, uint64_t* counts_out, bool classes) {
   HIP_CHECK(hipSetDevice(r.device));
   ChunkBuffers cb;
   for (Shard c : chunk_queries(qoff, sh.lo, sh.hi)) {
     const uint64_t n = c.hi - c.lo, w = (uint64_t)(k + 1);
     upload_chunk(r, cb, qbytes, qoff, c);
     if (cb.counts.n < n * w) cb.counts.alloc(n * w);
-    launch_leaves(r, cb.q.p, cb.off.p, n, k, cb.counts.p, nullptr, nullptr, cb.status.p, r.stream, nullptr, nullptr, nullptr, nullptr);
+    launch_count_leaves(r, classes, cb.q.p, cb.off.p, n, k, cb.counts.p, nullptr, nullptr, cb.status.p, r.stream, nullptr, nullptr, nullptr, nullptr);
     HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, r.stream));
     HIP_CHECK(hipMemcpyAsync(counts_out + c.lo * w, cb.counts.p, n * w * 8, hipMemcpyDeviceToHost, r.stream));
     HIP_CHECK(hipStreamSynchronize(r.stream));
@@ -63,13 +67,13 @@ struct MismatchHits {  // one shard's locate result, in query order
 // pass 1 (counts, leaves per query), scans, pass 2 (leaves), segmented sort by first row within each query, locate over the
 // flat leaf list, distances per hit.  false: the chunk holds more leaves than the cap and more than one query -- nothing appended
 bool locate_mismatch_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, bool want_pos, bool want_gpos, bool want_mm,
-                           MismatchHits& out, LeafLaunch launch_leaves) {
+                           MismatchHits& out, bool classes) {
   const hipStream_t s = r.stream;
   const uint64_t n = c.hi - c.lo;
   ChunkBuffers cb;
   upload_chunk(r, cb, qbytes, qoff, c);
   DevBuf<uint64_t> totals(n), nleaves(n), hit_off(n + 1), leaf_off(n + 1), scratch(scan_tiles(n) + 1);
-  launch_leaves(r, cb.q.p, cb.off.p, n, k, nullptr, totals.p, nleaves.p, cb.status.p, s, nullptr, nullptr, nullptr, nullptr);
+  launch_count_leaves(r, classes, cb.q.p, cb.off.p, n, k, nullptr, totals.p, nleaves.p, cb.status.p, s, nullptr, nullptr, nullptr, nullptr);
   launch_scan(r, totals.p, n, hit_off.p, scratch.p, s);
   uint64_t total = 0, nleaf = 0;
   HIP_CHECK(hipMemcpyAsync(&total, hit_off.p + n, 8, hipMemcpyDeviceToHost, s));
@@ -85,7 +89,7 @@ bool locate_mismatch_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qo
   HIP_CHECK(hipMemcpyAsync(out.counts.data() + at_q, totals.p, n * 8, hipMemcpyDeviceToHost, s));
   if (total) {
     DevBuf<uint64_t> key(nleaf), val(nleaf), key2(nleaf), val2(nleaf), width(nleaf), leaf_hit_off(nleaf + 1), lscratch(scan_tiles(nleaf) + 1);
-    launch_leaves(r, cb.q.p, cb.off.p, n, k, nullptr, nullptr, nullptr, nullptr, s, nullptr, leaf_off.p, key.p, val.p);
+    launch_count_leaves(r, classes, cb.q.p, cb.off.p, n, k, nullptr, nullptr, nullptr, nullptr, s, nullptr, leaf_off.p, key.p, val.p);
     // DFS from the right end does not visit the leaves in row order: sort each query's leaves by their first row
     unsigned end_bit = 1;
     while (end_bit < 64 && (r.dev.bwt_len >> end_bit)) end_bit++;
@@ -114,24 +118,24 @@ bool locate_mismatch_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qo
 }
 
 void locate_mismatch_range(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, bool want_pos, bool want_gpos, bool want_mm,
-                           MismatchHits& out, LeafLaunch launch_leaves) {
+                           MismatchHits& out, bool classes) {
   if (c.hi <= c.lo) return;
-  if (locate_mismatch_chunk(r, qbytes, qoff, c, k, want_pos, want_gpos, want_mm, out, launch_leaves)) return;
+  if (locate_mismatch_chunk(r, qbytes, qoff, c, k, want_pos, want_gpos, want_mm, out, classes)) return;
   const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order
-  locate_mismatch_range(r, qbytes, qoff, Shard{c.lo, mid}, k, want_pos, want_gpos, want_mm, out, launch_leaves);
-  locate_mismatch_range(r, qbytes, qoff, Shard{mid, c.hi}, k, want_pos, want_gpos, want_mm, out, launch_leaves);
+  locate_mismatch_range(r, qbytes, qoff, Shard{c.lo, mid}, k, want_pos, want_gpos, want_mm, out, classes);
+  locate_mismatch_range(r, qbytes, qoff, Shard{mid, c.hi}, k, want_pos, want_gpos, want_mm, out, classes);
 }
 
-// the host batch drivers of both leaf-producing kernels (awry_count_mismatch_batch / awry_count_pattern_batch, and the locate pair)
-void count_leaves_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int k, uint64_t* counts_out, LeafLaunch launch_leaves) {
+// the host batch drivers of both modes (awry_count_mismatch_batch / awry_count_pattern_batch, and the locate pair)
+void count_leaves_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int k, uint64_t* counts_out, bool classes) {
   require(idx && qoff && (counts_out || n == 0), "null argument");
   require(qbytes || qoff[n] == qoff[0], "null query bytes");
   require_mismatches(k);
-  for_each_replica(idx, n, [&](Replica& r, Shard sh, int) { count_mismatch_shard(r, qbytes, qoff, sh, k, counts_out, launch_leaves); });
+  for_each_replica(idx, n, [&](Replica& r, Shard sh, int) { count_mismatch_shard(r, qbytes, qoff, sh, k, counts_out, classes); });
 }
 
 void locate_leaves_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int k, uint64_t** hit_off_out,
-                         awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** mismatches_out, LeafLaunch launch_leaves) {
+                         awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** mismatches_out, bool classes) {
   require(idx && qoff && hit_off_out, "null argument");
   require(qbytes || qoff[n] == qoff[0], "null query bytes");
   require_mismatches(k);
@@ -139,7 +143,7 @@ void locate_leaves_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t*
   for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
     HIP_CHECK(hipSetDevice(r.device));
     for (Shard c : chunk_queries(qoff, sh.lo, sh.hi))
-      locate_mismatch_range(r, qbytes, qoff, c, k, hits_out != nullptr, global_pos_out != nullptr, mismatches_out != nullptr, res[g], launch_leaves);
+      locate_mismatch_range(r, qbytes, qoff, c, k, hits_out != nullptr, global_pos_out != nullptr, mismatches_out != nullptr, res[g], classes);
   });
   // shards are contiguous in query order: the result arrays are their concatenation
   MBuf<uint64_t> off, gp;
@@ -166,6 +170,16 @@ void locate_leaves_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t*
   if (hits_out) *hits_out = hits.release();
   if (global_pos_out) *global_pos_out = gp.release();
   if (mismatches_out) *mismatches_out = mm.release();
+}
+
+// the device-resident count of both modes (awry_dev_count_mismatch_tally / awry_dev_count_pattern_tally)
+void dev_count_leaves(awry_index* idx, int slot, bool classes, const void* d_qbytes, const void* d_qoff, uint64_t n, int k, void* d_counts,
+                      void* d_status, void* d_tally, void* stream) {
+  require_mismatches(k);
+  Replica& r = replica(idx, slot);
+  require(n == 0 || (d_qbytes && d_qoff && d_counts), "null argument");
+  launch_count_leaves(r, classes, (const uint8_t*)d_qbytes, (const uint64_t*)d_qoff, n, k, (uint64_t*)d_counts, nullptr, nullptr, (uint8_t*)d_status,
+                      (hipStream_t)stream, (unsigned long long*)d_tally);
 }
 
 }  // namespace

@@ -126,7 +126,7 @@ struct Replica {
     DevBuf<uint64_t> u_words;
     DevBuf<uint32_t> u_list;
     DevBuf<unsigned long long> u_bad;
-    // count_pattern_kernel: the DFS frames below the two a lane keeps in registers, [level][field][grid lane]
+    // count_dfs_kernel<CLASSES>: the DFS frames below the two a lane keeps in registers, [level][field][grid lane]
     DevBuf<uint64_t> pat_stack;
     // edit_scan_kernel: the pattern masks edit_masks_kernel writes in front of it, per query or per window
     DevBuf<uint64_t> edit_masks;

@@ -1,4 +1,4 @@
-"""Class-pattern count and locate on the GPU (awry_amd/csrc/pattern_kernels.hip.h) against tests/pattern_ref.py: the
+"""Class-pattern count and locate on the GPU (the class mode of awry_amd/csrc/mismatch_kernels.hip.h) against tests/pattern_ref.py: the
 brute-force definition (counts, positions, distances), the oracle's locate lists of the matched strings (order), the existing
 exact and mismatch paths (plain-letter patterns, bit for bit), the stack bound (a planted text that fills all 18 frames), the
 expansion cap, and independence of accelerators, SA ratio, replicas, row width, leaf capacity, lane refill and streams."""

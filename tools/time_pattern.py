@@ -1,8 +1,8 @@
-"""Rates of class-pattern count (awry_dev_count_pattern, pattern_kernels.hip.h) on the repeat-rich GRCh38-shaped text
+"""Rates of class-pattern count (awry_dev_count_pattern, the class mode of mismatch_kernels.hip.h) on the repeat-rich GRCh38-shaped text
 (tests/synth.repeat_rich_text, as bench.py) with the patterns resident in HBM; device events, warmed launches.
 
 Yardstick legs: plain-letter 31-mers and 101-bp reads at k = 0, 1, 2 through awry_dev_count_pattern and through
-awry_dev_count_mismatch (the existing kernel) on the same queries in the same run, 7 timings each: median, min..max, and the
+awry_dev_count_mismatch (the letter mode of the same kernel) on the same queries in the same run, 7 timings each: median, min..max, and the
 ratio of the medians beside the yardstick's own spread.
 Pattern legs: 23-mers "20 nt + NGG" at k = 0, 1, 2 and sampled 31-mers with 1, 2, 4 class positions at k = 0: patterns/s and
 expansions per pattern (the kernel's census).
@@ -24,7 +24,7 @@ from tests import pattern_ref, synth
 
 n = int(float(sys.argv[1])) if len(sys.argv) > 1 else 3_100_000_000
 nq = int(float(sys.argv[2])) if len(sys.argv) > 2 else 1_000_000
-lanes_per_cu = int(sys.argv[3]) if len(sys.argv) > 3 else 1024  # count_pattern_kernel<NUCLEOTIDE, false>: 4 waves per SIMD
+lanes_per_cu = int(sys.argv[3]) if len(sys.argv) > 3 else 1024  # count_dfs_kernel<NUCLEOTIDE, true, false>: 4 waves per SIMD
 REPS = 7
 CAP_PROBE = 1 << 14
 dev = torch.device("cuda", 0)
@@ -111,7 +111,7 @@ def main():
             want = counts[:nq * (k + 1)].clone().view(nq, k + 1)
             ms = timings(lambda: ix.dev_count_pattern(flat.data_ptr(), off.data_ptr(), nq, k, counts.data_ptr(), status.data_ptr(), stream, 0))
             leg["pattern"] = dict(summary(ms), queries_per_s=nq / (float(np.median(ms)) * 1e-3))
-            ok = status[:nq] == 0  # (a search abandoned at the expansion cap has counts 0: the existing kernel has no cap)
+            ok = status[:nq] == 0  # (a search abandoned at the expansion cap has counts 0: the letter mode has no cap)
             assert int((status[:nq] != 0).sum()) == int((status[:nq] == 6).sum())
             assert torch.equal(counts[:nq * (k + 1)].view(nq, k + 1)[ok], want[ok]), "the two kernels disagree"
             leg["abandoned_at_the_expansion_cap"] = int((~ok).sum())
