@@ -26,6 +26,10 @@ class Anchor(C.Structure):  # awry_anchor_t
     _fields_ = [("q_begin", C.c_uint32), ("q_len", C.c_uint32), ("start_row", C.c_uint64), ("count", C.c_uint64)]
 
 
+class Aln(C.Structure):  # awry_aln_t
+    _fields_ = [("t_begin", C.c_uint64), ("t_end", C.c_uint64), ("edits", C.c_uint32), ("status", C.c_uint32)]
+
+
 class Seed(C.Structure):  # awry_seed_t
     _fields_ = [("q_begin", C.c_uint32), ("q_len", C.c_uint32), ("t_pos", C.c_uint64)]
 
@@ -125,6 +129,10 @@ def load_library():
         C.POINTER(C.POINTER(Seed)), C.POINTER(u8p))
     sig("awry_dev_chain_seeds", i32, vp, i32, vp, vp, u64, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp)
     sig("awry_dev_chain_seeds_tally", i32, vp, i32, vp, vp, u64, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp)
+    sig("awry_align_chains_batch", i32, vp, vp, u64p, u64, u32, u64, u32, u32, u32, u32, u32, u64, u32, C.POINTER(u64p), C.POINTER(C.POINTER(Chain)),
+        C.POINTER(C.POINTER(Aln)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)), C.POINTER(u8p))
+    sig("awry_dev_align_chains", i32, vp, i32, vp, vp, vp, vp, vp, u64, u32, vp, vp, vp, vp, vp)
+    sig("awry_dev_align_chains_tally", i32, vp, i32, vp, vp, vp, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp)
     sig("awry_locate_edit_batch", i32, vp, vp, u64p, u64, i32, u64, C.POINTER(u64p), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(u8p),
         C.POINTER(u8p))
     sig("awry_dev_edit_windows", i32, vp, i32, vp, vp, vp, vp, vp, u64, i32, vp, vp, vp, vp, vp)

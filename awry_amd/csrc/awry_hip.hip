@@ -10,6 +10,7 @@
 #include "anchor_host.h"
 #include "chain_host.h"
 #include "edit_host.h"
+#include "chain_align_host.h"
 #include "prewarm.h"
 
 namespace {
@@ -421,6 +422,23 @@ int awry_chain_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* q
     const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
     require((seed_off_out == nullptr) == (seeds_out == nullptr), "seed_off_out and seeds_out are given or omitted together");
     chain_batch(idx, qbytes, qoff, n, min_len, max_hits, P, chain_off_out, chains_out, seed_off_out, seeds_out, status_out);
+  });
+}
+
+int awry_align_chains_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits,
+                            uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score, uint64_t max_alignments,
+                            uint32_t band, uint64_t** aln_off_out, awry_chain_t** chains_out, awry_aln_t** alns_out, uint64_t** cigar_off_out,
+                            uint32_t** cigar_out, uint8_t** status_out) {
+  return guarded([&] {
+    require(idx && qoff && aln_off_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_smem_args(min_len);
+    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
+    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    require_chain_align_args(max_alignments, band);
+    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
+    align_chains_batch(idx, qbytes, qoff, n, min_len, max_hits, P, max_alignments, band, aln_off_out, chains_out, alns_out, cigar_off_out, cigar_out,
+                       status_out);
   });
 }
 
@@ -939,6 +957,26 @@ int awry_dev_chain_seeds_tally(awry_index_t* idx, int slot, const uint64_t* d_se
     require(n == 0 || (d_seed_off && (d_chain_off ? d_member_off && d_chains && d_members : d_n_chains && d_n_members)), "null device pointer");
     launch_chain(r, d_seed_off, reinterpret_cast<const Seed*>(d_seeds), n, P, d_n_chains, d_n_members, d_chain_off, d_member_off,
                  reinterpret_cast<Chain*>(d_chains), reinterpret_cast<Seed*>(d_members), d_status, (hipStream_t)stream, (unsigned long long*)d_tally);
+  });
+}
+
+int awry_dev_align_chains(awry_index_t* idx, int slot, const uint8_t* d_qbytes, const uint64_t* d_qoff, const uint32_t* d_chain_query,
+                          const uint64_t* d_member_off, const awry_seed_t* d_members, uint64_t m, uint32_t band, awry_aln_t* d_alns, uint64_t* d_n_ops,
+                          const uint64_t* d_cigar_off, uint32_t* d_cigar, void* stream) {
+  return awry_dev_align_chains_tally(idx, slot, d_qbytes, d_qoff, d_chain_query, d_member_off, d_members, m, band, d_alns, d_n_ops, d_cigar_off, d_cigar,
+                                     nullptr, stream);
+}
+
+int awry_dev_align_chains_tally(awry_index_t* idx, int slot, const uint8_t* d_qbytes, const uint64_t* d_qoff, const uint32_t* d_chain_query,
+                                const uint64_t* d_member_off, const awry_seed_t* d_members, uint64_t m, uint32_t band, awry_aln_t* d_alns,
+                                uint64_t* d_n_ops, const uint64_t* d_cigar_off, uint32_t* d_cigar, uint64_t* d_tally, void* stream) {
+  return guarded([&] {
+    require_chain_align_args(1, band);
+    Replica& r = replica(idx, slot);
+    require(m == 0 || (d_qbytes && d_qoff && d_chain_query && d_member_off && d_members && (d_cigar_off ? d_cigar != nullptr : d_alns && d_n_ops)),
+            "null device pointer");
+    launch_chain_align(r, edit_text(r), d_qbytes, d_qoff, d_chain_query, d_member_off, reinterpret_cast<const Seed*>(d_members), m, (int)band,
+                       CHAIN_ALIGN_MAX_LEN, reinterpret_cast<Aln*>(d_alns), d_n_ops, d_cigar_off, d_cigar, (hipStream_t)stream, (unsigned long long*)d_tally);
   });
 }
 

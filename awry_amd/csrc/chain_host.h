@@ -33,6 +33,18 @@ struct ChainHits {  // one shard's result, in query order
   std::vector<awry_seed_t> members;
 };
 
+// what a chunk's fill pass leaves on the device, for a driver that goes on there (chain_align_host.h) instead of copying it out
+struct ChainOnDevice {
+  const ChunkBuffers& cb;  // the chunk's queries
+  Shard c;
+  const uint64_t *n_chains, *chain_off, *member_off;  // per query
+  const Chain* chains;
+  const Seed* members;
+  uint64_t nchains, nmembers;
+  const uint8_t* status;  // per query: Q_OK or Q_SEED_CAP
+};
+using ChainSink = std::function<void(Replica&, const ChainOnDevice&)>;  // returns with the stream synchronised
+
 template <class K, class... Args>
 void chain_launch(Replica& r, hipStream_t s, uint64_t items, K kernel, Args... args) {
   hipLaunchKernelGGL(kernel, dim3(grid_for(r, items, 256)), dim3(256), 0, s, args...);
@@ -41,9 +53,10 @@ void chain_launch(Replica& r, hipStream_t s, uint64_t items, K kernel, Args... a
 
 // SMEM count pass, scan, fill pass, ranges, scan of the located counts and locate (anchor_chunk's flow, text positions only); then
 // one seed per located hit, the chain count pass, the scans of chains and members, the fill pass.  false: the chunk's located
-// hits exceed the capacity and it holds more than one query -- nothing appended
+// hits exceed the capacity and it holds more than one query -- nothing appended.  With a sink, the chunk's chains and members go
+// to it, on the device, and nothing is appended to `out`.
 bool chain_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, uint32_t min_len, uint64_t max_hits, const ChainParams& P,
-                 bool want_members, ChainHits& out) {
+                 bool want_members, ChainHits& out, const ChainSink* sink = nullptr) {
   const hipStream_t s = r.stream;
   const uint64_t n = c.hi - c.lo;
   for (uint64_t i = c.lo; i < c.hi; i++)
@@ -94,6 +107,10 @@ bool chain_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard 
   DevBuf<Chain> d_chains(std::max<uint64_t>(nchains, 1));
   DevBuf<Seed> d_members(std::max<uint64_t>(nmembers, 1));
   if (nchains) launch_chain(r, soff.p, seeds.p, n, P, nullptr, nullptr, choff.p, moff.p, d_chains.p, d_members.p, nullptr, s);
+  if (sink) {
+    (*sink)(r, ChainOnDevice{cb, c, nch.p, choff.p, moff.p, d_chains.p, d_members.p, nchains, nmembers, status.p});
+    return true;
+  }
   const size_t at_q = out.n_chains.size(), at_c = out.chains.size(), at_m = out.members.size();
   out.n_chains.resize(at_q + n);
   out.status.resize(at_q + n);
@@ -110,12 +127,12 @@ bool chain_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard 
 }
 
 void chain_range(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, uint32_t min_len, uint64_t max_hits, const ChainParams& P,
-                 bool want_members, ChainHits& out) {
+                 bool want_members, ChainHits& out, const ChainSink* sink = nullptr) {
   if (c.hi <= c.lo) return;
-  if (chain_chunk(r, qbytes, qoff, c, min_len, max_hits, P, want_members, out)) return;
+  if (chain_chunk(r, qbytes, qoff, c, min_len, max_hits, P, want_members, out, sink)) return;
   const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order
-  chain_range(r, qbytes, qoff, Shard{c.lo, mid}, min_len, max_hits, P, want_members, out);
-  chain_range(r, qbytes, qoff, Shard{mid, c.hi}, min_len, max_hits, P, want_members, out);
+  chain_range(r, qbytes, qoff, Shard{c.lo, mid}, min_len, max_hits, P, want_members, out, sink);
+  chain_range(r, qbytes, qoff, Shard{mid, c.hi}, min_len, max_hits, P, want_members, out, sink);
 }
 
 // awry_chain_batch: shards over the replicas, results stitched in query order into pinned-pool arrays.  The out-pointers are

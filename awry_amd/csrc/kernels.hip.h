@@ -45,6 +45,10 @@
 //                                                            lanes, lane l on predecessor i - 1 - l, DPP maximum: count pass, two scans, fill
 //                                                            pass [kernels_chain]
 //                         + chain_expand / chain_seed_off kernels: located SMEM records -> seeds and per-query seed offsets [kernels_chain]
+//   align chains          CHAIN_ALIGN_KERNEL<A, NBMAX, FILL> pieces as diagonal runs, banded tables (NBMAX = 9, 17, 33 cells in registers) for the
+//                                                            extensions and gaps, one CIGAR per chain; one chain per lane over a class list, two
+//                                                            passes [kernels_chain_align]
+//                         + chain_align_classify / take / select / gather kernels: class lists, and the first chains of each query [kernels_chain_align]
 //   count, wide rows      count_nt2_wide_kernel, count_nt2_wide_probe_kernel   64-bit rows [kernels_wide]
 //   locate                LOCATE_TILE_KERNEL<A>              hit -> row, sampled / verified hits finished [this file]
 //                         + LOCATE_WALK_NT_LANE_KERNEL       LF walks of the rest, one hit per lane, whole block per step [this file]
@@ -565,3 +569,4 @@ __global__ __launch_bounds__(256) void locate_walk_nt_lane_kernel(DevIndex ix, u
 #include "edit_kernels.hip.h"      // localise, backstep_scalar, symbol_at, ByteStream
 #include "kernels_align.hip.h"     // edit_symbols, edit_owner, ByteStream
 #include "kernels_chain.hip.h"     // localise, tally_add, Anchor
+#include "kernels_chain_align.hip.h"  // Seed, Chain, ByteStream, edit_symbols, align_bam_op

@@ -580,6 +580,64 @@ void launch_chain(Replica& r, const uint64_t* d_seed_off, const Seed* d_seeds, u
   HIP_CHECK(hipGetLastError());
 }
 
+// Chain alignment (kernels_chain_align.hip.h) over m chains.  d_cigar_off == nullptr: the count pass (d_alns, d_n_ops); else the
+// fill pass.  Each pass classifies the chains anew (class lists in the stream's scratch: 3 m + 3 words) and runs the three
+// instantiations one after the other, each over its list; a launch whose list is empty ends at once.  The direction words live
+// in the stream's align_trace, max_rows (the longest query the launch takes) * 4, 8 or 16 bytes per grid lane: the grid of each
+// class is cut so that they stay within CHAIN_ALIGN_TRACE_BYTES (at 1024 rows: 512, 256 and 128 blocks of 256 lanes; at the 101 rows
+// of a short-read batch the whole grid), and the scratch grows to what the launch needs, not to the bound.
+constexpr size_t CHAIN_ALIGN_TRACE_BYTES = 512u << 20;
+void launch_chain_align(Replica& r, const uint8_t* text8, const uint8_t* d_q, const uint64_t* d_off, const uint32_t* d_chain_query,
+                        const uint64_t* d_member_off, const Seed* d_members, uint64_t m, int band, uint32_t max_rows, Aln* d_alns, uint64_t* d_n_ops,
+                        const uint64_t* d_cigar_off, uint32_t* d_cigar, hipStream_t s, unsigned long long* d_tally = nullptr) {
+  if (m == 0) return;
+  require(m < (1ull << 32), "more than 2^32 - 1 chains in one alignment launch");
+  require(max_rows >= 1 && max_rows <= (uint32_t)CHAIN_ALIGN_MAX_LEN && band >= 0 && band <= CHAIN_ALIGN_MAX_BAND,
+          "internal: chain alignment launch out of range");
+  const ScratchLock scratch_lock(r, s);
+  Replica::SurvScratch* sc = surv_scratch(r, s);
+  const size_t lists_need = (size_t)CHAIN_ALIGN_CLASSES * m + CHAIN_ALIGN_CLASSES;
+  auto blocks_for = [&](size_t row_bytes) {
+    return std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)grid_for(r, m, 256), CHAIN_ALIGN_TRACE_BYTES / ((size_t)max_rows * row_bytes * 256)));
+  };
+  size_t trace_bytes = 0;
+  for (int cls = 0; cls < CHAIN_ALIGN_CLASSES; cls++) {
+    const size_t row_bytes = (size_t)4 << cls;  // ChainAlignTrace: NW * sizeof(word) = 4, 8, 16
+    trace_bytes = std::max(trace_bytes, (size_t)blocks_for(row_bytes) * 256 * max_rows * row_bytes);
+  }
+  const size_t trace_need = (trace_bytes + 7) / 8;
+  if (sc->chain_align_lists.n < lists_need || sc->align_trace.n < trace_need) {
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (sc->chain_align_lists.n < lists_need) sc->chain_align_lists.alloc(lists_need + lists_need / 4);
+    if (sc->align_trace.n < trace_need) sc->align_trace.alloc(trace_need);
+  }
+  uint32_t* lists = sc->chain_align_lists.p;
+  uint32_t* list_n = lists + (size_t)CHAIN_ALIGN_CLASSES * m;
+  HIP_CHECK(hipMemsetAsync(list_n, 0, CHAIN_ALIGN_CLASSES * sizeof(uint32_t), s));
+  const bool fill = d_cigar_off != nullptr;
+  hipLaunchKernelGGL(chain_align_classify_kernel, dim3(grid_for(r, m, 256)), dim3(256), 0, s, r.dev.bwt_len - 1, d_off, d_chain_query, d_member_off, d_members,
+                     m, band, max_rows, fill ? nullptr : d_alns, fill ? nullptr : d_n_ops, lists, list_n);
+  with_alphabet(r.dev.alphabet, [&](auto A) {
+    constexpr int AL = decltype(A)::value;
+    with_flags(fill, [&](auto F) {
+      auto align = [&](auto CC) {
+        constexpr int CLS = decltype(CC)::value, NBMAX = chain_align_class_nb(CLS);
+        using TR = ChainAlignTrace<NBMAX>;
+        using TW = typename TR::word;
+        static_assert(TR::NW * sizeof(TW) == ((size_t)4 << CLS), "the trace bytes per row of the class");
+        const uint64_t blocks = blocks_for(TR::NW * sizeof(TW));
+        hipLaunchKernelGGL((chain_align_kernel<AL, NBMAX, decltype(F)::value>), dim3((unsigned)blocks), dim3(256), 0, s, text8, r.dev.bwt_len - 1, d_q, d_off,
+                           d_chain_query, d_member_off, d_members, lists + (size_t)CLS * m, list_n + CLS, band, reinterpret_cast<TW*>(sc->align_trace.p), d_alns,
+                           d_n_ops, d_cigar_off, d_cigar, d_tally);
+      };
+      if (2 * band + 1 <= chain_align_class_nb(0)) align(std::integral_constant<int, 0>{});
+      if (2 * band + 1 <= chain_align_class_nb(1)) align(std::integral_constant<int, 1>{});
+      align(std::integral_constant<int, 2>{});
+    });
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 // anchor records -> (start_row, end_row) pairs and located counts (0 for anchors of more than max_hits rows)
 void launch_anchor_ranges(Replica& r, const Anchor* d_anchors, uint64_t n, uint64_t max_hits, uint64_t* d_ranges, uint64_t* d_located, hipStream_t s) {
   if (n == 0) return;

@@ -134,6 +134,9 @@ struct Replica {
     DevBuf<uint64_t> align_trace;
     // chain_kernel: the working sets of queries beyond the LDS tile, one slab per group of the grid (sized by the grid, launchers.h)
     DevBuf<uint8_t> chain_slabs;
+    // chain_align_kernel: the class lists chain_align_classify_kernel writes in front of it -- [class][chain index], then the
+    // three list lengths (launchers.h); its direction words go to align_trace
+    DevBuf<uint32_t> chain_align_lists;
     // work-queue heads of the chunk / locate kernels launched on this stream: launches on one stream are ordered, so a
     // head is free again by the time the ring comes back to it, however many launches other streams have in flight
     DevBuf<unsigned long long> counters;

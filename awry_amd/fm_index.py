@@ -31,6 +31,8 @@ MAX_MISMATCHES = 2  # AWRY_MAX_MISMATCHES
 MAX_EDITS, EDIT_MAX_LEN, Q_CANDIDATE_CAP = 8, 256, 7  # AWRY_MAX_EDITS, AWRY_EDIT_MAX_LEN, AWRY_Q_CANDIDATE_CAP
 ALIGN_MAX_OPS = 17  # AWRY_ALIGN_MAX_OPS
 CHAIN_MAX_SEEDS, CHAIN_MAX_LOOKBACK, Q_SEED_CAP = 4096, 64, 8  # AWRY_CHAIN_MAX_SEEDS, AWRY_CHAIN_MAX_LOOKBACK, AWRY_Q_SEED_CAP
+CHAIN_ALIGN_MAX_BAND, CHAIN_ALIGN_MAX_SKEW, CHAIN_ALIGN_MAX_LEN = 8, 16, 1024  # AWRY_CHAIN_ALIGN_MAX_BAND, _MAX_SKEW, _MAX_LEN
+ALN_OK, ALN_SKEW, ALN_BAD_CHAIN = 0, 1, 2  # AWRY_ALN_OK, AWRY_ALN_SKEW, AWRY_ALN_BAD_CHAIN
 CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}  # the BAM op codes the alignment pass produces
 
 
@@ -105,6 +107,7 @@ ANCHOR_DTYPE = np.dtype([("q_begin", np.uint32), ("q_len", np.uint32), ("start_r
 SEED_DTYPE = np.dtype([("q_begin", np.uint32), ("q_len", np.uint32), ("t_pos", np.uint64)])  # awry_seed_t
 CHAIN_DTYPE = np.dtype([("score", np.uint32), ("n_seeds", np.uint32), ("q_begin", np.uint32), ("q_end", np.uint32), ("t_begin", np.uint64),
                         ("t_end", np.uint64)])  # awry_chain_t
+ALN_DTYPE = np.dtype([("t_begin", np.uint64), ("t_end", np.uint64), ("edits", np.uint32), ("status", np.uint32)])  # awry_aln_t
 
 
 class _Owned:
@@ -720,6 +723,59 @@ class FmIndex:
         """dev_edit_align + census: d_tally[2] += (hits aligned, table cells computed)"""
         _check(self._L.awry_dev_edit_align_tally(self._h, slot, d_qbytes, d_qoff, d_hit_query, d_hit_gpos, d_hit_edits, m, int(k), d_text_len, d_n_ops,
                                                  d_ops, d_tally, stream))
+
+    # ------------------------------------------------------------------ align chains: gap fill, end extension, CIGAR per chain
+    def parallel_align_chains_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 12, max_hits: int = 50, max_alignments: int = 1,
+                                  band: int = 4, max_seeds: int = 1024, lookback: int = 32, max_gap: int = 1000, max_skew: int = 100,
+                                  min_score: int = 20, want_cigar: bool = True):
+        """-> (aln_off uint64[n+1], chains CHAIN_DTYPE[total], alns ALN_DTYPE[total], cigar_off uint64[total+1], cigar uint32[runs],
+        status uint8[n]): the first min(n_chains, max_alignments) chains of every query, primary first, as parallel_chains_csr
+        reports them, each aligned base by base (include/awry_hip.h states the definition): alignment c covers
+        T[alns[c].t_begin .. alns[c].t_end) with alns[c].edits edits by the runs cigar[cigar_off[c] .. cigar_off[c+1]), each
+        len << 4 | BAM op; alns[c].status is ALN_OK, ALN_SKEW or ALN_BAD_CHAIN; want_cigar=False leaves cigar_off and cigar empty"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        off, ch, al, coff, cg, st = _u64p(), C.POINTER(_lib.Chain)(), C.POINTER(_lib.Aln)(), _u64p(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+        _check(self._L.awry_align_chains_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(max_hits), int(max_seeds),
+                                               int(lookback), int(max_gap), int(max_skew), int(min_score), int(max_alignments), int(band),
+                                               C.byref(off), C.byref(ch), C.byref(al), C.byref(coff) if want_cigar else None,
+                                               C.byref(cg) if want_cigar else None, C.byref(st)))
+        offs = _adopt(self._L, off, n + 1, np.uint64)
+        tot = int(offs[-1])
+        chains = _adopt(self._L, ch, 32 * tot, np.uint8).view(CHAIN_DTYPE)
+        alns = _adopt(self._L, al, 24 * tot, np.uint8).view(ALN_DTYPE)
+        status = _adopt(self._L, st, n, np.uint8)
+        if not want_cigar:
+            return offs, chains, alns, np.zeros(0, np.uint64), np.zeros(0, np.uint32), status
+        coffs = _adopt(self._L, coff, tot + 1, np.uint64)
+        return offs, chains, alns, coffs, _adopt(self._L, cg, int(coffs[-1]), np.uint32), status
+
+    def parallel_align_chains(self, queries: Iterable, min_len: int = 12, max_hits: int = 50, max_alignments: int = 1, band: int = 4,
+                              **chain_params):
+        """-> per query, [(score, t_begin, t_end, edits, "57=1X43=", status)] of its first max_alignments chains, the primary first
+        (none for an abandoned query); chain_params: max_seeds, lookback, max_gap, max_skew, min_score"""
+        off, ch, al, coff, cg, _ = self.parallel_align_chains_csr(*pack_queries(queries), min_len, max_hits, max_alignments, band, **chain_params)
+        return [[(int(ch[c]["score"]), int(al[c]["t_begin"]), int(al[c]["t_end"]), int(al[c]["edits"]), cigar_string(cg[coff[c]:coff[c + 1]]),
+                  int(al[c]["status"])) for c in range(int(off[i]), int(off[i + 1]))] for i in range(len(off) - 1)]
+
+    def align_chains_string(self, query, min_len: int = 12, max_hits: int = 50, max_alignments: int = 1, band: int = 4, **chain_params):
+        """alignments of one query's chains"""
+        return self.parallel_align_chains([query], min_len, max_hits, max_alignments, band, **chain_params)[0]
+
+    def dev_align_chains(self, d_qbytes, d_qoff, d_chain_query, d_member_off, d_members, m, band, d_alns, d_n_ops, d_cigar_off=None, d_cigar=None,
+                         stream=None, slot=0):
+        """device-resident alignment of the caller's chains (chain c: query d_chain_query[c] u32, members d_members[d_member_off[c] ..
+        d_member_off[c+1]) as 16-byte seed records): d_cigar_off None = the count pass (d_alns[m] 24-byte records, d_n_ops[m] u64); else
+        the fill pass writing the runs of chain c at d_cigar[d_cigar_off[c] ..); scan d_n_ops with dev_scan_counts in between"""
+        _check(self._L.awry_dev_align_chains(self._h, slot, d_qbytes, d_qoff, d_chain_query, d_member_off, d_members, m, int(band), d_alns, d_n_ops,
+                                             d_cigar_off, d_cigar, stream))
+
+    def dev_align_chains_tally(self, d_qbytes, d_qoff, d_chain_query, d_member_off, d_members, m, band, d_alns, d_n_ops, d_tally, d_cigar_off=None,
+                               d_cigar=None, stream=None, slot=0):
+        """dev_align_chains + census: d_tally[2] += (chains aligned with status ALN_OK, table cells computed)"""
+        _check(self._L.awry_dev_align_chains_tally(self._h, slot, d_qbytes, d_qoff, d_chain_query, d_member_off, d_members, m, int(band), d_alns,
+                                                   d_n_ops, d_cigar_off, d_cigar, d_tally, stream))
 
     def debug_rank_all(self, rows: np.ndarray, slot=0) -> np.ndarray:
         """Occ of every non-sentinel symbol at each row through the kernels' all-symbol rank -> uint64[len(rows), S]

@@ -359,6 +359,42 @@ class FmIndex {
     awry_free_buffer(coff); awry_free_buffer(ch); awry_free_buffer(soff); awry_free_buffer(sd); awry_free_buffer(st);
     return out;
   }
+  // the chains aligned (no counterpart in the reference; the definition is in awry_hip.h): of every query's chains the first
+  // max_alignments, the primary first -- the chain's score and spans, the text span the whole read aligns to, the edit count, a
+  // status (AWRY_ALN_OK, AWRY_ALN_SKEW, AWRY_ALN_BAD_CHAIN) and the CIGAR, one run per entry, len << 4 | BAM op (I 1, D 2, = 7, X 8)
+  struct ChainAlignment {
+    awry_chain_t chain;
+    uint64_t t_begin, t_end;
+    uint32_t edits, status;
+    std::vector<uint32_t> cigar;
+    std::string cigar_string() const {
+      std::string out;
+      for (uint32_t run : cigar) {
+        const uint32_t op = run & 15u;
+        out += std::to_string(run >> 4);
+        out += op == 7 ? '=' : op == 8 ? 'X' : op == 1 ? 'I' : 'D';
+      }
+      return out;
+    }
+  };
+  template <class StrRange>
+  std::vector<std::vector<ChainAlignment>> parallel_align_chains(const StrRange& queries, uint32_t min_len = 12, uint64_t max_hits = 50,
+                                                                 uint64_t max_alignments = 1, uint32_t band = 4, ChainParams p = ChainParams(),
+                                                                 std::vector<uint8_t>* status = nullptr) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* aoff = nullptr; awry_chain_t* ch = nullptr; awry_aln_t* al = nullptr; uint64_t* coff = nullptr; uint32_t* cg = nullptr; uint8_t* st = nullptr;
+    check(awry_align_chains_batch(h_, bytes.data(), off.data(), n, min_len, max_hits, p.max_seeds, p.lookback, p.max_gap, p.max_skew, p.min_score,
+                                  max_alignments, band, &aoff, &ch, &al, &coff, &cg, &st));
+    std::vector<std::vector<ChainAlignment>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = aoff[i]; j < aoff[i + 1]; j++)
+        out[i].push_back({ch[j], al[j].t_begin, al[j].t_end, al[j].edits, al[j].status, std::vector<uint32_t>(cg + coff[j], cg + coff[j + 1])});
+    if (status) status->assign(st, st + n);
+    awry_free_buffer(aoff); awry_free_buffer(ch); awry_free_buffer(al); awry_free_buffer(coff); awry_free_buffer(cg); awry_free_buffer(st);
+    return out;
+  }
   // src/fm_index.rs:559-582, 585-593
   SearchRange update_range_with_symbol(SearchRange r, char symbol) {
     awry_range_t o;

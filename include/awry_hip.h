@@ -394,6 +394,64 @@ int awry_chain_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *q
                      uint64_t **chain_off_out, awry_chain_t **chains_out, uint64_t **seed_off_out, awry_seed_t **seeds_out,
                      uint8_t **status_out);
 
+/* ---- align chains: gap fill, end extension, one CIGAR per chain (no counterpart in the reference) ----------------
+ * The stage after chaining in a seed-chain-extend mapper: a chain's seeds stay as diagonal runs, the query between consecutive
+ * seeds is aligned to the text between them ("gap fill"), the two ends of the read are extended into the text, and the chain gets
+ * a text span, an edit count and a CIGAR.  Everything is integer arithmetic and every tie is broken explicitly.
+ * Text model: the edit path's.  T is the text without its final '$', n = bwt_len - 1; queries are mapped to symbol indices and
+ *   rejected exactly as on the exact path; query N equals text N; a record join or text N is an ordinary symbol that costs an
+ *   edit unless the query has N there.  Unit costs.
+ * Parameters: band = W, 0 <= W <= AWRY_CHAIN_ALIGN_MAX_BAND = 8; AWRY_CHAIN_ALIGN_MAX_SKEW = 16; AWRY_CHAIN_ALIGN_MAX_LEN = 1024
+ *   query letters.
+ * Pieces.  A chain's members, in their reported order, are (qb, len, tp); (qe, te) is a running pair.  The first member is a
+ *   piece as it stands: qe = qb + len, te = tp + len.  Every later member is clipped on the left by o = max(0, qe - qb, te - tp):
+ *   if o >= len it is dropped and (qe, te) stay; otherwise the piece is (qb + o, len - o, tp + o) and qe = qb + len, te = tp + len.
+ *   Consecutive pieces therefore overlap neither in the query nor in the text.  A piece is a diagonal run: letter by letter it
+ *   emits '=' or 'X' by comparing symbol indices, and every 'X' is one edit (the chains of awry_chain_batch give only '='; a
+ *   caller's own seeds need not be exact matches).
+ * Segments.  A segment aligns x (a query letters) to a prefix of y (text; at most `avail` letters readable), inside the band
+ *   lo <= j - i <= hi, lo = min(0, m) - W, hi = max(0, m) + W; cells outside the band, or with j > J, are +infinity.
+ *   gap between consecutive pieces: x = q[qe_prev .. qb_next), y = T[te_prev .. tb_next), b = |y|, m = b - a, J = b; global: it
+ *     ends at (a, b).  a = 0 gives b 'D's, b = 0 gives a 'I's.
+ *   right extension: x = q[qe_last .. L), y_j = T[te_last + j], avail = n - te_last, m = min(0, avail - a), J = min(a + W,
+ *     avail); it ends at j*, the smallest j that minimises C[a][j]; t_end = te_last + j*.
+ *   left extension: the same on reversed strings, x = reverse(q[0 .. qb_first)), y_j = T[tb_first - 1 - j], avail = tb_first;
+ *     t_begin = tb_first - j*; the traceback from (a, j*) back to (0, 0) emits the operations already in query order.
+ *   Traceback, in every segment, by awry_align_edit_batch's rule on banded values: the diagonal first ('=' / 'X'), then 'I'
+ *   (i--), then 'D' (j--).
+ *   NB = |m| + 2 W + 1 <= 33 cells per row.  If any segment of a chain has |m| > AWRY_CHAIN_ALIGN_MAX_SKEW -- through dropped
+ *   members, a caller's seeds, or a read that hangs far over the text's start or end -- the chain is not aligned: status
+ *   AWRY_ALN_SKEW, t_begin / t_end = the pieces' span, edits = 0, no runs.  Members not strictly ascending in both q_begin and
+ *   t_pos, members that reach past L or n, and an empty member list give AWRY_ALN_BAD_CHAIN (so does, in the device primitive, a
+ *   query that is empty or longer than AWRY_CHAIN_ALIGN_MAX_LEN): t_begin = t_end = 0, edits = 0, no runs, nothing read out of
+ *   bounds.  AWRY_ALN_OK is 0.
+ * Result per chain: awry_aln_t; edits = the 'X's of the pieces + the costs of all segments.  The operations of left extension,
+ *   pieces, gaps and right extension are concatenated in query order and run-length encoded over the whole script (a gap's
+ *   leading '=' merges with the piece before it), in the encoding of awry_align_edit_batch: len << 4 | op, I 1, D 2, = 7, X 8.
+ *   The query is always consumed whole: no clipping.
+ * Properties.  (1) A gap's banded cost v <= |m| + 2 W + 1 is the unbanded optimum: a path that leaves the band needs at least
+ *   |m| + 2 W + 2 indels.  (2) An extension's banded cost v <= W is the unbanded optimum (over all end columns) when avail >= a.
+ *   (3) Replaying the CIGAR over q and T[t_begin .. t_end) reproduces both strings and the edit count.
+ *
+ * awry_align_chains_batch: the arguments of awry_chain_batch, then max_alignments >= 1 -- of each query's chains the first
+ * min(n_chains, max_alignments) are aligned, primary first -- and band.  CSR output, library-allocated (awry_free_buffer): the
+ * alignments of query i are alns[aln_off[i] .. aln_off[i+1]), chains[] holds the awry_chain_t records of exactly those chains
+ * (equal to what awry_chain_batch returns for them), the runs of alignment c are cigar[cigar_off[c] .. cigar_off[c+1]); status[n]
+ * is AWRY_Q_OK or AWRY_Q_SEED_CAP.  All but aln_off_out nullable; cigar_off_out and cigar_out are given or omitted together.
+ * Errors: those of awry_chain_batch; the edit path's index restrictions (bwt_len >= 2^32 or a wide-row replica =>
+ * AWRY_ERR_ARG, no HBM for the text copy => AWRY_ERR_OOM); band > 8 or max_alignments == 0 => AWRY_ERR_ARG; a query longer than
+ * AWRY_CHAIN_ALIGN_MAX_LEN fails the batch with AWRY_ERR_INVALID_QUERY and leaves the out-pointers untouched.  Chains and their
+ * members stay on the device; the alignment runs there in sub-batches of 2^18 chains (env AWRY_CHAIN_ALIGN_SUB_BATCH, read per
+ * call).  No accelerator, seed length, replica count, chunk capacity or sub-batch size changes any output. */
+enum { AWRY_CHAIN_ALIGN_MAX_BAND = 8, AWRY_CHAIN_ALIGN_MAX_SKEW = 16, AWRY_CHAIN_ALIGN_MAX_LEN = 1024 };
+enum { AWRY_ALN_OK = 0, AWRY_ALN_SKEW = 1, AWRY_ALN_BAD_CHAIN = 2 };
+typedef struct { uint64_t t_begin, t_end; uint32_t edits, status; } awry_aln_t;
+int awry_align_chains_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len,
+                            uint64_t max_hits, uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew,
+                            uint32_t min_score, uint64_t max_alignments, uint32_t band, uint64_t **aln_off_out,
+                            awry_chain_t **chains_out, awry_aln_t **alns_out, uint64_t **cigar_off_out, uint32_t **cigar_out,
+                            uint8_t **status_out);
+
 /* releases an array one of the calls above (or awry_locate / awry_read_query_file) returned.  Result arrays are pinned
  * host memory recycled through a process-wide pool (the device writes results straight into them); never pass them to
  * free().  AWRY_PINNED_CACHE_GB (default 4) bounds what the pool keeps between calls. */
@@ -607,6 +665,25 @@ int awry_dev_chain_seeds_tally(awry_index_t *idx, int slot, const uint64_t *d_se
                                uint64_t *d_n_chains, uint64_t *d_n_members, const uint64_t *d_chain_off,
                                const uint64_t *d_member_off, awry_chain_t *d_chains, awry_seed_t *d_members, uint8_t *d_status,
                                uint64_t *d_tally, void *stream);
+/* The device primitive under awry_align_chains_batch (the definition is stated there), for a caller with chains of their own:
+ * chain c belongs to query d_chain_query[c] (u32) and has the members d_members[d_member_off[c] .. d_member_off[c+1]); the queries
+ * are (d_qbytes, d_qoff), readable as for the other device entry points; m < 2^32.  The two-call protocol of awry_dev_smems:
+ * d_cigar_off == NULL is the count pass -> d_alns[m] and d_n_ops[m] (u64, ready for awry_dev_scan_counts); otherwise the fill
+ * pass writes the runs of chain c at d_cigar[d_cigar_off[c] ..) and never a slot at or beyond d_cigar_off[c+1] (d_alns / d_n_ops
+ * are not written there and may be NULL).  Each pass computes the alignments anew.  One chain per lane; the chains are first
+ * sorted into three classes by their widest segment (NB <= 9, 17, 33) and each class runs its own instantiation.  Queued on
+ * `stream`; no synchronisation except where the per-stream scratch (class lists, and up to 512 MiB of direction words, sized by
+ * the launch) grows. */
+int awry_dev_align_chains(awry_index_t *idx, int slot, const uint8_t *d_qbytes, const uint64_t *d_qoff,
+                          const uint32_t *d_chain_query, const uint64_t *d_member_off, const awry_seed_t *d_members, uint64_t m,
+                          uint32_t band, awry_aln_t *d_alns, uint64_t *d_n_ops, const uint64_t *d_cigar_off, uint32_t *d_cigar,
+                          void *stream);
+/* the same with a work census: d_tally[2] (u64, caller-zeroed) += {chains aligned with status AWRY_ALN_OK, table cells computed
+ * (the cells of every segment's rows 0..a inside band and table)}, per pass */
+int awry_dev_align_chains_tally(awry_index_t *idx, int slot, const uint8_t *d_qbytes, const uint64_t *d_qoff,
+                                const uint32_t *d_chain_query, const uint64_t *d_member_off, const awry_seed_t *d_members,
+                                uint64_t m, uint32_t band, awry_aln_t *d_alns, uint64_t *d_n_ops, const uint64_t *d_cigar_off,
+                                uint32_t *d_cigar, uint64_t *d_tally, void *stream);
 /* test hook of the all-symbol rank primitive: d_occ[i * S + s - 1] = Occ(s, d_rows[i]) for every non-sentinel symbol index s
  * (S = 5 nucleotide, 21 amino; inclusive of the row, as awry_update_range uses it); rows >= bwt_len give zeros */
 int awry_debug_rank_all(awry_index_t *idx, int slot, const void *d_rows, uint64_t n, void *d_occ, void *stream);

@@ -15,7 +15,7 @@ use std::os::raw::c_char;
 use std::path::{Path, PathBuf};
 use std::sync::Arc;
 
-use awry_hip_sys::{self as sys, awry_anchor_t as RawAnchor, awry_chain_t as RawChain, awry_seed_t as RawSeed};
+use awry_hip_sys::{self as sys, awry_aln_t as RawAln, awry_anchor_t as RawAnchor, awry_chain_t as RawChain, awry_seed_t as RawSeed};
 use rayon::iter::{IndexedParallelIterator, IntoParallelIterator, IntoParallelRefIterator, ParallelIterator};
 
 use crate::{
@@ -226,6 +226,19 @@ pub struct Chain {
     pub t_begin: u64,
     pub t_end: u64,
     pub seeds: Vec<(u32, u32, u64)>,
+}
+
+/// One aligned chain of [`FmIndex::parallel_align_chains`]: the chain's score, the text span `[t_begin, t_end)` the whole read
+/// aligns to, the edit count, the status (0 aligned, 1 `AWRY_ALN_SKEW`, 2 `AWRY_ALN_BAD_CHAIN`) and the CIGAR runs
+/// (`len << 4 | op`, see [`cigar_string`]).
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct ChainAlignment {
+    pub score: u32,
+    pub t_begin: u64,
+    pub t_end: u64,
+    pub edits: u32,
+    pub status: u32,
+    pub cigar: Vec<u32>,
 }
 
 /// The CIGAR string of the runs [`FmIndex::parallel_align_edit`] returns (`len << 4 | op`, BAM's op codes): `"57=1X43="`.
@@ -618,6 +631,66 @@ impl FmIndex {
         unsafe {
             sys::awry_free_buffer(smem_off as *mut std::os::raw::c_void);
             sys::awry_free_buffer(smems as *mut std::os::raw::c_void);
+        }
+        Ok(out)
+    }
+
+    /// The chains aligned (no counterpart in the reference; the definition is in include/awry_hip.h): of every query's chains the
+    /// first `max_alignments`, the primary first, each with the text span of the whole read, its edit count and its CIGAR; `band`
+    /// is 0..=8.  And per query whether it was abandoned because it has more than `params.max_seeds` seeds.
+    pub fn parallel_align_chains<'a>(
+        &self,
+        queries: impl ParallelIterator<Item = &'a str>,
+        min_len: u32,
+        max_hits: u64,
+        max_alignments: u64,
+        band: u32,
+        params: ChainParams,
+    ) -> Result<(Vec<Vec<ChainAlignment>>, Vec<bool>), AwryError> {
+        let csr = to_csr(queries);
+        let n = csr.offsets.len() - 1;
+        let mut aln_off: *mut u64 = std::ptr::null_mut();
+        let mut chains: *mut RawChain = std::ptr::null_mut();
+        let mut alns: *mut RawAln = std::ptr::null_mut();
+        let mut cigar_off: *mut u64 = std::ptr::null_mut();
+        let mut cigar: *mut u32 = std::ptr::null_mut();
+        let mut st: *mut u8 = std::ptr::null_mut();
+        check(unsafe {
+            sys::awry_align_chains_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, min_len, max_hits, params.max_seeds, params.lookback,
+                                         params.max_gap, params.max_skew, params.min_score, max_alignments, band, &mut aln_off, &mut chains, &mut alns,
+                                         &mut cigar_off, &mut cigar, &mut st)
+        })?;
+        let out = unsafe {
+            let off = std::slice::from_raw_parts(aln_off, n + 1);
+            let total = off[n] as usize;
+            let ch: &[RawChain] = if total == 0 { &[] } else { std::slice::from_raw_parts(chains, total) };
+            let al: &[RawAln] = if total == 0 { &[] } else { std::slice::from_raw_parts(alns, total) };
+            let coff = std::slice::from_raw_parts(cigar_off, total + 1);
+            let runs: &[u32] = if coff[total] == 0 { &[] } else { std::slice::from_raw_parts(cigar, coff[total] as usize) };
+            let status: &[u8] = if n == 0 { &[] } else { std::slice::from_raw_parts(st, n) };
+            let per = (0..n)
+                .map(|i| {
+                    (off[i] as usize..off[i + 1] as usize)
+                        .map(|j| ChainAlignment {
+                            score: ch[j].score,
+                            t_begin: al[j].t_begin,
+                            t_end: al[j].t_end,
+                            edits: al[j].edits,
+                            status: al[j].status,
+                            cigar: runs[coff[j] as usize..coff[j + 1] as usize].to_vec(),
+                        })
+                        .collect::<Vec<_>>()
+                })
+                .collect::<Vec<_>>();
+            (per, status.iter().map(|&s| s == 8).collect::<Vec<_>>())  // AWRY_Q_SEED_CAP
+        };
+        unsafe {
+            sys::awry_free_buffer(aln_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(chains as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(alns as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(cigar_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(cigar as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(st as *mut std::os::raw::c_void);
         }
         Ok(out)
     }
