@@ -39,6 +39,11 @@ class Chain(C.Structure):  # awry_chain_t
                 ("t_end", C.c_uint64)]
 
 
+class Map(C.Structure):  # awry_map_t
+    _fields_ = [("t_begin", C.c_uint64), ("t_end", C.c_uint64), ("edits", C.c_uint32), ("chain_score", C.c_uint32), ("chain_index", C.c_uint32),
+                ("strand", C.c_uint8), ("mapq", C.c_uint8), ("flags", C.c_uint16)]
+
+
 class BuildArgs(C.Structure):
     _fields_ = [("input_path", C.c_char_p), ("sa_tmp_path", C.c_char_p), ("sa_ratio", C.c_uint64),
                 ("kmer_len", C.c_uint8), ("alphabet", C.c_uint8), ("max_query_len", C.c_uint64),
@@ -133,6 +138,10 @@ def load_library():
         C.POINTER(C.POINTER(Aln)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)), C.POINTER(u8p))
     sig("awry_dev_align_chains", i32, vp, i32, vp, vp, vp, vp, vp, u64, u32, vp, vp, vp, vp, vp)
     sig("awry_dev_align_chains_tally", i32, vp, i32, vp, vp, vp, vp, vp, u64, u32, vp, vp, vp, vp, vp, vp)
+    sig("awry_map_batch", i32, vp, vp, u64p, u64, u32, u64, u32, u32, u32, u32, u32, u64, u64, u32, C.POINTER(u64p), C.POINTER(C.POINTER(Map)),
+        C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)), C.POINTER(u8p))
+    sig("awry_dev_revcomp", i32, vp, i32, vp, vp, u64, vp, vp, vp)
+    sig("awry_dev_map_select", i32, vp, i32, vp, vp, vp, vp, u64, u32, u32, vp, vp, vp, vp, vp, vp, vp)
     sig("awry_locate_edit_batch", i32, vp, vp, u64p, u64, i32, u64, C.POINTER(u64p), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(u8p),
         C.POINTER(u8p))
     sig("awry_dev_edit_windows", i32, vp, i32, vp, vp, vp, vp, vp, u64, i32, vp, vp, vp, vp, vp)

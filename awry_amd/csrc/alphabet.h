@@ -94,4 +94,13 @@ AWRY_HD uint8_t ascii_of_index(int alphabet, int idx) {
   return (unsigned)idx < 22u ? (uint8_t)T[idx] : (uint8_t)'X';
 }
 
+// complement of a nucleotide symbol index: $0 -> 0, A1 <-> T5, C2 <-> G3, N4 -> 4
+AWRY_HD int nt_complement_index(int idx) {
+  constexpr uint8_t T[6] = {0, 5, 3, 2, 4, 1};
+  return (unsigned)idx < 6u ? T[idx] : 4;
+}
+// the byte the reverse complement holds for a query byte: the letter of the complement of its symbol index (case folded, U read
+// as T, any other byte 'N', a sentinel '$').  The one table of host and device.
+AWRY_HD uint8_t nt_complement_ascii(uint8_t a) { return ascii_of_index(NUCLEOTIDE, nt_complement_index(index_of_ascii(NUCLEOTIDE, a))); }
+
 }  // namespace awry

@@ -11,6 +11,7 @@
 #include "chain_host.h"
 #include "edit_host.h"
 #include "chain_align_host.h"
+#include "map_host.h"
 #include "prewarm.h"
 
 namespace {
@@ -439,6 +440,22 @@ int awry_align_chains_batch(awry_index_t* idx, const uint8_t* qbytes, const uint
     require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
     align_chains_batch(idx, qbytes, qoff, n, min_len, max_hits, P, max_alignments, band, aln_off_out, chains_out, alns_out, cigar_off_out, cigar_out,
                        status_out);
+  });
+}
+
+int awry_map_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits, uint32_t max_seeds,
+                   uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score, uint64_t chains_per_strand, uint64_t max_report, uint32_t band,
+                   uint64_t** map_off_out, awry_map_t** maps_out, awry_pos_t** pos_out, uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out) {
+  return guarded([&] {
+    require(idx && qoff && map_off_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_smem_args(min_len);
+    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
+    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    require_map_args(chains_per_strand, max_report, band);
+    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
+    map_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, (uint32_t)max_report, band, map_off_out, maps_out, pos_out,
+              cigar_off_out, cigar_out, status_out);
   });
 }
 
@@ -977,6 +994,30 @@ int awry_dev_align_chains_tally(awry_index_t* idx, int slot, const uint8_t* d_qb
             "null device pointer");
     launch_chain_align(r, edit_text(r), d_qbytes, d_qoff, d_chain_query, d_member_off, reinterpret_cast<const Seed*>(d_members), m, (int)band,
                        CHAIN_ALIGN_MAX_LEN, reinterpret_cast<Aln*>(d_alns), d_n_ops, d_cigar_off, d_cigar, (hipStream_t)stream, (unsigned long long*)d_tally);
+  });
+}
+
+int awry_dev_revcomp(awry_index_t* idx, int slot, const uint8_t* d_qbytes, const uint64_t* d_qoff, uint64_t n, uint8_t* d_out_bytes, uint64_t* d_out_off,
+                     void* stream) {
+  return guarded([&] {
+    require(idx != nullptr, "null argument");
+    if (idx->host.alphabet != NUCLEOTIDE) throw ArgError("the reverse complement needs a nucleotide index");
+    Replica& r = replica(idx, slot);
+    require(d_out_off && (n == 0 || (d_qbytes && d_qoff && d_out_bytes)), "null device pointer");
+    launch_strand_expand(r, d_qbytes, d_qoff, n, d_out_bytes, d_out_off, (hipStream_t)stream);
+  });
+}
+
+int awry_dev_map_select(awry_index_t* idx, int slot, const uint64_t* d_aln_off, const awry_aln_t* d_alns, const awry_chain_t* d_chains,
+                        const uint8_t* d_chain_status, uint64_t n, uint32_t chains_per_strand, uint32_t max_report, uint64_t* d_n_maps,
+                        uint8_t* d_read_status, const uint64_t* d_map_off, awry_map_t* d_maps, uint32_t* d_sel, awry_pos_t* d_pos, void* stream) {
+  return guarded([&] {
+    require_map_args(chains_per_strand, max_report, 0);
+    Replica& r = replica(idx, slot);
+    require(n == 0 || (d_aln_off && d_alns && d_chains && (d_map_off ? d_maps != nullptr : d_n_maps != nullptr)), "null device pointer");
+    launch_map_select(r, d_aln_off, reinterpret_cast<const Aln*>(d_alns), reinterpret_cast<const Chain*>(d_chains), d_chain_status, n, chains_per_strand,
+                      max_report, d_n_maps, d_read_status, d_map_off, reinterpret_cast<MapRec*>(d_maps), d_sel, reinterpret_cast<uint64_t*>(d_pos),
+                      (hipStream_t)stream);
   });
 }
 

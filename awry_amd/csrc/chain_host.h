@@ -54,15 +54,32 @@ void chain_launch(Replica& r, hipStream_t s, uint64_t items, K kernel, Args... a
 // SMEM count pass, scan, fill pass, ranges, scan of the located counts and locate (anchor_chunk's flow, text positions only); then
 // one seed per located hit, the chain count pass, the scans of chains and members, the fill pass.  false: the chunk's located
 // hits exceed the capacity and it holds more than one query -- nothing appended.  With a sink, the chunk's chains and members go
-// to it, on the device, and nothing is appended to `out`.
+// to it, on the device, and nothing is appended to `out`.  both_strands (with a sink): the chunk's reads are uploaded once and
+// expanded on the device into the doubled batch (launch_strand_expand: query 2i = read i, query 2i + 1 = its reverse complement);
+// everything after that, the sink's view included, is over the 2 (c.hi - c.lo) queries, a rejected query is reported under its
+// read's index, and the capacity test counts reads, so a read's two strands are never split.
 bool chain_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, uint32_t min_len, uint64_t max_hits, const ChainParams& P,
-                 bool want_members, ChainHits& out, const ChainSink* sink = nullptr) {
+                 bool want_members, ChainHits& out, const ChainSink* sink = nullptr, bool both_strands = false) {
   const hipStream_t s = r.stream;
-  const uint64_t n = c.hi - c.lo;
+  const uint64_t nreads = c.hi - c.lo, n = both_strands ? 2 * nreads : nreads;
   for (uint64_t i = c.lo; i < c.hi; i++)
     if (qoff[i + 1] >= qoff[i] && qoff[i + 1] - qoff[i] >= (1ull << 31)) throw ArgError("a query of 2^31 letters or more");
-  ChunkBuffers cb;
-  upload_chunk(r, cb, qbytes, qoff, c);
+  ChunkBuffers cb, up;
+  upload_chunk(r, both_strands ? up : cb, qbytes, qoff, c);
+  if (both_strands) {
+    const uint64_t nbytes = up.h_off[nreads];
+    cb.q.alloc(2 * nbytes + 16);
+    cb.off.alloc(n + 1);
+    cb.status.alloc(std::max<uint64_t>(n, 1));
+    cb.h_off.resize(n + 1);
+    for (uint64_t i = 0; i < nreads; i++) {
+      cb.h_off[2 * i] = 2 * up.h_off[i];
+      cb.h_off[2 * i + 1] = 2 * up.h_off[i] + (up.h_off[i + 1] - up.h_off[i]);
+    }
+    cb.h_off[n] = 2 * nbytes;
+    cb.h_status.resize(n);
+    launch_strand_expand(r, up.q.p, up.off.p, nreads, cb.q.p, cb.off.p, s);
+  }
   DevBuf<uint64_t> na(n), aoff(n + 1), scratch(scan_tiles(n) + 1);
   launch_smems(r, cb.q.p, cb.off.p, n, min_len, na.p, nullptr, nullptr, cb.status.p, s);
   launch_scan(r, na.p, n, aoff.p, scratch.p, s);
@@ -70,7 +87,12 @@ bool chain_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard 
   HIP_CHECK(hipMemcpyAsync(&total, aoff.p + n, 8, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  check_status(cb, c.lo);
+  if (both_strands) {
+    for (uint64_t i = 0; i < n; i++)
+      if (cb.h_status[i] != Q_OK) raise_bad_query(c.lo + i / 2, cb.h_status[i]);  // the read's own index
+  } else {
+    check_status(cb, c.lo);
+  }
   if (total >= (1ull << 32)) throw ArgError("a chunk of queries with 2^32 SMEMs or more");
   DevBuf<uint64_t> soff(n + 1), d_gpos;
   DevBuf<Seed> seeds;
@@ -83,7 +105,7 @@ bool chain_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard 
     launch_scan(r, located.p, total, hoff.p, lscratch.p, s);
     HIP_CHECK(hipMemcpyAsync(&nhits, hoff.p + total, 8, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    if (nhits > anchor_hit_cap() && n > 1) return false;
+    if (nhits > anchor_hit_cap() && nreads > 1) return false;
     chain_launch(r, s, n + 1, chain_seed_off_kernel, aoff.p, hoff.p, n + 1, soff.p);
     if (nhits) {
       d_gpos.alloc(nhits);
@@ -127,12 +149,12 @@ bool chain_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard 
 }
 
 void chain_range(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, uint32_t min_len, uint64_t max_hits, const ChainParams& P,
-                 bool want_members, ChainHits& out, const ChainSink* sink = nullptr) {
+                 bool want_members, ChainHits& out, const ChainSink* sink = nullptr, bool both_strands = false) {
   if (c.hi <= c.lo) return;
-  if (chain_chunk(r, qbytes, qoff, c, min_len, max_hits, P, want_members, out, sink)) return;
-  const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order
-  chain_range(r, qbytes, qoff, Shard{c.lo, mid}, min_len, max_hits, P, want_members, out, sink);
-  chain_range(r, qbytes, qoff, Shard{mid, c.hi}, min_len, max_hits, P, want_members, out, sink);
+  if (chain_chunk(r, qbytes, qoff, c, min_len, max_hits, P, want_members, out, sink, both_strands)) return;
+  const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order (between reads, never between a read's strands)
+  chain_range(r, qbytes, qoff, Shard{c.lo, mid}, min_len, max_hits, P, want_members, out, sink, both_strands);
+  chain_range(r, qbytes, qoff, Shard{mid, c.hi}, min_len, max_hits, P, want_members, out, sink, both_strands);
 }
 
 // awry_chain_batch: shards over the replicas, results stitched in query order into pinned-pool arrays.  The out-pointers are

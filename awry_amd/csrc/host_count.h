@@ -14,9 +14,9 @@ std::vector<Shard> shard_queries(uint64_t n, size_t parts) {  // query i -> repl
   return out;
 }
 
-// cut [lo, hi) into chunks bounded in queries and bytes
-std::vector<Shard> chunk_queries(const uint64_t* qoff, uint64_t lo, uint64_t hi) {
-  const uint64_t MAXQ = 1ull << 24, MAXB = 1ull << 29;
+// cut [lo, hi) into chunks bounded in queries and bytes; copies: what the device holds per query given (2: both strands)
+std::vector<Shard> chunk_queries(const uint64_t* qoff, uint64_t lo, uint64_t hi, uint64_t copies = 1) {
+  const uint64_t MAXQ = (1ull << 24) / copies, MAXB = (1ull << 29) / copies;
   std::vector<Shard> out;
   uint64_t a = lo;
   while (a < hi) {

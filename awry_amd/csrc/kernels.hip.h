@@ -49,6 +49,10 @@
 //                                                            extensions and gaps, one CIGAR per chain; one chain per lane over a class list, two
 //                                                            passes [kernels_chain_align]
 //                         + chain_align_classify / take / select / gather kernels: class lists, and the first chains of each query [kernels_chain_align]
+//   map both strands      STRAND_EXPAND_KERNEL               reads -> the doubled batch (read, reverse complement), 16 lanes per read [kernels_map]
+//                         + MAP_SELECT_KERNEL<FILL>          one read per lane: rank the aligned chains of both strands by selection, drop
+//                                                            redundant spans, MAPQ; count pass, scan, fill pass [kernels_map]
+//                         + MAP_GATHER_KERNEL                the reported alignments as a chain list for the CIGAR fill pass [kernels_map]
 //   count, wide rows      count_nt2_wide_kernel, count_nt2_wide_probe_kernel   64-bit rows [kernels_wide]
 //   locate                LOCATE_TILE_KERNEL<A>              hit -> row, sampled / verified hits finished [this file]
 //                         + LOCATE_WALK_NT_LANE_KERNEL       LF walks of the rest, one hit per lane, whole block per step [this file]
@@ -570,3 +574,4 @@ __global__ __launch_bounds__(256) void locate_walk_nt_lane_kernel(DevIndex ix, u
 #include "kernels_align.hip.h"     // edit_symbols, edit_owner, ByteStream
 #include "kernels_chain.hip.h"     // localise, tally_add, Anchor
 #include "kernels_chain_align.hip.h"  // Seed, Chain, ByteStream, edit_symbols, align_bam_op
+#include "kernels_map.hip.h"       // Aln, Chain, Seed, localise

@@ -638,6 +638,27 @@ void launch_chain_align(Replica& r, const uint8_t* text8, const uint8_t* d_q, co
   HIP_CHECK(hipGetLastError());
 }
 
+// The doubled batch of n reads (kernels_map.hip.h): d_out_bytes holds 2 (d_off[n] - d_off[0]) bytes, d_out_off 2 n + 1 offsets.
+void launch_strand_expand(Replica& r, const uint8_t* d_q, const uint64_t* d_off, uint64_t n, uint8_t* d_out_bytes, uint64_t* d_out_off, hipStream_t s) {
+  require(r.dev.alphabet == NUCLEOTIDE, "the reverse complement needs a nucleotide index");
+  if (n == 0) { HIP_CHECK(hipMemsetAsync(d_out_off, 0, 8, s)); return; }
+  hipLaunchKernelGGL(strand_expand_kernel, dim3(grid_for(r, n * MAP_EXPAND_GROUP, 256)), dim3(256), 0, s, d_q, d_off, n, d_out_bytes, d_out_off);
+  HIP_CHECK(hipGetLastError());
+}
+
+// Rank, redundancy, report and MAPQ over the alignment records of a doubled batch of n reads (kernels_map.hip.h).  d_map_off ==
+// nullptr: the count pass (d_n_maps, d_read_status nullable); else the fill pass (d_maps; d_sel, d_pos nullable).
+void launch_map_select(Replica& r, const uint64_t* d_aln_off, const Aln* d_alns, const Chain* d_chains, const uint8_t* d_chain_status, uint64_t n,
+                       uint32_t chains_per_strand, uint32_t max_report, uint64_t* d_n_maps, uint8_t* d_read_status, const uint64_t* d_map_off, MapRec* d_maps,
+                       uint32_t* d_sel, uint64_t* d_pos, hipStream_t s) {
+  if (n == 0) return;
+  with_flags(d_map_off != nullptr, [&](auto F) {
+    hipLaunchKernelGGL(map_select_kernel<F()>, dim3(grid_for(r, n, 256)), dim3(256), 0, s, r.dev, d_aln_off, d_alns, d_chains, d_chain_status, n,
+                       chains_per_strand, max_report, d_n_maps, d_read_status, d_map_off, d_maps, d_sel, d_pos);
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 // anchor records -> (start_row, end_row) pairs and located counts (0 for anchors of more than max_hits rows)
 void launch_anchor_ranges(Replica& r, const Anchor* d_anchors, uint64_t n, uint64_t max_hits, uint64_t* d_ranges, uint64_t* d_located, hipStream_t s) {
   if (n == 0) return;

@@ -33,6 +33,7 @@ ALIGN_MAX_OPS = 17  # AWRY_ALIGN_MAX_OPS
 CHAIN_MAX_SEEDS, CHAIN_MAX_LOOKBACK, Q_SEED_CAP = 4096, 64, 8  # AWRY_CHAIN_MAX_SEEDS, AWRY_CHAIN_MAX_LOOKBACK, AWRY_Q_SEED_CAP
 CHAIN_ALIGN_MAX_BAND, CHAIN_ALIGN_MAX_SKEW, CHAIN_ALIGN_MAX_LEN = 8, 16, 1024  # AWRY_CHAIN_ALIGN_MAX_BAND, _MAX_SKEW, _MAX_LEN
 ALN_OK, ALN_SKEW, ALN_BAD_CHAIN = 0, 1, 2  # AWRY_ALN_OK, AWRY_ALN_SKEW, AWRY_ALN_BAD_CHAIN
+MAP_MAX_CHAINS, MAP_SECONDARY = 8, 1  # AWRY_MAP_MAX_CHAINS, AWRY_MAP_SECONDARY
 CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}  # the BAM op codes the alignment pass produces
 
 
@@ -108,6 +109,8 @@ SEED_DTYPE = np.dtype([("q_begin", np.uint32), ("q_len", np.uint32), ("t_pos", n
 CHAIN_DTYPE = np.dtype([("score", np.uint32), ("n_seeds", np.uint32), ("q_begin", np.uint32), ("q_end", np.uint32), ("t_begin", np.uint64),
                         ("t_end", np.uint64)])  # awry_chain_t
 ALN_DTYPE = np.dtype([("t_begin", np.uint64), ("t_end", np.uint64), ("edits", np.uint32), ("status", np.uint32)])  # awry_aln_t
+MAP_DTYPE = np.dtype([("t_begin", np.uint64), ("t_end", np.uint64), ("edits", np.uint32), ("chain_score", np.uint32), ("chain_index", np.uint32),
+                      ("strand", np.uint8), ("mapq", np.uint8), ("flags", np.uint16)])  # awry_map_t
 
 
 class _Owned:
@@ -776,6 +779,61 @@ class FmIndex:
         """dev_align_chains + census: d_tally[2] += (chains aligned with status ALN_OK, table cells computed)"""
         _check(self._L.awry_dev_align_chains_tally(self._h, slot, d_qbytes, d_qoff, d_chain_query, d_member_off, d_members, m, int(band), d_alns,
                                                    d_n_ops, d_cigar_off, d_cigar, d_tally, stream))
+
+    # ------------------------------------------------------------------ map reads on both strands: ranked alignments, MAPQ
+    def parallel_map_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4,
+                         max_report: int = 1, band: int = 4, max_seeds: int = 1024, lookback: int = 32, max_gap: int = 1000, max_skew: int = 100,
+                         min_score: int = 20, want_pos: bool = True, want_cigar: bool = True):
+        """-> (map_off uint64[n+1], maps MAP_DTYPE[total], pos uint64[total, 2], cigar_off uint64[total+1], cigar uint32[runs], status
+        uint8[n]): per read its best alignments over both strands, the primary first (include/awry_hip.h states the definition):
+        record c covers T[t_begin .. t_end) with `edits` edits by the runs cigar[cigar_off[c] .. cigar_off[c+1]) -- for strand 1 of
+        the read's reverse complement against the forward text -- pos[c] is the record and offset of t_begin, mapq the mapping
+        quality (0 for secondaries, which carry MAP_SECONDARY in flags); status[i] == Q_SEED_CAP marks a read one of whose strands
+        was abandoned at max_seeds; want_pos / want_cigar = False leave those arrays empty"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        off, mp, ps, coff, cg, st = _u64p(), C.POINTER(_lib.Map)(), C.POINTER(_lib.Pos)(), _u64p(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+        _check(self._L.awry_map_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(max_hits), int(max_seeds), int(lookback),
+                                      int(max_gap), int(max_skew), int(min_score), int(chains_per_strand), int(max_report), int(band), C.byref(off),
+                                      C.byref(mp), C.byref(ps) if want_pos else None, C.byref(coff) if want_cigar else None,
+                                      C.byref(cg) if want_cigar else None, C.byref(st)))
+        offs = _adopt(self._L, off, n + 1, np.uint64)
+        tot = int(offs[-1])
+        maps = _adopt(self._L, mp, 32 * tot, np.uint8).view(MAP_DTYPE)
+        pos = _adopt(self._L, ps, 2 * tot, np.uint64).reshape(-1, 2) if want_pos else np.zeros((0, 2), np.uint64)
+        status = _adopt(self._L, st, n, np.uint8)
+        if not want_cigar:
+            return offs, maps, pos, np.zeros(0, np.uint64), np.zeros(0, np.uint32), status
+        coffs = _adopt(self._L, coff, tot + 1, np.uint64)
+        return offs, maps, pos, coffs, _adopt(self._L, cg, int(coffs[-1]), np.uint32), status
+
+    def parallel_map(self, queries: Iterable, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4, max_report: int = 1, band: int = 4,
+                     **chain_params):
+        """-> per read, [(record, offset, strand, mapq, edits, "57=1X43=", flags)] of its reported alignments, the primary first (none
+        for a read that maps nowhere); chain_params: max_seeds, lookback, max_gap, max_skew, min_score"""
+        off, mp, pos, coff, cg, _ = self.parallel_map_csr(*pack_queries(queries), min_len, max_hits, chains_per_strand, max_report, band, **chain_params)
+        return [[(int(pos[c][0]), int(pos[c][1]), int(mp[c]["strand"]), int(mp[c]["mapq"]), int(mp[c]["edits"]), cigar_string(cg[coff[c]:coff[c + 1]]),
+                  int(mp[c]["flags"])) for c in range(int(off[i]), int(off[i + 1]))] for i in range(len(off) - 1)]
+
+    def map_string(self, query, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4, max_report: int = 1, band: int = 4, **chain_params):
+        """alignments of one read over both strands"""
+        return self.parallel_map([query], min_len, max_hits, chains_per_strand, max_report, band, **chain_params)[0]
+
+    def dev_revcomp(self, d_qbytes, d_qoff, n, d_out_bytes, d_out_off, stream=None, slot=0):
+        """device-resident doubled batch: query 2i of (d_out_bytes, d_out_off) is read i as given, query 2i + 1 its reverse
+        complement; the caller sizes d_out_bytes at 2 x the reads' bytes and d_out_off at 2 n + 1 u64"""
+        _check(self._L.awry_dev_revcomp(self._h, slot, d_qbytes, d_qoff, n, d_out_bytes, d_out_off, stream))
+
+    def dev_map_select(self, d_aln_off, d_alns, d_chains, d_chain_status, n, chains_per_strand, max_report, d_n_maps, d_read_status=None,
+                       d_map_off=None, d_maps=None, d_sel=None, d_pos=None, stream=None, slot=0):
+        """device-resident rank / redundancy / report / MAPQ over the alignment records of a doubled batch of n reads (24-byte
+        alignment and 32-byte chain records of query x at [d_aln_off[x], d_aln_off[x+1]), 2 n + 1 offsets): d_map_off None = the count
+        pass (d_n_maps[n] u64, optional d_read_status[n]); else the fill pass writing 32-byte records at d_maps[d_map_off[i] ..) and,
+        optionally, per record the alignment's index (d_sel, u32) and the position of t_begin (d_pos, 2 u64); scan d_n_maps with
+        dev_scan_counts in between"""
+        _check(self._L.awry_dev_map_select(self._h, slot, d_aln_off, d_alns, d_chains, d_chain_status, n, int(chains_per_strand), int(max_report),
+                                           d_n_maps, d_read_status, d_map_off, d_maps, d_sel, d_pos, stream))
 
     def debug_rank_all(self, rows: np.ndarray, slot=0) -> np.ndarray:
         """Occ of every non-sentinel symbol at each row through the kernels' all-symbol rank -> uint64[len(rows), S]

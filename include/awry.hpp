@@ -395,6 +395,47 @@ class FmIndex {
     awry_free_buffer(aoff); awry_free_buffer(ch); awry_free_buffer(al); awry_free_buffer(coff); awry_free_buffer(cg); awry_free_buffer(st);
     return out;
   }
+  // reads mapped on both strands (no counterpart in the reference; the definition is in awry_hip.h): per read its best alignments
+  // over the read as given (strand 0) and its reverse complement (strand 1), the primary first -- where t_begin lies (record and
+  // offset), the text span, the edit count, the chain it came from, a mapping quality (0 for the records after the first, which
+  // carry AWRY_MAP_SECONDARY in flags) and the CIGAR of the aligned strand against the forward text.  A read that maps nowhere has
+  // no records.
+  struct Mapping {
+    awry_pos_t pos;
+    uint64_t t_begin, t_end;
+    uint32_t edits, chain_score, chain_index;
+    uint8_t strand, mapq;
+    uint16_t flags;
+    std::vector<uint32_t> cigar;
+    std::string cigar_string() const {
+      std::string out;
+      for (uint32_t run : cigar) {
+        const uint32_t op = run & 15u;
+        out += std::to_string(run >> 4);
+        out += op == 7 ? '=' : op == 8 ? 'X' : op == 1 ? 'I' : 'D';
+      }
+      return out;
+    }
+  };
+  template <class StrRange>
+  std::vector<std::vector<Mapping>> parallel_map(const StrRange& queries, uint32_t min_len = 12, uint64_t max_hits = 50, uint64_t chains_per_strand = 4,
+                                                 uint64_t max_report = 1, uint32_t band = 4, ChainParams p = ChainParams(),
+                                                 std::vector<uint8_t>* status = nullptr) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* moff = nullptr; awry_map_t* mp = nullptr; awry_pos_t* ps = nullptr; uint64_t* coff = nullptr; uint32_t* cg = nullptr; uint8_t* st = nullptr;
+    check(awry_map_batch(h_, bytes.data(), off.data(), n, min_len, max_hits, p.max_seeds, p.lookback, p.max_gap, p.max_skew, p.min_score,
+                         chains_per_strand, max_report, band, &moff, &mp, &ps, &coff, &cg, &st));
+    std::vector<std::vector<Mapping>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = moff[i]; j < moff[i + 1]; j++)
+        out[i].push_back({ps[j], mp[j].t_begin, mp[j].t_end, mp[j].edits, mp[j].chain_score, mp[j].chain_index, mp[j].strand, mp[j].mapq, mp[j].flags,
+                          std::vector<uint32_t>(cg + coff[j], cg + coff[j + 1])});
+    if (status) status->assign(st, st + n);
+    awry_free_buffer(moff); awry_free_buffer(mp); awry_free_buffer(ps); awry_free_buffer(coff); awry_free_buffer(cg); awry_free_buffer(st);
+    return out;
+  }
   // src/fm_index.rs:559-582, 585-593
   SearchRange update_range_with_symbol(SearchRange r, char symbol) {
     awry_range_t o;

@@ -378,7 +378,7 @@ int awry_align_edit_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64
  *   Seeds walked by an unreported chain stay used.  Chains of a query are reported in the order found: the first is the primary.
  * Records.  awry_chain_t: q_begin / t_begin come from the chain's first member, q_end / t_end are the maxima of q_begin + q_len /
  *   t_pos + q_len over its members, n_seeds counts them; the members are listed first to last, in sorted order.
- * Scope.  Forward strand only.  Indexes with bwt_len >= 2^32 => AWRY_ERR_ARG, as on the edit path (a small index on wide-row
+ * Scope.  The strand the query is given on; awry_map_batch (below) maps both.  Indexes with bwt_len >= 2^32 => AWRY_ERR_ARG, as on the edit path (a small index on wide-row
  *   replicas works).  No accelerator, seed-table length, row width, replica count or chunk capacity changes any output.
  * AWRY_ERR_ARG: max_seeds == 0 or > AWRY_CHAIN_MAX_SEEDS, lookback outside 1 .. AWRY_CHAIN_MAX_LOOKBACK, max_gap == 0, min_score
  * == 0, min_len == 0, max_hits == 0.  Malformed queries fail the batch with AWRY_ERR_INVALID_QUERY, as for SMEMs, and leave the
@@ -451,6 +451,48 @@ int awry_align_chains_batch(awry_index_t *idx, const uint8_t *qbytes, const uint
                             uint32_t min_score, uint64_t max_alignments, uint32_t band, uint64_t **aln_off_out,
                             awry_chain_t **chains_out, awry_aln_t **alns_out, uint64_t **cigar_off_out, uint32_t **cigar_out,
                             uint8_t **status_out);
+
+/* ---- map reads on both strands: revcomp seeds, ranked alignments, MAPQ (no counterpart in the reference) --------
+ * The end of the seed-chain-extend pipeline: reads in, ranked placements out -- strand, position, edits, CIGAR and a mapping
+ * quality.  Nucleotide indexes only (an amino index => AWRY_ERR_ARG).  Everything is integer arithmetic and every tie is broken
+ * explicitly.
+ * Reverse complement.  rc(q) of a query of L bytes is the byte string rc(q)[i] = ascii_of_index(comp(index_of_ascii(q[L-1-i]))),
+ *   comp on symbol indices: $0 -> 0, A1 -> T5, C2 -> G3, G3 -> C2, N4 -> N4, T5 -> A1.  So case is folded, U reads as T, every
+ *   other byte becomes 'N' and a sentinel stays a sentinel: a query the exact path rejects is rejected on either strand, and the
+ *   error names the read's own index.
+ * Candidates.  Parameters: those of awry_align_chains_batch with max_alignments named chains_per_strand = A, 1 <= A <=
+ *   AWRY_MAP_MAX_CHAINS = 8, and max_report = R, 1 <= R <= 2 A.  For read i and strand s (0 forward, 1 reverse) let (c_j, a_j),
+ *   j = 0 .. min(n_chains, A) - 1, be the chain records and alignments awry_align_chains_batch(.., max_alignments = A, band)
+ *   returns for q (s = 0) or rc(q) (s = 1).  A candidate is a pair (s, j) with a_j.status == AWRY_ALN_OK.  Reverse-strand spans
+ *   and CIGARs are left as computed on rc(q) against the forward text (the SAM convention): no CIGAR is reversed.
+ * Rank.  The candidates are sorted ascending by (edits, -chain score, strand, t_begin, j): a total order.
+ * Redundancy.  Walking the sorted list, a candidate is dropped if a better-ranked KEPT candidate of the SAME strand has an
+ *   intersecting text span, max(b1, b2) < min(e1, e2); an empty span intersects nothing.  Two chains the chainer split at one
+ *   locus count once; the same span on opposite strands (a reverse-palindromic read) counts twice.
+ * Report.  The first min(R, kept) kept candidates are the read's records, the primary first; those after it carry the flag
+ *   AWRY_MAP_SECONDARY.  A read with no kept candidate has no records and is not an error.
+ * Status and MAPQ.  status[i] is AWRY_Q_SEED_CAP if either strand's chaining status is, else AWRY_Q_OK.  MAPQ of the primary: 0
+ *   if the status is AWRY_Q_SEED_CAP; else 60 if there is no second kept candidate (whether or not R would report it); else
+ *   min(60, 10 * (e2 - e1)), e1 and e2 the edits of the first and second kept candidates.  MAPQ of secondaries is 0.
+ * Record.  awry_map_t, 32 bytes: t_begin / t_end / edits of the alignment, chain_score, chain_index = j, strand, mapq, flags.
+ *
+ * awry_map_batch: CSR output, library-allocated (awry_free_buffer): the records of read i are maps[map_off[i] .. map_off[i+1]),
+ * pos[] holds, record by record, what awry_get_seq_location(t_begin) returns, the runs of record c are cigar[cigar_off[c] ..
+ * cigar_off[c+1]), status[n] as above.  All but map_off_out nullable; cigar_off_out and cigar_out are given or omitted together.
+ * Errors and index restrictions: those of awry_align_chains_batch (bwt_len >= 2^32 or a wide-row replica => AWRY_ERR_ARG, a read
+ * longer than AWRY_CHAIN_ALIGN_MAX_LEN or rejected on the exact path => AWRY_ERR_INVALID_QUERY, no HBM for the text copy =>
+ * AWRY_ERR_OOM, no replica => AWRY_ERR_NO_DEVICE); A outside 1 .. 8, R outside 1 .. 2 A or band > 8 => AWRY_ERR_ARG.  The
+ * out-pointers are written only on success.  Reads are uploaded once per chunk and expanded to both strands on the device; the
+ * alignment count pass (spans, edits) runs over every candidate, the CIGAR fill pass only over the records that are reported, in
+ * sub-batches (AWRY_CHAIN_ALIGN_SUB_BATCH).  The capacity fallback splits a chunk between reads, never between a read's strands.
+ * No accelerator, seed-table length, replica count, chunk capacity, sub-batch size or split of a chunk changes any output. */
+enum { AWRY_MAP_MAX_CHAINS = 8 };
+enum { AWRY_MAP_SECONDARY = 1 };
+typedef struct { uint64_t t_begin, t_end; uint32_t edits, chain_score, chain_index; uint8_t strand, mapq; uint16_t flags; } awry_map_t;
+int awry_map_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len, uint64_t max_hits,
+                   uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score,
+                   uint64_t chains_per_strand, uint64_t max_report, uint32_t band, uint64_t **map_off_out, awry_map_t **maps_out,
+                   awry_pos_t **pos_out, uint64_t **cigar_off_out, uint32_t **cigar_out, uint8_t **status_out);
 
 /* releases an array one of the calls above (or awry_locate / awry_read_query_file) returned.  Result arrays are pinned
  * host memory recycled through a process-wide pool (the device writes results straight into them); never pass them to
@@ -684,6 +726,27 @@ int awry_dev_align_chains_tally(awry_index_t *idx, int slot, const uint8_t *d_qb
                                 const uint32_t *d_chain_query, const uint64_t *d_member_off, const awry_seed_t *d_members,
                                 uint64_t m, uint32_t band, awry_aln_t *d_alns, uint64_t *d_n_ops, const uint64_t *d_cigar_off,
                                 uint32_t *d_cigar, uint64_t *d_tally, void *stream);
+/* The doubled batch of awry_map_batch, device-resident: query 2i of the output is read i as given, query 2i + 1 is rc(read i) (the
+ * definition is stated there); d_out_off[2i] = 2 (d_qoff[i] - d_qoff[0]), d_out_off[2i+1] = that + L_i, d_out_off[2n] = 2
+ * (d_qoff[n] - d_qoff[0]).  The caller sizes d_out_bytes at 2 x the reads' bytes (plus what the consuming entry point wants
+ * readable past the end) and d_out_off at 2 n + 1; nothing is written past either.  A group of 16 lanes owns a read; loads and
+ * both stores are contiguous per group.  Nucleotide indexes only (amino => AWRY_ERR_ARG).  Queued on `stream`, no
+ * synchronisation. */
+int awry_dev_revcomp(awry_index_t *idx, int slot, const uint8_t *d_qbytes, const uint64_t *d_qoff, uint64_t n,
+                     uint8_t *d_out_bytes, uint64_t *d_out_off, void *stream);
+/* Rank, redundancy, report and MAPQ of awry_map_batch over a caller's alignment records of a doubled batch of n reads: the
+ * alignments of query x (strand x & 1 of read x >> 1) are d_alns / d_chains [d_aln_off[x] .. d_aln_off[x+1]) -- d_aln_off has
+ * 2 n + 1 entries, of each query the first min(count, chains_per_strand) are candidates, only d_chains[].score is read --
+ * and d_chain_status[2n] (nullable) is the chaining status per query.  The two-call protocol of awry_dev_smems: d_map_off ==
+ * NULL is the count pass -> d_n_maps[n] (u64, ready for awry_dev_scan_counts) and optional d_read_status[n]; otherwise the fill
+ * pass writes the records of read i at d_maps[d_map_off[i] ..) and never a slot at or beyond d_map_off[i+1], and per record
+ * (both nullable) d_sel[] = the index of its alignment in d_alns (u32) and d_pos[] = record and offset of t_begin.  One read
+ * per lane; the candidates are ranked by repeated selection of the smallest key, so no array lives in registers.  Queued on
+ * `stream`, no synchronisation. */
+int awry_dev_map_select(awry_index_t *idx, int slot, const uint64_t *d_aln_off, const awry_aln_t *d_alns,
+                        const awry_chain_t *d_chains, const uint8_t *d_chain_status, uint64_t n, uint32_t chains_per_strand,
+                        uint32_t max_report, uint64_t *d_n_maps, uint8_t *d_read_status, const uint64_t *d_map_off,
+                        awry_map_t *d_maps, uint32_t *d_sel, awry_pos_t *d_pos, void *stream);
 /* test hook of the all-symbol rank primitive: d_occ[i * S + s - 1] = Occ(s, d_rows[i]) for every non-sentinel symbol index s
  * (S = 5 nucleotide, 21 amino; inclusive of the row, as awry_update_range uses it); rows >= bwt_len give zeros */
 int awry_debug_rank_all(awry_index_t *idx, int slot, const void *d_rows, uint64_t n, void *d_occ, void *stream);

@@ -15,7 +15,8 @@ use std::os::raw::c_char;
 use std::path::{Path, PathBuf};
 use std::sync::Arc;
 
-use awry_hip_sys::{self as sys, awry_aln_t as RawAln, awry_anchor_t as RawAnchor, awry_chain_t as RawChain, awry_seed_t as RawSeed};
+use awry_hip_sys::{self as sys, awry_aln_t as RawAln, awry_anchor_t as RawAnchor, awry_chain_t as RawChain, awry_map_t as RawMap, awry_pos_t as RawPos,
+                   awry_seed_t as RawSeed};
 use rayon::iter::{IndexedParallelIterator, IntoParallelIterator, IntoParallelRefIterator, ParallelIterator};
 
 use crate::{
@@ -238,6 +239,23 @@ pub struct ChainAlignment {
     pub t_end: u64,
     pub edits: u32,
     pub status: u32,
+    pub cigar: Vec<u32>,
+}
+
+/// One reported alignment of [`FmIndex::parallel_map`]: where `t_begin` lies, the text span `[t_begin, t_end)`, the edit count, the
+/// chain it came from, the strand (0 the read as given, 1 its reverse complement), the mapping quality, the flags
+/// (`AWRY_MAP_SECONDARY` on every record after the first) and the CIGAR runs of the aligned strand against the forward text.
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct Mapping {
+    pub position: LocalizedSequencePosition,
+    pub t_begin: u64,
+    pub t_end: u64,
+    pub edits: u32,
+    pub chain_score: u32,
+    pub chain_index: u32,
+    pub strand: u8,
+    pub mapq: u8,
+    pub flags: u16,
     pub cigar: Vec<u32>,
 }
 
@@ -688,6 +706,72 @@ impl FmIndex {
             sys::awry_free_buffer(aln_off as *mut std::os::raw::c_void);
             sys::awry_free_buffer(chains as *mut std::os::raw::c_void);
             sys::awry_free_buffer(alns as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(cigar_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(cigar as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(st as *mut std::os::raw::c_void);
+        }
+        Ok(out)
+    }
+
+    /// Reads mapped on both strands (no counterpart in the reference; the definition is in include/awry_hip.h): per read its best
+    /// alignments over the read and its reverse complement, the primary first, at most `max_report` of them (1..=2 *
+    /// `chains_per_strand`, which is 1..=8), each with strand, position, edit count, MAPQ and CIGAR.  And per read whether one of
+    /// its strands was abandoned because it has more than `params.max_seeds` seeds (its MAPQ is then 0).
+    pub fn parallel_map<'a>(
+        &self,
+        queries: impl ParallelIterator<Item = &'a str>,
+        min_len: u32,
+        max_hits: u64,
+        chains_per_strand: u64,
+        max_report: u64,
+        band: u32,
+        params: ChainParams,
+    ) -> Result<(Vec<Vec<Mapping>>, Vec<bool>), AwryError> {
+        let csr = to_csr(queries);
+        let n = csr.offsets.len() - 1;
+        let mut map_off: *mut u64 = std::ptr::null_mut();
+        let mut maps: *mut RawMap = std::ptr::null_mut();
+        let mut pos: *mut RawPos = std::ptr::null_mut();
+        let mut cigar_off: *mut u64 = std::ptr::null_mut();
+        let mut cigar: *mut u32 = std::ptr::null_mut();
+        let mut st: *mut u8 = std::ptr::null_mut();
+        check(unsafe {
+            sys::awry_map_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, min_len, max_hits, params.max_seeds, params.lookback,
+                                params.max_gap, params.max_skew, params.min_score, chains_per_strand, max_report, band, &mut map_off, &mut maps, &mut pos,
+                                &mut cigar_off, &mut cigar, &mut st)
+        })?;
+        let out = unsafe {
+            let off = std::slice::from_raw_parts(map_off, n + 1);
+            let total = off[n] as usize;
+            let mp: &[RawMap] = if total == 0 { &[] } else { std::slice::from_raw_parts(maps, total) };
+            let ps: &[RawPos] = if total == 0 { &[] } else { std::slice::from_raw_parts(pos, total) };
+            let coff = std::slice::from_raw_parts(cigar_off, total + 1);
+            let runs: &[u32] = if coff[total] == 0 { &[] } else { std::slice::from_raw_parts(cigar, coff[total] as usize) };
+            let status: &[u8] = if n == 0 { &[] } else { std::slice::from_raw_parts(st, n) };
+            let per = (0..n)
+                .map(|i| {
+                    (off[i] as usize..off[i + 1] as usize)
+                        .map(|j| Mapping {
+                            position: LocalizedSequencePosition::new(ps[j].seq_idx as usize, ps[j].local_pos as usize),
+                            t_begin: mp[j].t_begin,
+                            t_end: mp[j].t_end,
+                            edits: mp[j].edits,
+                            chain_score: mp[j].chain_score,
+                            chain_index: mp[j].chain_index,
+                            strand: mp[j].strand,
+                            mapq: mp[j].mapq,
+                            flags: mp[j].flags,
+                            cigar: runs[coff[j] as usize..coff[j + 1] as usize].to_vec(),
+                        })
+                        .collect::<Vec<_>>()
+                })
+                .collect::<Vec<_>>();
+            (per, status.iter().map(|&s| s == 8).collect::<Vec<_>>())  // AWRY_Q_SEED_CAP
+        };
+        unsafe {
+            sys::awry_free_buffer(map_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(maps as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(pos as *mut std::os::raw::c_void);
             sys::awry_free_buffer(cigar_off as *mut std::os::raw::c_void);
             sys::awry_free_buffer(cigar as *mut std::os::raw::c_void);
             sys::awry_free_buffer(st as *mut std::os::raw::c_void);
