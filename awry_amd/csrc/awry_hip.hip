@@ -236,6 +236,12 @@ int awry_set_seed_kmer_len(awry_index_t* idx, int k) {
 
 int awry_debug_set_count_kernel(int mode) { g_count_kernel.store(mode); return AWRY_OK; }
 int awry_debug_force_wide_rows(int on) { g_force_wide.store(on ? 1 : 0); return AWRY_OK; }
+int awry_debug_set_max_blocks(int blocks) {
+  if (blocks < 0) { g_last_error = "awry_debug_set_max_blocks: negative bound"; return AWRY_ERR_ARG; }
+  g_max_blocks.store(blocks);
+  return AWRY_OK;
+}
+int awry_debug_max_blocks(void) { return g_max_blocks.load(); }
 
 const char* awry_count_schedule(const awry_index_t* idx, int L) {
   static const char* names[] = {"count_nt2_quad_kernel", "count_nt2_chunk_kernel", "count_nt2_quad4_kernel",

@@ -127,7 +127,7 @@ void launch_locate(Replica& r, const uint64_t* d_range_start, int rs_stride, con
   if (total == 0) return;
   unsigned long long* ctr = next_counter(r, s);
   const uint64_t tiles = (total + LOC_TILE - 1) / LOC_TILE;
-  const dim3 g((unsigned)std::min<uint64_t>(tiles, (uint64_t)r.num_cus * 8)), b(256);
+  const dim3 g((unsigned)std::min<uint64_t>(tiles, bound_blocks((uint64_t)r.num_cus * 8))), b(256);
   // consecutive tiles a block draws at a time (one search of the whole offset array per run): long enough to amortise
   // that search, short enough that every block still draws several runs and the launch ends evenly
   const uint32_t run_len = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, tiles / ((uint64_t)g.x * 4)));
@@ -203,7 +203,7 @@ template <class K>
 unsigned resident_grid(const Replica& r, K kernel) {
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 2; }
-  return (unsigned)r.num_cus * (unsigned)per_cu;
+  return (unsigned)bound_blocks((uint64_t)r.num_cus * (unsigned)per_cu);
 }
 
 // d_lens != nullptr: read q has d_lens[q] letters (1..L) in its W = ceil(L / 32) words; else every read has L letters

@@ -198,9 +198,23 @@ Replica& replica(awry_index* ix, int slot) {
   return r;
 }
 
+// awry_debug_set_max_blocks: an upper bound on the block count of a launch, read at every launch; 0 (the default): none.  For
+// tests: on a grid of one block every lane of a stride loop takes item after item, and scratch indexed by grid lane is reused
+// from trip to trip, at batches of a few hundred items.  It bounds grid_for, resident_grid and the block counts the launchers
+// of launchers.h work out themselves from num_cus or a byte budget (launch_locate, launch_chain, launch_chain_align,
+// launch_edit_align); scratch sized from such a grid is sized from the bounded one.  It does not bound grids that are a function
+// of the data (launch_scan: one tile per block) nor the grids of the k-mer count schedules (num_cus * 8 lists, probe_resume_per_cu,
+// lcx_reads_grid), whose list layout is tied to the block count, nor the other grids a call site writes out itself from num_cus
+// (the amino two-phase schedule, the LIST_GLOBAL pass of count_scalar_kernel, stream_copy_kernel).
+std::atomic<int> g_max_blocks{0};
+uint64_t bound_blocks(uint64_t blocks) {
+  const int m = g_max_blocks.load();
+  return m > 0 ? std::min<uint64_t>(blocks, (uint64_t)m) : blocks;
+}
+
 int grid_for(const Replica& r, uint64_t work_items, int per_block, int blocks_per_cu = 8) {
   uint64_t want = (work_items + per_block - 1) / per_block;
-  uint64_t cap = (uint64_t)r.num_cus * blocks_per_cu;
+  uint64_t cap = bound_blocks((uint64_t)r.num_cus * blocks_per_cu);
   return (int)std::max<uint64_t>(1, std::min(want, cap));
 }
 

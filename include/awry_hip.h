@@ -97,6 +97,15 @@ int awry_debug_set_count_kernel(int mode);
  * the reference is u64 throughout, src/search.rs:7).  on != 0 makes replicas placed AFTERWARDS (awry_set_devices) take
  * those kernels whatever the index size -- for tests: a real index of that size takes an hour of host SA-IS to build. */
 int awry_debug_force_wide_rows(int on);
+/* An upper bound on the block count of a launch (process-wide, read at every launch; 0, the default: none; negative:
+ * AWRY_ERR_ARG).  For tests: on a grid of one block the lanes of the stride-loop kernels take item after item at batches of a
+ * few hundred items.  Bounded: the grids that grid_for and resident_grid size (the read pipelines, the generic count kernel, the
+ * mismatch and class-pattern search, the locate walk passes, index construction) and the tile grid of locate.  Not bounded:
+ * grids that are a function of the data (the prefix scans) and the grids the k-mer count schedules, the amino two-phase
+ * schedule, the list passes of the generic count kernel and the stream copy size themselves from the CU count or an occupancy
+ * query.  Results do not depend on it. */
+int awry_debug_set_max_blocks(int blocks);
+int awry_debug_max_blocks(void);
 /* device pointer of replica `slot`'s dense SA (u32 SA[j * ratio]) or NULL -- for tests that dump it */
 const void *awry_debug_dense_sa(const awry_index_t *idx, int slot);
 /* name(s) of the kernel(s) awry_dev_count_nt2 launches for k-mers of length L on replica 0 (for profiling reports) */
