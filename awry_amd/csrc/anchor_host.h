@@ -1,5 +1,6 @@
 // anchor_host.h -- shard drivers of anchors (greedy longest-match factorisation), of SMEMs (all super-maximal exact matches) and
-// of locating either: one driver over awry_anchor_t records, parameterised over the launcher that finds them
+// of locating either: one driver over awry_anchor_t records, parameterised over the launcher that finds them.  Its device part,
+// the record-locate stage (find_records, locate_records), is also the first stage of chain_chunk (chain_host.h).
 // A part of awry_hip.hip (one translation unit): included there, in order, and not on its own.
 #pragma once
 
@@ -18,11 +19,7 @@ void require_anchor_args(uint32_t min_len, int skip) {
 
 // Located hits a chunk may hold on the device; a chunk with more, and more than one query, is split in halves and each half
 // redone in query order.  Read per call: AWRY_ANCHOR_HIT_CAP (tests shrink it).
-uint64_t anchor_hit_cap() {
-  const char* e = getenv("AWRY_ANCHOR_HIT_CAP");
-  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
-  return v ? std::min<uint64_t>(v, 1ull << 31) : (1ull << 26);
-}
+uint64_t anchor_hit_cap() { return env_cap("AWRY_ANCHOR_HIT_CAP", 1ull << 26, 1ull << 31); }
 
 void require_smem_args(uint32_t min_len) {
   if (min_len < 1) throw ArgError("min_len must be at least 1");
@@ -48,8 +45,78 @@ struct AnchorHits {  // one shard's result, in query order
   uint64_t nhits = 0;
 };
 
-// count pass, scan, fill pass; with max_hits != 0 also ranges, scan of the located counts and the locate pipeline over the
-// flat anchor list.  false: the chunk's located hits exceed the capacity and it holds more than one query -- nothing appended
+// ---- the record-locate stage: shared by anchor_chunk, which copies its results out, and chain_chunk (chain_host.h), which goes
+// on to seeds on the device --------------------------------------------------------------------------------------------------------
+
+struct LocatedRecords {  // what the stage leaves on the device
+  ChunkBuffers cb, up;                         // the chunk's queries; `up` holds the reads as given when every read is two queries
+  DevBuf<uint64_t> n_rec, rec_off, scratch;    // per query: records, their offsets; the scratch of scans over the queries
+  DevBuf<Anchor> rec;                          // the `total` records
+  DevBuf<uint64_t> ranges, located, hit_off, lscratch;  // per record: rows, hits located (0 over max_hits), their offsets
+  DevBuf<uint64_t> gpos, pos;                  // the `nhits` located hits: text positions, and on request (record, offset) pairs
+  uint64_t total = 0, nhits = 0;
+  void release_records() { rec.reset(); ranges.reset(); located.reset(); hit_off.reset(); lscratch.reset(); }
+};
+
+// Upload, count pass, scan, status check, fill pass; with max_hits != 0 also the records' ranges and the scan of the located
+// counts.  copies == 2: the reads are uploaded once and expanded on the device into the doubled batch (launch_strand_expand: query
+// 2i = read i, query 2i + 1 = its reverse complement); everything after that is over the 2 (c.hi - c.lo) queries, a rejected query
+// is raised under its read's index, and the capacity test counts reads, so a read's two strands are never split.  `what` names the
+// records in the message of a chunk with 2^32 of them.  false: the chunk's located hits exceed the capacity and it holds more than
+// one read -- nothing has been located.  Two stream synchronisations (one with max_hits == 0 or without records).
+template <class Find>
+bool find_records(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, const Find& find, uint64_t max_hits, int copies, const char* what,
+                  LocatedRecords& L) {
+  const hipStream_t s = r.stream;
+  const uint64_t nreads = c.hi - c.lo, n = copies * nreads;
+  ChunkBuffers& cb = L.cb;
+  upload_chunk(r, copies == 2 ? L.up : cb, qbytes, qoff, c);
+  if (copies == 2) {
+    const ChunkBuffers& up = L.up;
+    const uint64_t nbytes = up.h_off[nreads];
+    cb.q.alloc(2 * nbytes + 16);
+    cb.off.alloc(n + 1);
+    cb.status.alloc(std::max<uint64_t>(n, 1));
+    cb.h_off.resize(n + 1);
+    for (uint64_t i = 0; i < nreads; i++) {
+      cb.h_off[2 * i] = 2 * up.h_off[i];
+      cb.h_off[2 * i + 1] = 2 * up.h_off[i] + (up.h_off[i + 1] - up.h_off[i]);
+    }
+    cb.h_off[n] = 2 * nbytes;
+    cb.h_status.resize(n);
+    launch_strand_expand(r, up.q.p, up.off.p, nreads, cb.q.p, cb.off.p, s);
+  }
+  L.n_rec.alloc(n); L.rec_off.alloc(n + 1); L.scratch.alloc(scan_tiles(n) + 1);
+  find(r, cb.q.p, cb.off.p, n, L.n_rec.p, nullptr, nullptr, cb.status.p, s);
+  launch_scan(r, L.n_rec.p, n, L.rec_off.p, L.scratch.p, s);
+  HIP_CHECK(hipMemcpyAsync(&L.total, L.rec_off.p + n, 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  for (uint64_t i = 0; i < n; i++)
+    if (cb.h_status[i] != Q_OK) raise_bad_query(c.lo + i / copies, cb.h_status[i]);  // the read's own index
+  const uint64_t total = L.total;
+  if (total >= (1ull << 32)) throw ArgError(std::string("a chunk of queries with 2^32 ") + what + " or more");
+  if (!total) return true;
+  L.rec.alloc(total);
+  if (max_hits) { L.ranges.alloc(2 * total); L.located.alloc(total); L.hit_off.alloc(total + 1); L.lscratch.alloc(scan_tiles(total) + 1); }
+  find(r, cb.q.p, cb.off.p, n, nullptr, L.rec_off.p, L.rec.p, nullptr, s);
+  if (!max_hits) return true;
+  launch_anchor_ranges(r, L.rec.p, total, max_hits, L.ranges.p, L.located.p, s);
+  launch_scan(r, L.located.p, total, L.hit_off.p, L.lscratch.p, s);
+  HIP_CHECK(hipMemcpyAsync(&L.nhits, L.hit_off.p + total, 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  return !(L.nhits > anchor_hit_cap() && nreads > 1);
+}
+
+// the locate pipeline over the flat record list: text positions, and with want_pos (record, offset) pairs
+void locate_records(Replica& r, LocatedRecords& L, bool want_pos) {
+  if (!L.nhits) return;
+  L.gpos.alloc(L.nhits);
+  if (want_pos) L.pos.alloc(2 * L.nhits);
+  launch_locate(r, L.ranges.p, 2, L.hit_off.p, L.total, L.nhits, L.gpos.p, L.pos.p, r.stream);
+}
+
+// the stage with max_hits != 0, or the records alone; then the copy-out.  false: over capacity (find_records) -- nothing appended
 template <class Find>
 bool anchor_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, const Find& find, uint64_t max_hits, bool want_pos, bool want_gpos,
                   AnchorHits& out) {
@@ -57,58 +124,24 @@ bool anchor_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard
   const uint64_t n = c.hi - c.lo;
   for (uint64_t i = c.lo; i < c.hi; i++)
     if (qoff[i + 1] >= qoff[i] && qoff[i + 1] - qoff[i] >= (1ull << 32)) throw ArgError("a query of 2^32 letters or more");
-  ChunkBuffers cb;
-  upload_chunk(r, cb, qbytes, qoff, c);
-  DevBuf<uint64_t> na(n), aoff(n + 1), scratch(scan_tiles(n) + 1);
-  find(r, cb.q.p, cb.off.p, n, na.p, nullptr, nullptr, cb.status.p, s);
-  launch_scan(r, na.p, n, aoff.p, scratch.p, s);
-  uint64_t total = 0;
-  HIP_CHECK(hipMemcpyAsync(&total, aoff.p + n, 8, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  check_status(cb, c.lo);
-  if (total >= (1ull << 32)) throw ArgError("a chunk of queries with 2^32 anchors or more");
-  DevBuf<Anchor> d_anchors(std::max<uint64_t>(total, 1));
-  find(r, cb.q.p, cb.off.p, n, nullptr, aoff.p, d_anchors.p, nullptr, s);
-  DevBuf<uint64_t> ranges, located, hoff, lscratch, d_gpos, d_pos;
-  uint64_t nhits = 0;
-  if (max_hits && total) {
-    ranges.alloc(2 * total); located.alloc(total); hoff.alloc(total + 1); lscratch.alloc(scan_tiles(total) + 1);
-    launch_anchor_ranges(r, d_anchors.p, total, max_hits, ranges.p, located.p, s);
-    launch_scan(r, located.p, total, hoff.p, lscratch.p, s);
-    HIP_CHECK(hipMemcpyAsync(&nhits, hoff.p + total, 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (nhits > anchor_hit_cap() && n > 1) return false;
-    if (nhits) {
-      d_gpos.alloc(nhits);
-      if (want_pos) d_pos.alloc(2 * nhits);
-      launch_locate(r, ranges.p, 2, hoff.p, total, nhits, d_gpos.p, d_pos.p, s);
-    }
-  }
+  LocatedRecords L;
+  if (!find_records(r, qbytes, qoff, c, find, max_hits, 1, "anchors", L)) return false;
+  locate_records(r, L, want_pos);
+  const uint64_t total = L.total, nhits = L.nhits;
   const size_t at_q = out.n_anchors.size(), at_a = out.anchors.size(), at_h = (size_t)out.nhits;
   out.n_anchors.resize(at_q + n);
-  HIP_CHECK(hipMemcpyAsync(out.n_anchors.data() + at_q, na.p, n * 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(out.n_anchors.data() + at_q, L.n_rec.p, n * 8, hipMemcpyDeviceToHost, s));
   out.anchors.resize(at_a + total);
-  if (total) HIP_CHECK(hipMemcpyAsync(out.anchors.data() + at_a, d_anchors.p, total * sizeof(Anchor), hipMemcpyDeviceToHost, s));
+  if (total) HIP_CHECK(hipMemcpyAsync(out.anchors.data() + at_a, L.rec.p, total * sizeof(Anchor), hipMemcpyDeviceToHost, s));
   if (max_hits) {
     out.located.resize(at_a + total);
-    if (total) HIP_CHECK(hipMemcpyAsync(out.located.data() + at_a, located.p, total * 8, hipMemcpyDeviceToHost, s));
-    if (want_gpos) { out.gpos.resize(at_h + nhits); if (nhits) HIP_CHECK(hipMemcpyAsync(out.gpos.data() + at_h, d_gpos.p, nhits * 8, hipMemcpyDeviceToHost, s)); }
-    if (want_pos) { out.pos.resize(at_h + nhits); if (nhits) HIP_CHECK(hipMemcpyAsync(out.pos.data() + at_h, d_pos.p, nhits * 16, hipMemcpyDeviceToHost, s)); }
+    if (total) HIP_CHECK(hipMemcpyAsync(out.located.data() + at_a, L.located.p, total * 8, hipMemcpyDeviceToHost, s));
+    if (want_gpos) { out.gpos.resize(at_h + nhits); if (nhits) HIP_CHECK(hipMemcpyAsync(out.gpos.data() + at_h, L.gpos.p, nhits * 8, hipMemcpyDeviceToHost, s)); }
+    if (want_pos) { out.pos.resize(at_h + nhits); if (nhits) HIP_CHECK(hipMemcpyAsync(out.pos.data() + at_h, L.pos.p, nhits * 16, hipMemcpyDeviceToHost, s)); }
     out.nhits += nhits;
   }
   HIP_CHECK(hipStreamSynchronize(s));
   return true;
-}
-
-template <class Find>
-void anchor_range(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, const Find& find, uint64_t max_hits, bool want_pos, bool want_gpos,
-                  AnchorHits& out) {
-  if (c.hi <= c.lo) return;
-  if (anchor_chunk(r, qbytes, qoff, c, find, max_hits, want_pos, want_gpos, out)) return;
-  const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order
-  anchor_range(r, qbytes, qoff, Shard{c.lo, mid}, find, max_hits, want_pos, want_gpos, out);
-  anchor_range(r, qbytes, qoff, Shard{mid, c.hi}, find, max_hits, want_pos, want_gpos, out);
 }
 
 // the batch entry points' common body: shards over the replicas, results stitched in query order into pinned-pool arrays.
@@ -119,35 +152,24 @@ void anchor_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, 
   std::vector<AnchorHits> res(std::max<size_t>(1, idx->reps.size()));
   for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
     HIP_CHECK(hipSetDevice(r.device));
-    for (Shard c : chunk_queries(qoff, sh.lo, sh.hi)) anchor_range(r, qbytes, qoff, c, find, max_hits, hits_out != nullptr, global_pos_out != nullptr, res[g]);
+    for (Shard c : chunk_queries(qoff, sh.lo, sh.hi))
+      halve_until_fits(c, [&](Shard h) { return anchor_chunk(r, qbytes, qoff, h, find, max_hits, hits_out != nullptr, global_pos_out != nullptr, res[g]); });
   });
   MBuf<uint64_t> aoff, hoff, gp;
   MBuf<awry_anchor_t> anchors;
   MBuf<awry_pos_t> hits;
-  aoff.grow(n + 1);
-  aoff.p[0] = 0;
-  uint64_t q = 0, total = 0, nhits = 0;
-  for (auto& x : res)
-    for (uint64_t c : x.n_anchors) { total += c; aoff.p[++q] = total; }
-  require(q == n, "internal: shard results do not cover the batch");
-  anchors.grow(std::max<uint64_t>(1, total));
-  if (max_hits) { hoff.grow(total + 1); hoff.p[0] = 0; }
-  uint64_t at = 0;
-  for (auto& x : res) {
-    if (!x.anchors.empty()) pool_memcpy(anchors.p + at, x.anchors.data(), x.anchors.size() * sizeof(awry_anchor_t));
-    if (max_hits)
-      for (size_t j = 0; j < x.located.size(); j++) { nhits += x.located[j]; hoff.p[at + j + 1] = nhits; }
-    at += x.anchors.size();
+  const uint64_t total = stitch_offsets(res, &AnchorHits::n_anchors, n, aoff);
+  require(stitch_concat(res, &AnchorHits::anchors, anchors) == total, "internal: shard results do not cover the anchors");
+  if (max_hits) {  // the located counts are per anchor: their offsets run over the whole batch's anchors
+    hoff.grow(total + 1);
+    hoff.p[0] = 0;
+    uint64_t at = 0, nhits = 0;
+    for (auto& x : res)
+      for (uint64_t c : x.located) { require(at < total, "internal: shard results do not cover the anchors"); nhits += c; hoff.p[++at] = nhits; }
+    require(at == total, "internal: shard results do not cover the anchors");
   }
-  require(at == total, "internal: shard results do not cover the anchors");
-  if (hits_out) hits.grow(std::max<uint64_t>(1, nhits));
-  if (global_pos_out) gp.grow(std::max<uint64_t>(1, nhits));
-  uint64_t ath = 0;
-  for (auto& x : res) {
-    if (hits_out && x.nhits) pool_memcpy(hits.p + ath, x.pos.data(), x.nhits * sizeof(awry_pos_t));
-    if (global_pos_out && x.nhits) pool_memcpy(gp.p + ath, x.gpos.data(), x.nhits * 8);
-    ath += x.nhits;
-  }
+  if (hits_out) stitch_concat(res, &AnchorHits::pos, hits);
+  if (global_pos_out) stitch_concat(res, &AnchorHits::gpos, gp);
   *anchor_off_out = aoff.release();
   *anchors_out = anchors.release();
   if (hit_off_out) *hit_off_out = hoff.release();

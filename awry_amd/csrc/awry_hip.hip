@@ -6,6 +6,7 @@
 #include "launchers.h"
 #include "host_count.h"
 #include "host_locate.h"
+#include "batch_host.h"
 #include "mismatch_host.h"
 #include "anchor_host.h"
 #include "chain_host.h"

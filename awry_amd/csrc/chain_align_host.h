@@ -1,6 +1,6 @@
-// chain_align_host.h -- the driver of awry_align_chains_batch: chain_chunk's flow through the chain fill pass (chain_host.h), then,
-// with chains and members still on the device, the first chains of every query, the alignment count pass, a scan, the fill pass
-// and the copy-out, in sub-batches
+// chain_align_host.h -- the driver of awry_align_chains_batch, a sink of chain_chunk (chain_host.h): with chains and members still
+// on the device, the first chains of every query (select_chains), then per sub-batch the alignment count pass, the CIGAR fill
+// (fill_cigar) and the copy-out.  map_host.h uses the same two stages.
 // A part of awry_hip.hip (one translation unit): included there, in order, after chain_host.h and edit_host.h, and not on its own.
 #pragma once
 
@@ -22,11 +22,7 @@ void require_chain_align_args(uint64_t max_alignments, uint32_t band) {
 
 // Chains the alignment passes take per launch: their staging (records, run counts, offsets, and the class lists: 52 B per chain,
 // plus the runs) is bounded by the sub-batch whatever the batch.  Read per call: AWRY_CHAIN_ALIGN_SUB_BATCH (tests shrink it).
-uint64_t chain_align_sub_batch() {
-  const char* e = getenv("AWRY_CHAIN_ALIGN_SUB_BATCH");
-  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
-  return v ? std::min<uint64_t>(v, 1ull << 24) : (1ull << 18);
-}
+uint64_t chain_align_sub_batch() { return env_cap("AWRY_CHAIN_ALIGN_SUB_BATCH", 1ull << 18, 1ull << 24); }
 
 struct ChainAlnHits {  // one shard's result, in query order
   std::vector<uint64_t> n_alns;  // per query
@@ -37,65 +33,92 @@ struct ChainAlnHits {  // one shard's result, in query order
   std::vector<uint32_t> cigar;  // the runs, back to back
 };
 
-// One chunk, from where chain_chunk's fill pass leaves it: the first min(n_chains, max_alignments) chains of every query (a count
-// per query, a scan, their records and queries, a scan of their member counts, their members), then per sub-batch the count
-// pass, the scan of the run counts and the fill pass, appended to `out`.
+// ---- the two stages shared with map_chunk (map_host.h) ----------------------------------------------------------------------------
+
+struct SelectedChains {  // the first chains of every query, as a chain list of their own on the device
+  DevBuf<uint64_t> taken, aoff, scratch;  // per query: chains taken, their offsets; the scratch of scans over the queries
+  DevBuf<uint32_t> query;                 // per selected chain: its query
+  DevBuf<Chain> chains;
+  DevBuf<uint64_t> mcnt, moff, mscratch;  // per selected chain: members, their offsets
+  DevBuf<Seed> members;
+  uint64_t total = 0, nsel = 0;           // selected chains, and their members
+  void release_scratch() { mcnt.reset(); mscratch.reset(); }
+};
+
+// The first min(n_chains, take) chains of each of v's nq queries: a count per query, a scan, their records and queries, a scan of
+// their member counts, their members.  Two stream synchronisations; without a chain only the first, and only `taken`, `aoff` and
+// `scratch` are allocated.  Returns with the gather queued.
+void select_chains(Replica& r, const ChainOnDevice& v, uint64_t nq, uint64_t take, SelectedChains& S) {
+  const hipStream_t s = r.stream;
+  S.taken.alloc(nq); S.aoff.alloc(nq + 1); S.scratch.alloc(scan_tiles(nq) + 1);
+  flat_launch(r, s, nq, chain_align_take_kernel, v.n_chains, nq, take, S.taken.p);
+  launch_scan(r, S.taken.p, nq, S.aoff.p, S.scratch.p, s);
+  HIP_CHECK(hipMemcpyAsync(&S.total, S.aoff.p + nq, 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  const uint64_t total = S.total;
+  require(total <= v.nchains && total < (1ull << 32), "internal: more chains selected than the chunk has");
+  if (!total) return;
+  S.query.alloc(total); S.chains.alloc(total); S.mcnt.alloc(total); S.moff.alloc(total + 1); S.mscratch.alloc(scan_tiles(total) + 1);
+  flat_launch(r, s, nq, chain_align_select_kernel, v.chain_off, v.chains, S.aoff.p, nq, S.query.p, S.chains.p, S.mcnt.p);
+  launch_scan(r, S.mcnt.p, total, S.moff.p, S.mscratch.p, s);
+  HIP_CHECK(hipMemcpyAsync(&S.nsel, S.moff.p + total, 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  require(S.nsel <= v.nmembers, "internal: the selected chains have more members than the chunk");
+  S.members.alloc(std::max<uint64_t>(S.nsel, 1));
+  flat_launch(r, s, nq, chain_align_gather_kernel, v.member_off, v.members, S.aoff.p, S.moff.p, nq, S.members.p);
+}
+
+// The CIGAR fill of one sub-batch: c chains (their queries, member offsets and members as launch_chain_align takes them) whose run
+// counts lie in d_nops.  Scan of the run counts, the runs read back, and if there are any the fill pass and its runs appended to
+// `cigar`.  d_coff (c + 1) and d_cscratch (scan_tiles(c) + 1) are the caller's.  Two stream synchronisations, without runs one:
+// what the caller has queued before rides on the first.
+void fill_cigar(Replica& r, const uint8_t* text8, const ChunkBuffers& cb, const uint32_t* d_query, const uint64_t* d_moff, const Seed* d_members, uint64_t c,
+                int band, uint32_t Lmax, const uint64_t* d_nops, uint64_t* d_coff, uint64_t* d_cscratch, std::vector<uint32_t>& cigar) {
+  const hipStream_t s = r.stream;
+  uint64_t runs = 0;
+  launch_scan(r, d_nops, c, d_coff, d_cscratch, s);
+  HIP_CHECK(hipMemcpyAsync(&runs, d_coff + c, 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (!runs) return;
+  DevBuf<uint32_t> d_cigar(runs);
+  launch_chain_align(r, text8, cb.q.p, cb.off.p, d_query, d_moff, d_members, c, band, Lmax, nullptr, nullptr, d_coff, d_cigar.p, s);
+  const size_t at_c = cigar.size();
+  cigar.resize(at_c + runs);
+  HIP_CHECK(hipMemcpyAsync(cigar.data() + at_c, d_cigar.p, runs * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// One chunk, from where chain_chunk's fill pass leaves it: the first min(n_chains, max_alignments) chains of every query, then
+// per sub-batch the count pass and the CIGAR fill, so that the staging is bounded by the sub-batch; appended to `out`.
 void align_chunk_chains(Replica& r, const uint8_t* text8, const ChainOnDevice& v, uint64_t max_alignments, int band, bool want_cigar, ChainAlnHits& out) {
   const hipStream_t s = r.stream;
   const uint64_t n = v.c.hi - v.c.lo;
   uint64_t Lmax = 1;
   for (uint64_t i = 0; i < n; i++) Lmax = std::max(Lmax, v.cb.h_off[i + 1] - v.cb.h_off[i]);
-  DevBuf<uint64_t> taken(n), aoff(n + 1), scratch(scan_tiles(n) + 1);
-  chain_launch(r, s, n, chain_align_take_kernel, v.n_chains, n, max_alignments, taken.p);
-  launch_scan(r, taken.p, n, aoff.p, scratch.p, s);
-  uint64_t total = 0;
   const size_t at_q = out.n_alns.size(), at_a = out.alns.size();
-  out.n_alns.resize(at_q + n);
+  out.n_alns.resize(at_q + n);  // (zeros: what a chunk without a chain reports)
   out.status.resize(at_q + n);
-  HIP_CHECK(hipMemcpyAsync(&total, aoff.p + n, 8, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(out.n_alns.data() + at_q, taken.p, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(out.status.data() + at_q, v.status, n, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  require(total <= v.nchains, "internal: more chains selected than the chunk has");
+  HIP_CHECK(hipMemcpyAsync(out.status.data() + at_q, v.status, n, hipMemcpyDeviceToHost, s));  // rides on the selection's first wait
+  SelectedChains S;
+  select_chains(r, v, n, max_alignments, S);
+  const uint64_t total = S.total;
   if (!total) return;
-  DevBuf<uint32_t> sel_query(total);
-  DevBuf<Chain> sel_chains(total);
-  DevBuf<uint64_t> mcnt(total), smoff(total + 1), sscratch(scan_tiles(total) + 1);
-  chain_launch(r, s, n, chain_align_select_kernel, v.chain_off, v.chains, aoff.p, n, sel_query.p, sel_chains.p, mcnt.p);
-  launch_scan(r, mcnt.p, total, smoff.p, sscratch.p, s);
-  uint64_t nsel = 0;
-  HIP_CHECK(hipMemcpyAsync(&nsel, smoff.p + total, 8, hipMemcpyDeviceToHost, s));
   out.chains.resize(at_a + total);
   out.alns.resize(at_a + total);
   out.n_ops.resize(at_a + total);
-  HIP_CHECK(hipMemcpyAsync(out.chains.data() + at_a, sel_chains.p, total * sizeof(Chain), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  require(nsel <= v.nmembers, "internal: the selected chains have more members than the chunk");
-  DevBuf<Seed> sel_members(std::max<uint64_t>(nsel, 1));
-  chain_launch(r, s, n, chain_align_gather_kernel, v.member_off, v.members, aoff.p, smoff.p, n, sel_members.p);
+  // these two ride on the first sub-batch's wait
+  HIP_CHECK(hipMemcpyAsync(out.n_alns.data() + at_q, S.taken.p, n * 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(out.chains.data() + at_a, S.chains.p, total * sizeof(Chain), hipMemcpyDeviceToHost, s));
   const uint64_t sub = std::min(chain_align_sub_batch(), total);
   DevBuf<Aln> alns(sub);
   DevBuf<uint64_t> nops(sub), coff(sub + 1), cscratch(scan_tiles(sub) + 1);
   for (uint64_t at = 0; at < total; at += sub) {
     const uint64_t c = std::min(sub, total - at);
-    launch_chain_align(r, text8, v.cb.q.p, v.cb.off.p, sel_query.p + at, smoff.p + at, sel_members.p, c, band, (uint32_t)Lmax, alns.p, nops.p, nullptr, nullptr, s);
-    uint64_t runs = 0;
-    if (want_cigar) {
-      launch_scan(r, nops.p, c, coff.p, cscratch.p, s);
-      HIP_CHECK(hipMemcpyAsync(&runs, coff.p + c, 8, hipMemcpyDeviceToHost, s));
-    }
+    launch_chain_align(r, text8, v.cb.q.p, v.cb.off.p, S.query.p + at, S.moff.p + at, S.members.p, c, band, (uint32_t)Lmax, alns.p, nops.p, nullptr, nullptr, s);
     HIP_CHECK(hipMemcpyAsync(out.alns.data() + at_a + at, alns.p, c * sizeof(Aln), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(out.n_ops.data() + at_a + at, nops.p, c * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (runs) {
-      DevBuf<uint32_t> cigar(runs);
-      launch_chain_align(r, text8, v.cb.q.p, v.cb.off.p, sel_query.p + at, smoff.p + at, sel_members.p, c, band, (uint32_t)Lmax, nullptr, nullptr, coff.p, cigar.p,
-                         s);
-      const size_t at_c = out.cigar.size();
-      out.cigar.resize(at_c + runs);
-      HIP_CHECK(hipMemcpyAsync(out.cigar.data() + at_c, cigar.p, runs * 4, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-    }
+    if (want_cigar) fill_cigar(r, text8, v.cb, S.query.p + at, S.moff.p + at, S.members.p, c, band, (uint32_t)Lmax, nops.p, coff.p, cscratch.p, out.cigar);
+    else HIP_CHECK(hipStreamSynchronize(s));
   }
 }
 
@@ -105,52 +128,28 @@ void align_chains_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* 
                         uint64_t max_alignments, uint32_t band, uint64_t** aln_off_out, awry_chain_t** chains_out, awry_aln_t** alns_out,
                         uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out) {
   require_chain_index(idx->host.bwt_len);
-  for (uint64_t i = 0; i < n; i++)
-    if (qoff[i + 1] > qoff[i] && qoff[i + 1] - qoff[i] > (uint64_t)CHAIN_ALIGN_MAX_LEN)
-      throw QueryError("query " + std::to_string(i) + ": longer than 1024 letters (AWRY_CHAIN_ALIGN_MAX_LEN)");
+  require_chain_align_lengths(qoff, n);
   const bool want_cigar = cigar_out != nullptr;
   std::vector<ChainAlnHits> res(std::max<size_t>(1, idx->reps.size()));
   for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
     HIP_CHECK(hipSetDevice(r.device));
     const uint8_t* text8 = edit_text(r);
-    const ChainSink sink = [&, g, text8](Replica& rr, const ChainOnDevice& v) { align_chunk_chains(rr, text8, v, max_alignments, (int)band, want_cigar, res[g]); };
-    ChainHits unused;
-    for (Shard c : chunk_queries(qoff, sh.lo, sh.hi)) chain_range(r, qbytes, qoff, c, min_len, max_hits, P, true, unused, &sink);
+    const auto sink = [&, g, text8](Replica& rr, const ChainOnDevice& v) { align_chunk_chains(rr, text8, v, max_alignments, (int)band, want_cigar, res[g]); };
+    for (Shard c : chunk_queries(qoff, sh.lo, sh.hi))
+      halve_until_fits(c, [&](Shard h) { return chain_chunk(r, qbytes, qoff, h, min_len, max_hits, P, false, sink); });
   });
   MBuf<uint64_t> aoff, coff;
   MBuf<awry_chain_t> chains;
   MBuf<awry_aln_t> alns;
   MBuf<uint32_t> cg;
   MBuf<uint8_t> st;
-  aoff.grow(n + 1);
-  aoff.p[0] = 0;
-  if (status_out) st.grow(std::max<uint64_t>(1, n));
-  uint64_t q = 0, total = 0, runs = 0;
-  for (auto& x : res) {
-    if (status_out && !x.status.empty()) memcpy(st.p + q, x.status.data(), x.status.size());
-    for (uint64_t c : x.n_alns) { total += c; aoff.p[++q] = total; }
-    runs += x.cigar.size();
-  }
-  require(q == n, "internal: shard results do not cover the batch");
-  if (chains_out) chains.grow(std::max<uint64_t>(1, total));
-  if (alns_out) alns.grow(std::max<uint64_t>(1, total));
-  if (want_cigar) { coff.grow(total + 1); cg.grow(std::max<uint64_t>(1, runs)); }
-  uint64_t at = 0, at_c = 0;
-  for (auto& x : res) {
-    require(x.chains.size() == x.alns.size() && x.alns.size() == x.n_ops.size(), "internal: the alignment passes do not cover the chains");
-    if (chains_out && !x.chains.empty()) pool_memcpy(chains.p + at, x.chains.data(), x.chains.size() * sizeof(awry_chain_t));
-    if (alns_out && !x.alns.empty()) pool_memcpy(alns.p + at, x.alns.data(), x.alns.size() * sizeof(awry_aln_t));
-    if (want_cigar) {
-      if (!x.cigar.empty()) pool_memcpy(cg.p + at_c, x.cigar.data(), x.cigar.size() * 4);
-      for (size_t j = 0; j < x.n_ops.size(); j++) { coff.p[at + j] = at_c; at_c += x.n_ops[j]; }
-    }
-    at += x.alns.size();
-  }
-  require(at == total, "internal: shard results do not cover the alignments");
-  if (want_cigar) {
-    require(at_c == runs, "internal: the run counts do not cover the CIGAR runs");
-    coff.p[total] = runs;
-  }
+  const uint64_t total = stitch_offsets(res, &ChainAlnHits::n_alns, n, aoff);
+  for (auto& x : res) require(x.chains.size() == x.alns.size() && x.alns.size() == x.n_ops.size(), "internal: the alignment passes do not cover the chains");
+  require(stitch_size(res, &ChainAlnHits::alns) == total, "internal: shard results do not cover the alignments");
+  if (status_out) stitch_concat(res, &ChainAlnHits::status, st);
+  if (chains_out) stitch_concat(res, &ChainAlnHits::chains, chains);
+  if (alns_out) stitch_concat(res, &ChainAlnHits::alns, alns);
+  if (want_cigar) stitch_run_offsets(res, &ChainAlnHits::n_ops, total, stitch_concat(res, &ChainAlnHits::cigar, cg), coff);
   *aln_off_out = aoff.release();
   if (chains_out) *chains_out = chains.release();
   if (alns_out) *alns_out = alns.release();

@@ -1,5 +1,6 @@
 // edit_host.h -- the chunk driver of locate within k edits: pigeonhole pieces, their located hits as diagonals, windows, the scan,
-// and on request the alignment pass over the hits (awry_align_edit_batch)
+// and on request the alignment pass over the hits (awry_align_edit_batch).  Launches, the capacity fallback and the stitching are
+// batch_host.h's.
 // A part of awry_hip.hip (one translation unit): included there, in order, and not on its own.
 #pragma once
 
@@ -17,20 +18,12 @@ void require_edits(int k) {
 
 // Candidates (located piece hits) a chunk may hold on the device; a chunk with more, and more than one query, is split in
 // halves and each half redone in query order.  Read per call: AWRY_EDIT_CANDIDATE_CAP (tests shrink it).
-uint64_t edit_candidate_cap() {
-  const char* e = getenv("AWRY_EDIT_CANDIDATE_CAP");
-  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
-  return v ? std::min<uint64_t>(v, 1ull << 31) : (1ull << 26);
-}
+uint64_t edit_candidate_cap() { return env_cap("AWRY_EDIT_CANDIDATE_CAP", 1ull << 26, 1ull << 31); }
 
 // Hits the alignment pass takes per launch: its fixed-stride staging (text_len, n_ops, ops, and the scan of the run counts: 89 B
 // per hit) is bounded by the sub-batch whatever the hit count -- 89 MiB at the default 2^20.  Read per call:
 // AWRY_ALIGN_SUB_BATCH (tests shrink it).
-uint64_t align_sub_batch() {
-  const char* e = getenv("AWRY_ALIGN_SUB_BATCH");
-  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
-  return v ? std::min<uint64_t>(v, 1ull << 24) : (1ull << 20);
-}
+uint64_t align_sub_batch() { return env_cap("AWRY_ALIGN_SUB_BATCH", 1ull << 20, 1ull << 24); }
 
 // The text as symbol indices for the scan: the replica's text8 while the verify accelerators keep it, else a copy of the
 // replica's own, recovered from the index on first use (one LF chain per file SA sample) and kept with the replica.  Nothing
@@ -73,12 +66,6 @@ struct EditWants {  // what the caller asked for: the chunk driver copies back n
   bool pos, gpos, edits, align;
 };
 
-template <class K, class... Args>
-void edit_launch(Replica& r, hipStream_t s, uint64_t items, K kernel, Args... args) {
-  hipLaunchKernelGGL(kernel, dim3(grid_for(r, items, 256)), dim3(256), 0, s, args...);
-  HIP_CHECK(hipGetLastError());
-}
-
 // The alignment pass over the nhits hits of a chunk, which lie on the device in window order: their queries out of the windows',
 // then per sub-batch the kernel at a fixed stride, a scan of the run counts and the compaction to CSR, appended to `out`.
 void align_chunk_hits(Replica& r, const uint8_t* text8, const ChunkBuffers& cb, const uint32_t* win_query, const uint64_t* win_hit_off, uint64_t m,
@@ -88,14 +75,14 @@ void align_chunk_hits(Replica& r, const uint8_t* text8, const ChunkBuffers& cb, 
   DevBuf<uint32_t> hit_query(nhits), text_len(sub), ops(sub * ALIGN_MAX_OPS);
   DevBuf<uint8_t> n_ops(sub);
   DevBuf<uint64_t> counts(sub), cigar_off(sub + 1), scratch(scan_tiles(sub) + 1);
-  edit_launch(r, s, nhits, align_hit_query_kernel, win_hit_off, win_query, m, nhits, hit_query.p);
+  flat_launch(r, s, nhits, align_hit_query_kernel, win_hit_off, win_query, m, nhits, hit_query.p);
   const size_t at_h = out.text_len.size();
   out.text_len.resize(at_h + nhits);
   out.n_ops.resize(at_h + nhits);
   for (uint64_t at = 0; at < nhits; at += sub) {
     const uint64_t c = std::min(sub, nhits - at);
     launch_edit_align(r, text8, cb.q.p, cb.off.p, hit_query.p + at, d_gpos + at, d_edits + at, c, k, Lmax, text_len.p, n_ops.p, ops.p, s);
-    edit_launch(r, s, c, align_counts_kernel, n_ops.p, c, counts.p);
+    flat_launch(r, s, c, align_counts_kernel, n_ops.p, c, counts.p);
     launch_scan(r, counts.p, c, cigar_off.p, scratch.p, s);
     uint64_t runs = 0;
     HIP_CHECK(hipMemcpyAsync(&runs, cigar_off.p + c, 8, hipMemcpyDeviceToHost, s));
@@ -105,7 +92,7 @@ void align_chunk_hits(Replica& r, const uint8_t* text8, const ChunkBuffers& cb, 
     require(runs <= c * (uint64_t)ALIGN_MAX_OPS, "internal: more CIGAR runs than the bound allows");
     if (runs) {
       DevBuf<uint32_t> cigar(runs);
-      edit_launch(r, s, c, align_compact_kernel, ops.p, n_ops.p, cigar_off.p, c, cigar.p);
+      flat_launch(r, s, c, align_compact_kernel, ops.p, n_ops.p, cigar_off.p, c, cigar.p);
       const size_t at_c = out.cigar.size();
       out.cigar.resize(at_c + runs);
       HIP_CHECK(hipMemcpyAsync(out.cigar.data() + at_c, cigar.p, runs * 4, hipMemcpyDeviceToHost, s));
@@ -141,7 +128,7 @@ bool edit_chunk(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const u
   DevBuf<uint8_t> pstatus(np);
   HIP_CHECK(hipMemcpyAsync(poff.p, h_poff.data(), (np + 1) * 8, hipMemcpyHostToDevice, s));
   launch_count_ascii(r, cb.q.p, poff.p, np, pcounts.p, pranges.p, pstatus.p, s, true);
-  edit_launch(r, s, n, edit_cap_kernel, pcounts.p, pstatus.p, n, k, max_candidates, cb.status.p);
+  flat_launch(r, s, n, edit_cap_kernel, pcounts.p, pstatus.p, n, k, max_candidates, cb.status.p);
   launch_scan(r, pcounts.p, np, phoff.p, pscratch.p, s);
   uint64_t total = 0;
   HIP_CHECK(hipMemcpyAsync(&total, phoff.p + np, 8, hipMemcpyDeviceToHost, s));
@@ -157,33 +144,33 @@ bool edit_chunk(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const u
   if (total) {
     DevBuf<uint64_t> cand_gpos(total), key(total), key2(total), heads(total), head_off(total + 1), hscratch(scan_tiles(total) + 1);
     launch_locate(r, pranges.p, 2, phoff.p, np, total, cand_gpos.p, nullptr, s);
-    edit_launch(r, s, total, edit_diagonals_kernel, cand_gpos.p, phoff.p, np, total, cb.off.p, k, key.p);
-    edit_launch(r, s, n + 1, edit_every_nth_kernel, phoff.p, n + 1, w, cand_off.p);
+    flat_launch(r, s, total, edit_diagonals_kernel, cand_gpos.p, phoff.p, np, total, cb.off.p, k, key.p);
+    flat_launch(r, s, n + 1, edit_every_nth_kernel, phoff.p, n + 1, w, cand_off.p);
     unsigned end_bit = 1;
     while (end_bit < 64 && ((r.dev.bwt_len + 2 * (uint64_t)EDIT_MAX_LEN) >> end_bit)) end_bit++;
     size_t tmp_bytes = 0;
     HIP_CHECK(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, key.p, key2.p, (unsigned)total, (unsigned)n, cand_off.p, cand_off.p + 1, 0, end_bit, s));
     DevBuf<uint8_t> tmp(std::max<size_t>(tmp_bytes, 8));
     HIP_CHECK(rocprim::segmented_radix_sort_keys(tmp.p, tmp_bytes, key.p, key2.p, (unsigned)total, (unsigned)n, cand_off.p, cand_off.p + 1, 0, end_bit, s));
-    edit_launch(r, s, total, edit_run_heads_kernel, key2.p, cand_off.p, n, total, k, heads.p);
+    flat_launch(r, s, total, edit_run_heads_kernel, key2.p, cand_off.p, n, total, k, heads.p);
     launch_scan(r, heads.p, total, head_off.p, hscratch.p, s);
     HIP_CHECK(hipMemcpyAsync(&m, head_off.p + total, 8, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     DevBuf<uint32_t> win_query(m), win_count(m);
     DevBuf<uint64_t> run_lo(m), run_hi(m), win_first(m), win_hits(m), win_hit_off(m + 1), wscratch(scan_tiles(m) + 1), q_hit_off(n + 1);
-    edit_launch(r, s, total, edit_run_ends_kernel, key2.p, cand_off.p, n, total, k, head_off.p, win_query.p, run_lo.p, run_hi.p);
-    edit_launch(r, s, m, edit_windows_kernel, win_query.p, run_lo.p, run_hi.p, m, cb.off.p, k, n_text, win_first.p, win_count.p);
+    flat_launch(r, s, total, edit_run_ends_kernel, key2.p, cand_off.p, n, total, k, head_off.p, win_query.p, run_lo.p, run_hi.p);
+    flat_launch(r, s, m, edit_windows_kernel, win_query.p, run_lo.p, run_hi.p, m, cb.off.p, k, n_text, win_first.p, win_count.p);
     launch_edit_windows(r, text8, cb.q.p, cb.off.p, win_query.p, win_first.p, win_count.p, m, k, W, n, win_hits.p, nullptr, nullptr, nullptr, s);
     launch_scan(r, win_hits.p, m, win_hit_off.p, wscratch.p, s);
     HIP_CHECK(hipMemcpyAsync(&nhits, win_hit_off.p + m, 8, hipMemcpyDeviceToHost, s));
-    edit_launch(r, s, n + 1, edit_query_hit_off_kernel, cand_off.p, head_off.p, win_hit_off.p, n, q_hit_off.p);
+    flat_launch(r, s, n + 1, edit_query_hit_off_kernel, cand_off.p, head_off.p, win_hit_off.p, n, q_hit_off.p);
     HIP_CHECK(hipMemcpyAsync(h_qhoff.data(), q_hit_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     if (nhits) {
       DevBuf<uint64_t> d_gpos(nhits), d_pos(want_pos ? 2 * nhits : 0);
       DevBuf<uint8_t> d_edits(nhits);
       launch_edit_windows(r, text8, cb.q.p, cb.off.p, win_query.p, win_first.p, win_count.p, m, k, W, n, nullptr, win_hit_off.p, d_gpos.p, d_edits.p, s);
-      if (want_pos) edit_launch(r, s, nhits, edit_localise_kernel, r.dev, nhits, d_gpos.p, d_pos.p);
+      if (want_pos) flat_launch(r, s, nhits, edit_localise_kernel, r.dev, nhits, d_gpos.p, d_pos.p);
       if (want_gpos) { out.gpos.resize(at_h + nhits); HIP_CHECK(hipMemcpyAsync(out.gpos.data() + at_h, d_gpos.p, nhits * 8, hipMemcpyDeviceToHost, s)); }
       if (want_pos) { out.pos.resize(at_h + nhits); HIP_CHECK(hipMemcpyAsync(out.pos.data() + at_h, d_pos.p, nhits * 16, hipMemcpyDeviceToHost, s)); }
       if (want_edits) { out.edits.resize(at_h + nhits); HIP_CHECK(hipMemcpyAsync(out.edits.data() + at_h, d_edits.p, nhits, hipMemcpyDeviceToHost, s)); }
@@ -198,15 +185,6 @@ bool edit_chunk(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const u
   return true;
 }
 
-void edit_range(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, uint64_t max_candidates, EditWants want,
-                EditHits& out) {
-  if (c.hi <= c.lo) return;
-  if (edit_chunk(r, text8, qbytes, qoff, c, k, max_candidates, want, out)) return;
-  const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order
-  edit_range(r, text8, qbytes, qoff, Shard{c.lo, mid}, k, max_candidates, want, out);
-  edit_range(r, text8, qbytes, qoff, Shard{mid, c.hi}, k, max_candidates, want, out);
-}
-
 // awry_locate_edit_batch and awry_align_edit_batch (which passes the last three: text_len_out alone, the two cigar arrays together,
 // or all): shards over the replicas, results stitched in query order.  The out-pointers are written only when everything has
 // succeeded.
@@ -219,47 +197,25 @@ void locate_edit_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* q
     HIP_CHECK(hipSetDevice(r.device));
     const uint8_t* text8 = edit_text(r);
     for (Shard c : chunk_queries(qoff, sh.lo, sh.hi))
-      edit_range(r, text8, qbytes, qoff, c, k, max_candidates, want, res[g]);
+      halve_until_fits(c, [&](Shard h) { return edit_chunk(r, text8, qbytes, qoff, h, k, max_candidates, want, res[g]); });
   });
-  MBuf<uint64_t> off, gp;
+  MBuf<uint64_t> off, gp, coff;
   MBuf<awry_pos_t> hits;
   MBuf<uint8_t> ed, st;
   MBuf<uint32_t> tl, cg;
-  MBuf<uint64_t> coff;
-  off.grow(n + 1);
-  off.p[0] = 0;
-  if (status_out) st.grow(std::max<uint64_t>(1, n));
-  uint64_t q = 0, total = 0;
+  const uint64_t total = stitch_offsets(res, &EditHits::counts, n, off);
+  uint64_t nhits = 0;
   for (auto& x : res) {
-    if (status_out && !x.status.empty()) memcpy(st.p + q, x.status.data(), x.status.size());
-    for (uint64_t cnt : x.counts) { total += cnt; off.p[++q] = total; }
-  }
-  require(q == n, "internal: shard results do not cover the batch");
-  if (hits_out) hits.grow(std::max<uint64_t>(1, total));
-  if (global_pos_out) gp.grow(std::max<uint64_t>(1, total));
-  if (edits_out) ed.grow(std::max<uint64_t>(1, total));
-  if (text_len_out) tl.grow(std::max<uint64_t>(1, total));
-  uint64_t runs = 0;
-  for (auto& x : res) runs += x.cigar.size();
-  if (cigar_out) { coff.grow(total + 1); cg.grow(std::max<uint64_t>(1, runs)); }
-  uint64_t at = 0, at_c = 0;
-  for (auto& x : res) {
-    if (hits_out && x.nhits) pool_memcpy(hits.p + at, x.pos.data(), x.nhits * sizeof(awry_pos_t));
-    if (global_pos_out && x.nhits) pool_memcpy(gp.p + at, x.gpos.data(), x.nhits * 8);
-    if (edits_out && x.nhits) pool_memcpy(ed.p + at, x.edits.data(), x.nhits);
     if (want.align) require(x.text_len.size() == x.nhits && x.n_ops.size() == x.nhits, "internal: the alignment pass does not cover the hits");
-    if (text_len_out && x.nhits) pool_memcpy(tl.p + at, x.text_len.data(), x.nhits * 4);
-    if (cigar_out) {
-      if (!x.cigar.empty()) pool_memcpy(cg.p + at_c, x.cigar.data(), x.cigar.size() * 4);
-      for (uint64_t h = 0; h < x.nhits; h++) { coff.p[at + h] = at_c; at_c += x.n_ops[h]; }
-    }
-    at += x.nhits;
+    nhits += x.nhits;
   }
-  require(at == total, "internal: shard results do not cover the hits");
-  if (cigar_out) {
-    require(at_c == runs, "internal: the run counts do not cover the CIGAR runs");
-    coff.p[total] = runs;
-  }
+  require(nhits == total, "internal: shard results do not cover the hits");
+  if (status_out) stitch_concat(res, &EditHits::status, st);
+  if (hits_out) stitch_concat(res, &EditHits::pos, hits);
+  if (global_pos_out) stitch_concat(res, &EditHits::gpos, gp);
+  if (edits_out) stitch_concat(res, &EditHits::edits, ed);
+  if (text_len_out) stitch_concat(res, &EditHits::text_len, tl);
+  if (cigar_out) stitch_run_offsets(res, &EditHits::n_ops, total, stitch_concat(res, &EditHits::cigar, cg), coff);
   *hit_off_out = off.release();
   if (hits_out) *hits_out = hits.release();
   if (global_pos_out) *global_pos_out = gp.release();

@@ -1,4 +1,5 @@
-// mismatch_host.h -- shard drivers of the substitution-tolerant and class-pattern count and locate
+// mismatch_host.h -- shard drivers of the substitution-tolerant and class-pattern count and locate (launches, the capacity
+// fallback and the stitching are batch_host.h's)
 // A part of awry_hip.hip (one translation unit): included there, in order, and not on its own.
 #pragma once
 
@@ -18,22 +19,6 @@ void require_mismatches(int k) {
   if (k < 0 || k > MM_MAX_K) throw ArgError("max_mismatches must be 0, 1 or 2");
 }
 
-// upload one chunk's query bytes and chunk-relative offsets (the generic count path's layout)
-void upload_chunk(Replica& r, ChunkBuffers& cb, const uint8_t* qbytes, const uint64_t* qoff, Shard c) {
-  const uint64_t n = c.hi - c.lo, base = qoff[c.lo], nbytes = qoff[c.hi] - base;
-  cb.h_off.resize(n + 1);
-  for (uint64_t i = 0; i <= n; i++) {
-    if (qoff[c.lo + i] < base || (i && qoff[c.lo + i] < qoff[c.lo + i - 1])) throw ArgError("query offsets must be non-decreasing");
-    cb.h_off[i] = qoff[c.lo + i] - base;
-  }
-  if (cb.q.n < nbytes + 16) cb.q.alloc(nbytes + 16);
-  if (cb.off.n < n + 1) cb.off.alloc(n + 1);
-  if (cb.status.n < n) cb.status.alloc(n);
-  if (nbytes) HIP_CHECK(hipMemcpyAsync(cb.q.p, qbytes + base, nbytes, hipMemcpyHostToDevice, r.stream));
-  HIP_CHECK(hipMemcpyAsync(cb.off.p, cb.h_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, r.stream));
-  cb.h_status.resize(n);
-}
-
 void count_mismatch_shard(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard sh, int k, uint64_t* counts_out, bool classes) {
   HIP_CHECK(hipSetDevice(r.device));
   ChunkBuffers cb;
@@ -51,11 +36,7 @@ void count_mismatch_shard(Replica& r, const uint8_t* qbytes, const uint64_t* qof
 
 // Leaves (row ranges of the variants that occur) a locate chunk may hold on the device; a chunk with more is split in halves
 // and each half redone (one query with more gets what it needs).  Read per call: AWRY_MISMATCH_LEAF_CAP (tests shrink it).
-uint64_t mismatch_leaf_cap() {
-  const char* e = getenv("AWRY_MISMATCH_LEAF_CAP");
-  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
-  return v ? std::min<uint64_t>(v, 1ull << 31) : (1ull << 26);
-}
+uint64_t mismatch_leaf_cap() { return env_cap("AWRY_MISMATCH_LEAF_CAP", 1ull << 26, 1ull << 31); }
 
 struct MismatchHits {  // one shard's locate result, in query order
   std::vector<uint64_t> counts;  // hits per query
@@ -99,31 +80,18 @@ bool locate_mismatch_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qo
     DevBuf<uint8_t> tmp(std::max<size_t>(tmp_bytes, 8));
     HIP_CHECK(rocprim::segmented_radix_sort_pairs(tmp.p, tmp_bytes, key.p, key2.p, val.p, val2.p, (unsigned)nleaf, (unsigned)n, leaf_off.p,
                                                   leaf_off.p + 1, 0, end_bit, s));
-    hipLaunchKernelGGL(mm_leaf_widths_kernel, dim3(grid_for(r, nleaf, 256)), dim3(256), 0, s, val2.p, nleaf, width.p);
-    HIP_CHECK(hipGetLastError());
+    flat_launch(r, s, nleaf, mm_leaf_widths_kernel, val2.p, nleaf, width.p);
     launch_scan(r, width.p, nleaf, leaf_hit_off.p, lscratch.p, s);
     DevBuf<uint64_t> d_gpos(total), d_pos(want_pos ? 2 * total : 0);
     DevBuf<uint8_t> d_mm(want_mm ? total : 0);
     launch_locate(r, key2.p, 1, leaf_hit_off.p, nleaf, total, d_gpos.p, d_pos.p, s);
-    if (want_mm) {
-      hipLaunchKernelGGL(mm_hit_distance_kernel, dim3(grid_for(r, total, 256)), dim3(256), 0, s, leaf_hit_off.p, val2.p, nleaf, total, d_mm.p);
-      HIP_CHECK(hipGetLastError());
-    }
+    if (want_mm) flat_launch(r, s, total, mm_hit_distance_kernel, leaf_hit_off.p, val2.p, nleaf, total, d_mm.p);
     if (want_gpos) { out.gpos.resize(at_h + total); HIP_CHECK(hipMemcpyAsync(out.gpos.data() + at_h, d_gpos.p, total * 8, hipMemcpyDeviceToHost, s)); }
     if (want_pos) { out.pos.resize(at_h + total); HIP_CHECK(hipMemcpyAsync(out.pos.data() + at_h, d_pos.p, total * 16, hipMemcpyDeviceToHost, s)); }
     if (want_mm) { out.mm.resize(at_h + total); HIP_CHECK(hipMemcpyAsync(out.mm.data() + at_h, d_mm.p, total, hipMemcpyDeviceToHost, s)); }
   }
   HIP_CHECK(hipStreamSynchronize(s));
   return true;
-}
-
-void locate_mismatch_range(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, int k, bool want_pos, bool want_gpos, bool want_mm,
-                           MismatchHits& out, bool classes) {
-  if (c.hi <= c.lo) return;
-  if (locate_mismatch_chunk(r, qbytes, qoff, c, k, want_pos, want_gpos, want_mm, out, classes)) return;
-  const uint64_t mid = c.lo + (c.hi - c.lo) / 2;  // the capacity fallback: halves, in query order
-  locate_mismatch_range(r, qbytes, qoff, Shard{c.lo, mid}, k, want_pos, want_gpos, want_mm, out, classes);
-  locate_mismatch_range(r, qbytes, qoff, Shard{mid, c.hi}, k, want_pos, want_gpos, want_mm, out, classes);
 }
 
 // the host batch drivers of both modes (awry_count_mismatch_batch / awry_count_pattern_batch, and the locate pair)
@@ -142,30 +110,17 @@ void locate_leaves_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t*
   std::vector<MismatchHits> res(std::max<size_t>(1, idx->reps.size()));
   for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
     HIP_CHECK(hipSetDevice(r.device));
+    const bool want_pos = hits_out != nullptr, want_gpos = global_pos_out != nullptr, want_mm = mismatches_out != nullptr;
     for (Shard c : chunk_queries(qoff, sh.lo, sh.hi))
-      locate_mismatch_range(r, qbytes, qoff, c, k, hits_out != nullptr, global_pos_out != nullptr, mismatches_out != nullptr, res[g], classes);
+      halve_until_fits(c, [&](Shard h) { return locate_mismatch_chunk(r, qbytes, qoff, h, k, want_pos, want_gpos, want_mm, res[g], classes); });
   });
-  // shards are contiguous in query order: the result arrays are their concatenation
   MBuf<uint64_t> off, gp;
   MBuf<awry_pos_t> hits;
   MBuf<uint8_t> mm;
-  off.grow(n + 1);
-  off.p[0] = 0;
-  uint64_t q = 0, total = 0;
-  for (auto& x : res)
-    for (uint64_t c : x.counts) { total += c; off.p[++q] = total; }
-  require(q == n, "internal: shard results do not cover the batch");
-  if (hits_out) hits.grow(std::max<uint64_t>(1, total));
-  if (global_pos_out) gp.grow(std::max<uint64_t>(1, total));
-  if (mismatches_out) mm.grow(std::max<uint64_t>(1, total));
-  uint64_t at = 0;
-  for (auto& x : res) {
-    const uint64_t t = x.counts.empty() ? 0 : std::max({x.gpos.size(), x.pos.size(), x.mm.size()});
-    if (hits_out && t) pool_memcpy(hits.p + at, x.pos.data(), t * sizeof(awry_pos_t));
-    if (global_pos_out && t) pool_memcpy(gp.p + at, x.gpos.data(), t * 8);
-    if (mismatches_out && t) pool_memcpy(mm.p + at, x.mm.data(), t);
-    at += t;
-  }
+  stitch_offsets(res, &MismatchHits::counts, n, off);
+  if (hits_out) stitch_concat(res, &MismatchHits::pos, hits);
+  if (global_pos_out) stitch_concat(res, &MismatchHits::gpos, gp);
+  if (mismatches_out) stitch_concat(res, &MismatchHits::mm, mm);
   *hit_off_out = off.release();
   if (hits_out) *hits_out = hits.release();
   if (global_pos_out) *global_pos_out = gp.release();

@@ -479,3 +479,49 @@ def test_invalid_queries_fail_the_batch_and_a_capped_query_has_no_alignments(nt,
     got = nt.ix.parallel_align_chains_csr(*pack_queries(three), 1, 50, 2, 4, *P)
     assert_batch_equals(got, want)
     assert got[5][1] == Q_SEED_CAP and got[0][2] == got[0][1]
+
+
+# ---- the chunk driver's rarely taken branches, on 64 reads of 101 letters ------------------------------------------------------------
+
+from tests.test_smems_gpu import all_equal, shrunk_cap, small_reads, with_bad_read  # noqa: E402
+
+NO_CHAIN = E2E_PARAMS[KEY]._replace(min_score=10 ** 6)  # above any reachable score
+
+
+def assert_no_alignments(got, n):
+    off, ch, al, coff, cg, st = got
+    assert np.array_equal(off, np.zeros(n + 1, np.uint64)) and len(ch) == 0 and len(al) == 0 and np.array_equal(coff, [0]) and len(cg) == 0
+    assert st.dtype == np.uint8 and np.array_equal(st, np.zeros(n, np.uint8))
+
+
+def test_chunks_without_smems_and_without_chains_give_zero_offsets_and_ok_status(nt):
+    reads = small_reads(nt)
+    qb, qo = pack_queries(reads)
+    assert_no_alignments(nt.ix.parallel_align_chains_csr(qb, qo, 102, 20, 3, 4, *E2E_PARAMS[KEY]), len(reads))  # min_len above every read's length
+    assert int(nt.ix.parallel_locate_smems_csr(qb, qo, KEY[1], KEY[0])[2][-1]) >= len(reads)  # seeds, and no chain of them
+    assert_no_alignments(nt.ix.parallel_align_chains_csr(qb, qo, *KEY, 3, 4, *NO_CHAIN), len(reads))
+
+
+def test_the_call_without_the_cigar_arrays_agrees_field_for_field(nt):
+    qb, qo = pack_queries(small_reads(nt))
+    full = nt.ix.parallel_align_chains_csr(qb, qo, *KEY, 3, 4, *E2E_PARAMS[KEY])
+    bare = nt.ix.parallel_align_chains_csr(qb, qo, *KEY, 3, 4, *E2E_PARAMS[KEY], want_cigar=False)
+    assert int(full[0][-1]) >= 64 and len(full[4]) >= 64
+    assert all(np.array_equal(bare[k], full[k]) for k in (0, 1, 2, 5)) and len(bare[3]) == 0 and len(bare[4]) == 0
+
+
+def test_a_bad_read_is_named_before_the_capacity_test_splits_its_chunk(nt):
+    reads = small_reads(nt, 6)
+    with shrunk_cap("AWRY_ANCHOR_HIT_CAP"):
+        for bad in (b"AC$T", b"", bytes([0x41, 0x80])):
+            with pytest.raises(AwryError) as e:
+                nt.ix.parallel_align_chains_csr(*pack_queries(with_bad_read(reads, bad)), *KEY, 3, 4, *E2E_PARAMS[KEY])
+            assert e.value.code == ERR_INVALID_QUERY and "query 3:" in str(e.value), bad
+
+
+def test_seven_reads_halved_down_to_single_reads_equal_the_uncapped_call(nt):
+    qb, qo = pack_queries(small_reads(nt, 7))
+    want = nt.ix.parallel_align_chains_csr(qb, qo, *KEY, 3, 4, *E2E_PARAMS[KEY])
+    assert int(want[0][-1]) >= 7
+    with shrunk_cap("AWRY_ANCHOR_HIT_CAP"):
+        assert all_equal(want, nt.ix.parallel_align_chains_csr(qb, qo, *KEY, 3, 4, *E2E_PARAMS[KEY]))

@@ -385,3 +385,55 @@ def test_oracle_scale_seeds_on_a_2_mbp_text(oracle):
     assert sum(1 for _, c in want if c) >= 400
     assert_batch_equals(ix.parallel_chains_csr(*pack_queries(qs), 10, 30, *P), want)
     ix.close()
+
+
+# ---- the chunk driver's rarely taken branches, on 64 reads of 101 letters ------------------------------------------------------------
+
+from tests.test_smems_gpu import all_equal, shrunk_cap, small_reads, with_bad_read  # noqa: E402
+
+NO_CHAIN = E2E_PARAMS[(12, 20)]._replace(min_score=10 ** 6)  # above any reachable score
+
+
+def assert_no_chains(got, n):
+    off, ch, soff, sd, st = got
+    assert np.array_equal(off, np.zeros(n + 1, np.uint64)) and len(ch) == 0 and np.array_equal(soff, [0]) and len(sd) == 0
+    assert st.dtype == np.uint8 and np.array_equal(st, np.zeros(n, np.uint8))
+
+
+def test_chunks_without_smems_and_without_chains_give_zero_offsets_and_ok_status(nt):
+    reads = small_reads(nt)
+    qb, qo = pack_queries(reads)
+    assert_no_chains(nt.ix.parallel_chains_csr(qb, qo, 102, 20, *E2E_PARAMS[(12, 20)]), len(reads))  # min_len above every read's length
+    assert int(nt.ix.parallel_locate_smems_csr(qb, qo, 20, 12)[2][-1]) >= len(reads)  # seeds, and no chain of them
+    assert_no_chains(nt.ix.parallel_chains_csr(qb, qo, 12, 20, *NO_CHAIN), len(reads))
+
+
+def test_a_bad_read_is_named_before_the_capacity_test_splits_its_chunk(nt):
+    reads = small_reads(nt, 6)
+    with shrunk_cap("AWRY_ANCHOR_HIT_CAP"):
+        for bad in (b"AC$T", b"", bytes([0x41, 0x80])):
+            with pytest.raises(AwryError) as e:
+                nt.ix.parallel_chains_csr(*pack_queries(with_bad_read(reads, bad)), 12, 20, *E2E_PARAMS[(12, 20)])
+            assert e.value.code == ERR_INVALID_QUERY and "query 3:" in str(e.value), bad
+
+
+def test_seven_reads_halved_down_to_single_reads_equal_the_uncapped_call(nt):
+    qb, qo = pack_queries(small_reads(nt, 7))
+    want = nt.ix.parallel_chains_csr(qb, qo, 12, 20, *E2E_PARAMS[(12, 20)])
+    assert int(want[0][-1]) >= 7
+    with shrunk_cap("AWRY_ANCHOR_HIT_CAP"):
+        assert all_equal(want, nt.ix.parallel_chains_csr(qb, qo, 12, 20, *E2E_PARAMS[(12, 20)]))
+
+
+def test_every_member_seed_is_a_located_hit_of_an_smem_of_the_same_read(nt):
+    reads = small_reads(nt)
+    qb, qo = pack_queries(reads)
+    off, ch, soff, sd, st = nt.ix.parallel_chains_csr(qb, qo, 12, 20, *E2E_PARAMS[(12, 20)])
+    moff, sm, hoff, g, _ = nt.ix.parallel_locate_smems_csr(qb, qo, 20, 12)
+    assert not st.any() and int(np.diff(off.astype(np.int64)).max()) >= 2  # no read abandoned, and one of at least two chains
+    for i in range(len(reads)):
+        hits = {(int(sm[s]["q_begin"]), int(sm[s]["q_len"]), int(t)) for s in range(int(moff[i]), int(moff[i + 1])) for t in g[int(hoff[s]):int(hoff[s + 1])]}
+        members = sd[int(soff[int(off[i])]):int(soff[int(off[i + 1])])]
+        assert len(members) or off[i] == off[i + 1]
+        for m in members:
+            assert (int(m["q_begin"]), int(m["q_len"]), int(m["t_pos"])) in hits, (i, m)

@@ -379,3 +379,16 @@ def test_device_primitive_on_hand_made_windows(nt):
     assert [int(v) for v in t] == [cols, scanned]
     again = dev_windows(nt, qs, wins, k)
     assert np.array_equal(again[0], n_hits) and np.array_equal(again[1], g) and np.array_equal(again[2], e)
+
+
+def test_seven_reads_halved_down_to_single_reads_equal_the_uncapped_call(nt):
+    qs = reads_for(nt, np.random.default_rng(61), 101, 2)[0][:7]
+    qb, qo = pack_queries(qs)
+    want = nt.ix.parallel_align_edit_csr(qb, qo, 2, NO_CAP)
+    assert len(qs) == 7 and int(want[0][-1]) >= 4
+    os.environ["AWRY_EDIT_CANDIDATE_CAP"] = "1"  # every chunk of more than one read is over capacity
+    try:
+        got = nt.ix.parallel_align_edit_csr(qb, qo, 2, NO_CAP)
+    finally:
+        del os.environ["AWRY_EDIT_CANDIDATE_CAP"]
+    assert len(got) == len(want) and same(got, want)

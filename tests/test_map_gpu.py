@@ -422,3 +422,43 @@ def test_invalid_reads_fail_the_batch_and_name_the_read(nt):
     aa.close()
     got = nt.ix.map_string(bytes(nt.text[100:1124]), 12, 20)  # and the index still answers: a 1024-letter read, and its reverse complement
     assert got == [(0, 100, 0, 60, 0, "1024=", 0)] and nt.ix.map_string(mp.rc(nt.text[100:1124]), 12, 20) == [(0, 100, 1, 60, 0, "1024=", 0)]
+
+
+# ---- the chunk driver's rarely taken branches, on 64 reads of 101 letters ------------------------------------------------------------
+
+from tests.test_smems_gpu import all_equal, shrunk_cap, small_reads, with_bad_read  # noqa: E402
+
+NO_CHAIN = P_MAIN._replace(min_score=10 ** 6)  # above any reachable score
+
+
+def assert_no_records(got, n):
+    off, maps, pos, coff, cg, st = got
+    assert np.array_equal(off, np.zeros(n + 1, np.uint64)) and len(maps) == 0 and len(pos) == 0 and np.array_equal(coff, [0]) and len(cg) == 0
+    assert st.dtype == np.uint8 and np.array_equal(st, np.zeros(n, np.uint8))
+
+
+def test_chunks_without_smems_and_without_chains_give_zero_offsets_and_ok_status(nt):
+    reads = small_reads(nt)
+    qb, qo = pack_queries(reads)
+    assert_no_records(nt.ix.parallel_map_csr(qb, qo, 102, 20, 3, 6, 4, *P_MAIN), len(reads))  # min_len above every read's length: no candidate
+    assert int(nt.ix.parallel_locate_smems_csr(qb, qo, KEY[1], KEY[0])[2][-1]) >= len(reads)  # seeds, and no chain of them
+    assert_no_records(nt.ix.parallel_map_csr(qb, qo, *KEY, 3, 6, 4, *NO_CHAIN), len(reads))
+
+
+def test_a_bad_read_is_named_under_its_own_index_before_the_capacity_test_splits_its_chunk(nt):
+    reads = small_reads(nt, 6)
+    # '#' is '$' on the reverse strand; the non-ASCII byte is 'N' there, so only the read as given is rejected -- under the read's index
+    for bad, why in ((b"AC$T", "'$' or '#'"), (b"", "empty query"), (b"AC#T", "'$' or '#'"), (bytes([0x41, 0x80, 0x43]), "non-ASCII")):
+        with shrunk_cap("AWRY_ANCHOR_HIT_CAP"):
+            with pytest.raises(AwryError) as e:
+                nt.ix.parallel_map_csr(*pack_queries(with_bad_read(reads, bad)), *KEY, 3, 6, 4, *P_MAIN)
+        print(bad, str(e.value))
+        assert e.value.code == ERR_INVALID_QUERY and "query 3: " in str(e.value) and why in str(e.value), bad
+
+
+def test_seven_reads_halved_down_to_single_reads_equal_the_uncapped_call(nt):
+    qb, qo = pack_queries(small_reads(nt, 7))
+    want = nt.ix.parallel_map_csr(qb, qo, *KEY, 3, 6, 4, *P_MAIN)
+    assert int(want[0][-1]) >= 7
+    with shrunk_cap("AWRY_ANCHOR_HIT_CAP"):
+        assert all_equal(want, nt.ix.parallel_map_csr(qb, qo, *KEY, 3, 6, 4, *P_MAIN))

@@ -299,3 +299,17 @@ def test_letters_and_classes_stay_two_tables(nt_index, nt_text):
     letters, classes = mr.brute_force(text, qs[0], 0, 0)[0], pattern_ref.brute_force(text, qs[0], 0, 0)[0]
     assert int(classes[0]) >= 1 and int(classes[0]) != int(letters[0])  # the inputs cannot hide a swapped table
     assert int(nt_index.parallel_count_pattern_csr(qb, qo, 0)[0, 0]) != int(nt_index.parallel_count_mismatch_csr(qb, qo, 0)[0, 0])
+
+
+def test_seven_reads_halved_down_to_single_reads_equal_the_uncapped_call(nt_index, nt_text):
+    qs = [bytes(q) for q in synth.sampled_queries(nt_text[0], 7, 25, 3)]
+    qb, qo = pack_queries(qs)
+    want = {k: _results(nt_index, qb, qo, k) for k in (1, 2)}
+    assert int(want[2][1][-1]) >= 7
+    os.environ["AWRY_MISMATCH_LEAF_CAP"] = "1"  # every chunk of more than one read is over capacity
+    try:
+        for k in (1, 2):
+            got = _results(nt_index, qb, qo, k)
+            assert len(got) == len(want[k]) and _same(got, want[k]), k
+    finally:
+        del os.environ["AWRY_MISMATCH_LEAF_CAP"]

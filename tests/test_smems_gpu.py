@@ -390,3 +390,72 @@ def test_invalid_query_in_a_batch_is_rejected_and_out_pointers_stay(nt):
     rc = L.awry_locate_smems_batch(nt.ix._h, qb.ctypes.data, qo.ctypes.data_as(u64p), 2, 1, 10, C.byref(off), C.byref(sm), C.byref(hoff), C.byref(hits), C.byref(gp))
     assert rc == ERR_INVALID_QUERY and not off and not sm and not hoff and not hits and not gp
     assert nt.ix.smems_string(b"ACGT") == nt.ref(b"ACGT")  # and the index still answers
+
+
+# ---- small batches through the chunk driver's rarely taken branches (shared with the chain, align-chains and map suites) ---------
+
+def small_reads(w, n=64, L=101, seed=123):
+    """n reads of L letters out of the text, free of N: every fourth is two halves from two places (two chains), every other of the
+    rest has one substitution in the middle (two SMEMs)"""
+    rng = np.random.default_rng(seed)
+    text = bytes(w.text)
+    out = []
+    while len(out) < n:
+        p, p2 = (int(x) for x in rng.integers(0, len(text) - 1 - L, size=2))
+        q = bytearray(text[p:p + L] if len(out) % 4 else text[p:p + 50] + text[p2:p2 + L - 50])
+        if len(out) % 4 == 2:
+            q[L // 2] = b"ACGT"[(b"ACGT".index(q[L // 2]) + 1) % 4] if q[L // 2] in b"ACGT" else 0
+        if all(c in b"ACGT" for c in q):
+            out.append(bytes(q))
+    return out
+
+
+class shrunk_cap:
+    """with shrunk_cap("AWRY_ANCHOR_HIT_CAP"): every chunk of more than one read is over capacity and halves down to single reads"""
+
+    def __init__(self, *names):
+        self.names = names
+
+    def __enter__(self):
+        for k in self.names:
+            os.environ[k] = "1"
+
+    def __exit__(self, *exc):
+        for k in self.names:
+            del os.environ[k]
+
+
+def with_bad_read(reads, bad):
+    """7 reads with `bad` in the middle"""
+    return reads[:3] + [bad] + reads[3:6]
+
+
+def all_equal(a, b):
+    return len(a) == len(b) and all(x.shape == y.shape and np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def test_a_chunk_without_smems_gives_zero_offsets(nt):
+    reads = small_reads(nt)
+    off, sm, hoff, g, p = nt.ix.parallel_locate_smems_csr(*pack_queries(reads), 50, 102)  # min_len above every read's length
+    assert np.array_equal(off, np.zeros(len(reads) + 1, np.uint64)) and len(sm) == 0
+    assert np.array_equal(hoff, [0]) and len(g) == 0 and p.shape == (0, 2)
+
+
+def test_a_bad_read_is_named_before_the_capacity_test_splits_its_chunk(nt):
+    reads = small_reads(nt, 6)
+    assert int(nt.ix.parallel_locate_smems_csr(*pack_queries(reads), 50, 12)[2][-1]) > 6  # over a capacity of one hit
+    with shrunk_cap("AWRY_ANCHOR_HIT_CAP"):
+        for bad in (b"AC$T", b"", bytes([0x41, 0x80])):
+            with pytest.raises(AwryError) as e:
+                nt.ix.parallel_locate_smems_csr(*pack_queries(with_bad_read(reads, bad)), 50, 12)
+            assert e.value.code == ERR_INVALID_QUERY and "query 3:" in str(e.value), bad
+
+
+def test_seven_reads_halved_down_to_single_reads_equal_the_uncapped_call(nt):
+    reads = small_reads(nt, 7)
+    qb, qo = pack_queries(reads)
+    want = nt.ix.parallel_locate_smems_csr(qb, qo, 50, 12), nt.ix.parallel_locate_anchors_csr(qb, qo, 50, 12)
+    assert all(int(w[2][-1]) > 7 for w in want)
+    with shrunk_cap("AWRY_ANCHOR_HIT_CAP"):
+        got = nt.ix.parallel_locate_smems_csr(qb, qo, 50, 12), nt.ix.parallel_locate_anchors_csr(qb, qo, 50, 12)
+    assert all_equal(want[0], got[0]) and all_equal(want[1], got[1])
