@@ -41,17 +41,7 @@ __global__ __launch_bounds__(256) void count_nt2_quad_kernel(DevIndex ix, const 
       if (fresh) {
         if (USE_SEED) {
           const uint64_t sidx = ((w >> (2 * (L - k))) & ((1ull << (2 * k)) - 1));
-          const SeedEntry e = seed[sidx];
-          const uint32_t scnt = seed_cnt(e);
-          sp = scnt ? e.sp : 1u;
-          ep = scnt ? e.sp + scnt - 1u : 0u;
-          i = L - k;
-          if (scnt == 1u && i > 0) {  // singleton: it survives the next step only if BWT[sp] is the next letter
-            const uint32_t nc = (uint32_t)(w >> (2 * (i - 1))) & 3u;
-            if (seed_sym(e) != (int)(nc == 3u ? 5u : nc + 1u)) { sp = 1u; ep = 0u; }
-          }
-          // count not representable, or a position seed (ix.seed_pos) that would have to be stepped: start without the table
-          if (scnt == SEED_CNT_SAT || (ix.seed_pos && scnt == 1u && sp <= ep && i > 0)) i = -1;
+          kmer_seed_start(seed[sidx], w, L - k, ix.seed_pos, sp, ep, i);
           if (TALLY) t_probe++;
         }
         if (!USE_SEED || i < 0) {
@@ -134,17 +124,7 @@ __global__ __launch_bounds__(256) void count_nt2_quad4_kernel(DevIndex ix, const
           w = __shfl(wq, (lane & ~3) | t, 64);
           if (USE_SEED) {
             const uint64_t ev = __shfl(eq, (lane & ~3) | t, 64);
-            const SeedEntry e{(uint32_t)ev, (uint32_t)(ev >> 32)};
-            const uint32_t scnt = seed_cnt(e);
-            sp = scnt ? e.sp : 1u;
-            ep = scnt ? e.sp + scnt - 1u : 0u;
-            i = L - k;
-            if (scnt == 1u && i > 0) {  // singleton: it survives the next step only if BWT[sp] is the next letter
-              const uint32_t nc = (uint32_t)(w >> (2 * (i - 1))) & 3u;
-              if (seed_sym(e) != (int)(nc == 3u ? 5u : nc + 1u)) { sp = 1u; ep = 0u; }
-            }
-            // count not representable, or a position seed (ix.seed_pos) that would have to be stepped: start without the table
-            if (scnt == SEED_CNT_SAT || (ix.seed_pos && scnt == 1u && sp <= ep && i > 0)) i = -1;
+            kmer_seed_start(SeedEntry{(uint32_t)ev, (uint32_t)(ev >> 32)}, w, L - k, ix.seed_pos, sp, ep, i);
             if (TALLY) t_probe++;
           }
           if (!USE_SEED || i < 0) {

@@ -1,4 +1,4 @@
-// kernels_quad.hip.h -- nucleotide quad primitives: a quad of lanes ranks one 128-B block; text windows for seed-and-verify.
+// kernels_quad.hip.h -- nucleotide quad primitives: a quad of lanes ranks one 128-B block; the start of a search from its seed entry; text windows for seed-and-verify.
 // A part of kernels.hip.h (one header, cut by kernel family): included there, in order, and not on its own.
 #pragma once
 
@@ -70,6 +70,33 @@ __device__ __forceinline__ void quad_step(const uint64_t* __restrict__ blocks, R
   const Row v1 = quad_sum(quad_rank_part(d1, x, r1, c, l));
   sp = cl + v0;
   ep = cl + v1 - 1;
+}
+
+// Where a search starts from its seed entry (32-bit rows): reads_body uses the first two, count_nt2_quad_kernel and
+// count_nt2_quad4_kernel the third (the chunk, resume and wide kernels keep their own text).
+// The range of an entry: its rows, or the empty range [1, 0] where it has none.  Returns the number of rows.
+__device__ __forceinline__ uint32_t seed_entry_range(SeedEntry e, uint32_t& sp, uint32_t& ep) {
+  const uint32_t scnt = seed_cnt(e);
+  sp = scnt ? e.sp : 1u;
+  ep = scnt ? e.sp + scnt - 1u : 0u;
+  return scnt;
+}
+// A singleton entry keeps BWT[sp]: its row survives the next step only if that is the next letter, letter i - 1 of the query
+// (at bit sh of w).  Entries of scnt != 1 rows and searches with no letter left (i == 0) are not touched.
+__device__ __forceinline__ void seed_singleton_check(SeedEntry e, uint32_t scnt, uint64_t w, int sh, int i, uint32_t& sp, uint32_t& ep) {
+  if (scnt == 1u && i > 0) {
+    const uint32_t nc = (uint32_t)(w >> sh) & 3u;
+    if (seed_sym(e) != (int)(nc == 3u ? 5u : nc + 1u)) { sp = 1u; ep = 0u; }
+  }
+}
+// Start of a k-mer (one word w) with i0 letters left of its seed window: the checked range of its entry and i = i0; or
+// i = -1 where the search has to start without the table -- a count the entry cannot represent, or a position seed
+// (seed_pos: sp is a text position, not a row) that would have to be stepped.
+__device__ __forceinline__ void kmer_seed_start(SeedEntry e, uint64_t w, int i0, uint32_t seed_pos, uint32_t& sp, uint32_t& ep, int& i) {
+  const uint32_t scnt = seed_entry_range(e, sp, ep);
+  i = i0;
+  seed_singleton_check(e, scnt, w, 2 * (i - 1), i, sp, ep);
+  if (scnt == SEED_CNT_SAT || (seed_pos && scnt == 1u && sp <= ep && i > 0)) i = -1;
 }
 
 // Seed-and-verify switch: compare the remaining i letters with the text instead of taking i more LF steps?

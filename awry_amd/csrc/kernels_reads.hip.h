@@ -72,9 +72,7 @@ __device__ __forceinline__ void reads_body(const DevIndex& ix, const uint64_t* _
           uint32_t scnt = SEED_CNT_SAT;
           if (seeded) {
             e = seed[(win & ((1ull << (2 * k)) - 1))];
-            scnt = seed_cnt(e);
-            sp = scnt ? e.sp : 1u;
-            ep = scnt ? e.sp + scnt - 1u : 0u;
+            scnt = seed_entry_range(e, sp, ep);
             i = first;
           }
           if (!seeded || scnt == SEED_CNT_SAT) {  // no table, or a count the entry cannot represent
@@ -85,10 +83,7 @@ __device__ __forceinline__ void reads_body(const DevIndex& ix, const uint64_t* _
           }
           steps_done = 0;
           w = i > 0 ? qw[(i - 1) >> 5] : 0;
-          if (USE_SEED && scnt == 1u && i > 0) {  // singleton: it survives the next step only if BWT[sp] is the next letter
-            const uint32_t nc = (uint32_t)(w >> (2 * ((i - 1) & 31))) & 3u;
-            if (seed_sym(e) != (int)(nc == 3u ? 5u : nc + 1u)) { sp = 1u; ep = 0u; }
-          }
+          if (USE_SEED) seed_singleton_check(e, scnt, w, 2 * ((i - 1) & 31), i, sp, ep);
           if (seeded && ix.seed_pos && scnt == 1u && sp <= ep) {
             // position seed: e.sp is SA[row], the text position of the single candidate -- there is no row to step from
             if (i == 0) {  // the read is the seed window itself

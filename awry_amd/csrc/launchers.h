@@ -206,6 +206,34 @@ unsigned resident_grid(const Replica& r, K kernel) {
   return (unsigned)bound_blocks((uint64_t)r.num_cus * (unsigned)per_cu);
 }
 
+// Packed queries on a wide-row replica (64-bit rows), for both packed launchers: k-mers (one word, d_tally optional) and reads
+// (d_lens, d_range_start optional).  The census is the k-mer path's: d_tally goes with equal lengths only.  The caller holds
+// the stream's ScratchLock.
+void launch_count_nt2_wide(Replica& r, const uint64_t* d_words, uint64_t n, int L, uint64_t* d_counts, uint64_t* d_range_start, bool use_seed,
+                           hipStream_t s, const uint32_t* d_lens, unsigned long long* d_tally) {
+  require(!(d_lens && d_tally), "internal: no census for reads of unequal lengths");
+  const bool sdw = use_seed && r.seed_k > 0 && r.dev.seed64 && (d_lens || r.seed_k <= L);  // ragged reads decide per read
+  const dim3 bw(256);
+  if (sdw && wide_two_phase(n)) {  // per-lane probe pass, then the quads on what has to be stepped
+    Nt2Survivors sv, fb;
+    const unsigned nblk = (unsigned)r.num_cus * 8;
+    two_phase_lists(r, s, n, nblk, 0u, &sv, &fb);
+    if (d_lens) hipLaunchKernelGGL((count_nt2_wide_probe_kernel<true, false>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens, d_tally);
+    else with_flags(d_tally != nullptr, [&](auto T) {
+      hipLaunchKernelGGL((count_nt2_wide_probe_kernel<false, T()>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens, d_tally);
+    });
+    with_flags(d_lens != nullptr, [&](auto R) {
+      hipLaunchKernelGGL((count_nt2_wide_kernel<true, R(), true>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, d_lens, d_tally, sv);
+    });
+  } else {
+    const dim3 gw(grid_for(r, n * 4, 256));
+    with_flags(sdw, d_lens != nullptr, [&](auto S, auto R) {
+      hipLaunchKernelGGL((count_nt2_wide_kernel<S(), R()>), gw, bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, d_lens, d_tally);
+    });
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
 // d_lens != nullptr: read q has d_lens[q] letters (1..L) in its W = ceil(L / 32) words; else every read has L letters
 void launch_count_nt2_long(Replica& r, const uint64_t* d_words, uint64_t n, int L, uint64_t* d_counts, uint64_t* d_range_start,
                            bool use_seed, hipStream_t s, const uint32_t* d_lens = nullptr) {
@@ -213,24 +241,8 @@ void launch_count_nt2_long(Replica& r, const uint64_t* d_words, uint64_t n, int 
   require(L >= 1 && L <= 1 << 20, "packed read length out of range");
   if (n == 0) return;
   const ScratchLock scratch_lock(r, s);
-  if (r.wide) {  // 64-bit rows
-    const bool sdw = use_seed && r.seed_k > 0 && r.dev.seed64 && (d_lens || r.seed_k <= L);
-    const dim3 gw(grid_for(r, n * 4, 256)), bw(256);
-    if (sdw && wide_two_phase(n)) {  // per-lane probe pass, then the quads on what has to be stepped
-      Nt2Survivors sv, fb;
-      const unsigned nblk = (unsigned)r.num_cus * 8;
-      two_phase_lists(r, s, n, nblk, 0u, &sv, &fb);
-      with_flags(d_lens != nullptr, [&](auto R) {
-        hipLaunchKernelGGL((count_nt2_wide_probe_kernel<R(), false>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens, (unsigned long long*)nullptr);
-        hipLaunchKernelGGL((count_nt2_wide_kernel<true, R(), true>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, d_lens, (unsigned long long*)nullptr, sv);
-      });
-      HIP_CHECK(hipGetLastError());
-      return;
-    }
-    with_flags(sdw, d_lens != nullptr, [&](auto S, auto R) {
-      hipLaunchKernelGGL((count_nt2_wide_kernel<S(), R()>), gw, bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, d_lens, (unsigned long long*)nullptr);
-    });
-    HIP_CHECK(hipGetLastError());
+  if (r.wide) {
+    launch_count_nt2_wide(r, d_words, n, L, d_counts, d_range_start, use_seed, s, d_lens, nullptr);
     return;
   }
   const bool sd = use_seed && r.seed_k > 0 && (d_lens || r.seed_k <= L);  // ragged reads decide per read
@@ -272,24 +284,8 @@ void launch_count_nt2(Replica& r, const uint64_t* d_words, uint64_t n, int L, ui
   require(L >= 1 && L <= 32, "packed k-mer length must be in 1..32");
   if (n == 0) return;
   const ScratchLock scratch_lock(r, s);
-  if (r.wide) {  // 64-bit rows: one word per k-mer is the W = 1 case of the wide kernel
-    const bool sdw = use_seed && r.seed_k > 0 && r.dev.seed64 && r.seed_k <= L;
-    const dim3 gw(grid_for(r, n * 4, 256)), bw(256);
-    if (sdw && wide_two_phase(n)) {
-      Nt2Survivors sv, fb;
-      const unsigned nblk = (unsigned)r.num_cus * 8;
-      two_phase_lists(r, s, n, nblk, 0u, &sv, &fb);
-      with_flags(d_tally != nullptr, [&](auto T) {
-        hipLaunchKernelGGL((count_nt2_wide_probe_kernel<false, T()>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, (uint64_t*)nullptr, sv, (const uint32_t*)nullptr, d_tally);
-      });
-      hipLaunchKernelGGL((count_nt2_wide_kernel<true, false, true>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, (uint64_t*)nullptr, (const uint32_t*)nullptr, d_tally, sv);
-      HIP_CHECK(hipGetLastError());
-      return;
-    }
-    with_flags(sdw, [&](auto S) {
-      hipLaunchKernelGGL((count_nt2_wide_kernel<S(), false>), gw, bw, 0, s, r.dev, d_words, n, L, d_counts, (uint64_t*)nullptr, (const uint32_t*)nullptr, d_tally);
-    });
-    HIP_CHECK(hipGetLastError());
+  if (r.wide) {  // one word per k-mer is the W = 1 case of the wide kernel
+    launch_count_nt2_wide(r, d_words, n, L, d_counts, nullptr, use_seed, s, nullptr, d_tally);
     return;
   }
   // k-mers shorter than the seed table's k: their own complete table ("rung", built on first use) -- the entry IS the
