@@ -63,10 +63,11 @@ struct LocatedRecords {  // what the stage leaves on the device
 // 2i = read i, query 2i + 1 = its reverse complement); everything after that is over the 2 (c.hi - c.lo) queries, a rejected query
 // is raised under its read's index, and the capacity test counts reads, so a read's two strands are never split.  `what` names the
 // records in the message of a chunk with 2^32 of them.  false: the chunk's located hits exceed the capacity and it holds more than
-// one read -- nothing has been located.  Two stream synchronisations (one with max_hits == 0 or without records).
+// one read -- nothing has been located.  Two stream synchronisations (one with max_hits == 0 or without records).  unit: the reads
+// that are never split (2: a read pair) -- a chunk of one unit is never refused, or its halving would not end.
 template <class Find>
 bool find_records(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, const Find& find, uint64_t max_hits, int copies, const char* what,
-                  LocatedRecords& L) {
+                  LocatedRecords& L, uint64_t unit = 1) {
   const hipStream_t s = r.stream;
   const uint64_t nreads = c.hi - c.lo, n = copies * nreads;
   ChunkBuffers& cb = L.cb;
@@ -105,7 +106,7 @@ bool find_records(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard
   launch_scan(r, L.located.p, total, L.hit_off.p, L.lscratch.p, s);
   HIP_CHECK(hipMemcpyAsync(&L.nhits, L.hit_off.p + total, 8, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  return !(L.nhits > anchor_hit_cap() && nreads > 1);
+  return !(L.nhits > anchor_hit_cap() && nreads > unit);
 }
 
 // the locate pipeline over the flat record list: text positions, and with want_pos (record, offset) pairs

@@ -49,15 +49,16 @@ struct ChainOnDevice {
 // chains and members, the fill pass, and sink(r, ChainOnDevice), which returns with the stream synchronised.  false: the chunk's
 // located hits exceed the capacity and it holds more than one read -- the sink has not been called.  both_strands: every read is
 // two queries, itself and its reverse complement (find_records, copies == 2); the sink's view is over the 2 (c.hi - c.lo) queries.
+// unit: find_records' (2 for read pairs, whose chunks are cut between pairs).
 template <class Sink>
 bool chain_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, uint32_t min_len, uint64_t max_hits, const ChainParams& P,
-                 bool both_strands, Sink&& sink) {
+                 bool both_strands, Sink&& sink, uint64_t unit = 1) {
   const hipStream_t s = r.stream;
   const uint64_t n = (both_strands ? 2 : 1) * (c.hi - c.lo);
   for (uint64_t i = c.lo; i < c.hi; i++)
     if (qoff[i + 1] >= qoff[i] && qoff[i + 1] - qoff[i] >= (1ull << 31)) throw ArgError("a query of 2^31 letters or more");
   LocatedRecords L;
-  if (!find_records(r, qbytes, qoff, c, smem_finder(min_len), max_hits, both_strands ? 2 : 1, "SMEMs", L)) return false;
+  if (!find_records(r, qbytes, qoff, c, smem_finder(min_len), max_hits, both_strands ? 2 : 1, "SMEMs", L, unit)) return false;
   DevBuf<uint64_t> soff(n + 1);
   DevBuf<Seed> seeds;
   if (L.total) {

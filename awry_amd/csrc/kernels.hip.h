@@ -53,6 +53,12 @@
 //                         + MAP_SELECT_KERNEL<FILL>          one read per lane: rank the aligned chains of both strands by selection, drop
 //                                                            redundant spans, MAPQ; count pass, scan, fill pass [kernels_map]
 //                         + MAP_GATHER_KERNEL                the reported alignments as a chain list for the CIGAR fill pass [kernels_map]
+//   map read pairs        PAIR_WINDOWS_KERNEL                one candidate slot per lane: is it an anchor, and the window of starts in which it
+//                                                            expects the other mate [kernels_pair]
+//                         + pair_sub_windows / PAIR_BEST_HIT / PAIR_RESCUED kernels: windows cut for the edit scan, the smallest (distance,
+//                                                            position) hit of a window, the rescued candidate [kernels_pair]
+//                         + PAIR_SELECT_KERNEL<FILL>         one pair per lane: rescued candidates appended, the pair of smallest cost, pair
+//                                                            MAPQ, flags, insert; count pass, scan, fill pass [kernels_pair]
 //   count, wide rows      count_nt2_wide_kernel, count_nt2_wide_probe_kernel   64-bit rows [kernels_wide]
 //   locate                LOCATE_TILE_KERNEL<A>              hit -> row, sampled / verified hits finished [this file]
 //                         + LOCATE_WALK_NT_LANE_KERNEL       LF walks of the rest, one hit per lane, whole block per step [this file]
@@ -575,3 +581,4 @@ __global__ __launch_bounds__(256) void locate_walk_nt_lane_kernel(DevIndex ix, u
 #include "kernels_chain.hip.h"     // localise, tally_add, Anchor
 #include "kernels_chain_align.hip.h"  // Seed, Chain, ByteStream, edit_symbols, align_bam_op
 #include "kernels_map.hip.h"       // Aln, Chain, Seed, localise
+#include "kernels_pair.hip.h"      // MapRec, localise, EDIT_MAX_LEN

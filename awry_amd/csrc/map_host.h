@@ -31,6 +31,28 @@ struct MapHits {  // one shard's result, in read order
   std::vector<uint32_t> cigar;  // the runs, back to back
 };
 
+// The CIGAR fill over nwin reported alignments, d_win[k] = the index of record k's alignment among S's chains (d_nops: their run
+// counts): the alignments as a chain list of their own (map_gather_kernel), then the fill pass over them only, in sub-batches.
+// n_ops[nwin] (host) receives the run counts, the runs are appended to `cigar`.  Shared with pair_chunk (pair_host.h).
+void fill_reported_cigars(Replica& r, const uint8_t* text8, const ChainOnDevice& v, const SelectedChains& S, const uint64_t* d_nops, const uint32_t* d_win,
+                          uint64_t nwin, int band, uint32_t Lmax, uint64_t* n_ops, std::vector<uint32_t>& cigar) {
+  const hipStream_t s = r.stream;
+  DevBuf<uint32_t> win_query(nwin);
+  DevBuf<uint64_t> win_mcnt(nwin), win_nops(nwin), win_moff(nwin + 1), wscratch(scan_tiles(nwin) + 1);
+  flat_launch(r, s, nwin, map_gather_kernel, d_win, nwin, S.query.p, S.moff.p, S.members.p, d_nops, win_query.p, win_mcnt.p, win_nops.p, nullptr, nullptr);
+  launch_scan(r, win_mcnt.p, nwin, win_moff.p, wscratch.p, s);
+  uint64_t nwm = 0;
+  HIP_CHECK(hipMemcpyAsync(&nwm, win_moff.p + nwin, 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(n_ops, win_nops.p, nwin * 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  DevBuf<Seed> win_members(std::max<uint64_t>(nwm, 1));
+  flat_launch(r, s, nwin, map_gather_kernel, d_win, nwin, S.query.p, S.moff.p, S.members.p, d_nops, nullptr, nullptr, nullptr, win_moff.p, win_members.p);
+  const uint64_t sub = std::min(chain_align_sub_batch(), nwin);
+  DevBuf<uint64_t> coff(sub + 1), cscratch(scan_tiles(sub) + 1);
+  for (uint64_t at = 0; at < nwin; at += sub)
+    fill_cigar(r, text8, v.cb, win_query.p + at, win_moff.p + at, win_members.p, std::min(sub, nwin - at), band, Lmax, win_nops.p + at, coff.p, cscratch.p, cigar);
+}
+
 // One chunk, from where chain_chunk's fill pass leaves the doubled batch: the first min(n_chains, A) chains of each of the 2 n
 // queries, the alignment count pass over all of them in sub-batches (before anything else: the selection needs every record),
 // the selection per read, and the CIGAR fill over the reported alignments, appended to `out`.
@@ -81,23 +103,8 @@ void map_chunk(Replica& r, const uint8_t* text8, const ChainOnDevice& v, uint32_
     HIP_CHECK(hipStreamSynchronize(s));
     return;
   }
-  // the reported alignments as a chain list of their own, then the fill pass over them only
-  DevBuf<uint32_t> win_query(nwin);
-  DevBuf<uint64_t> win_mcnt(nwin), win_nops(nwin), win_moff(nwin + 1), wscratch(scan_tiles(nwin) + 1);
-  flat_launch(r, s, nwin, map_gather_kernel, win.p, nwin, S.query.p, S.moff.p, S.members.p, nops.p, win_query.p, win_mcnt.p, win_nops.p, nullptr, nullptr);
-  launch_scan(r, win_mcnt.p, nwin, win_moff.p, wscratch.p, s);
-  uint64_t nwm = 0;
   out.n_ops.resize(at_m + nwin);
-  HIP_CHECK(hipMemcpyAsync(&nwm, win_moff.p + nwin, 8, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(out.n_ops.data() + at_m, win_nops.p, nwin * 8, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  DevBuf<Seed> win_members(std::max<uint64_t>(nwm, 1));
-  flat_launch(r, s, nwin, map_gather_kernel, win.p, nwin, S.query.p, S.moff.p, S.members.p, nops.p, nullptr, nullptr, nullptr, win_moff.p, win_members.p);
-  const uint64_t sub = std::min(chain_align_sub_batch(), nwin);
-  DevBuf<uint64_t> coff(sub + 1), cscratch(scan_tiles(sub) + 1);
-  for (uint64_t at = 0; at < nwin; at += sub)
-    fill_cigar(r, text8, v.cb, win_query.p + at, win_moff.p + at, win_members.p, std::min(sub, nwin - at), band, (uint32_t)Lmax, win_nops.p + at, coff.p,
-               cscratch.p, out.cigar);
+  fill_reported_cigars(r, text8, v, S, nops.p, win.p, nwin, band, (uint32_t)Lmax, out.n_ops.data() + at_m, out.cigar);
 }
 
 // awry_map_batch: shards over the replicas, results stitched in read order into pinned-pool arrays.  The out-pointers are written

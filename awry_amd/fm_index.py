@@ -34,6 +34,8 @@ CHAIN_MAX_SEEDS, CHAIN_MAX_LOOKBACK, Q_SEED_CAP = 4096, 64, 8  # AWRY_CHAIN_MAX_
 CHAIN_ALIGN_MAX_BAND, CHAIN_ALIGN_MAX_SKEW, CHAIN_ALIGN_MAX_LEN = 8, 16, 1024  # AWRY_CHAIN_ALIGN_MAX_BAND, _MAX_SKEW, _MAX_LEN
 ALN_OK, ALN_SKEW, ALN_BAD_CHAIN = 0, 1, 2  # AWRY_ALN_OK, AWRY_ALN_SKEW, AWRY_ALN_BAD_CHAIN
 MAP_MAX_CHAINS, MAP_SECONDARY = 8, 1  # AWRY_MAP_MAX_CHAINS, AWRY_MAP_SECONDARY
+MAP_PROPER_PAIR, MAP_RESCUED, MAP_MATE_UNMAPPED = 2, 4, 8  # AWRY_MAP_PROPER_PAIR, AWRY_MAP_RESCUED, AWRY_MAP_MATE_UNMAPPED
+PAIR_MAX_INSERT, PAIR_MAX_ANCHORS, PAIR_NO_CHAIN = 1 << 20, 4, 0xFFFFFFFF  # AWRY_PAIR_MAX_INSERT, AWRY_PAIR_MAX_ANCHORS, AWRY_PAIR_NO_CHAIN
 CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}  # the BAM op codes the alignment pass produces
 
 
@@ -834,6 +836,75 @@ class FmIndex:
         dev_scan_counts in between"""
         _check(self._L.awry_dev_map_select(self._h, slot, d_aln_off, d_alns, d_chains, d_chain_status, n, int(chains_per_strand), int(max_report),
                                            d_n_maps, d_read_status, d_map_off, d_maps, d_sel, d_pos, stream))
+
+    # ------------------------------------------------------------------ map read pairs: insert-size pairing, mate rescue, proper-pair flag
+    def parallel_map_pairs_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4,
+                               band: int = 4, min_insert: int = 0, max_insert: int = 1000, unpaired_penalty: int = 4, rescue_anchors: int = 2,
+                               rescue_edits: int = 4, max_seeds: int = 1024, lookback: int = 32, max_gap: int = 1000, max_skew: int = 100,
+                               min_score: int = 20, want_pos: bool = True, want_cigar: bool = True):
+        """the 2P reads interleaved (read 2p and 2p + 1 are the mates of pair p) -> (map_off uint64[2P+1], maps MAP_DTYPE[total], pos
+        uint64[total, 2], cigar_off uint64[total+1], cigar uint32[runs], status uint8[2P], insert uint32[P]): at most one record per
+        read, the placements of the best pair (include/awry_hip.h states the definition): both mates carry the pair MAPQ and
+        MAP_PROPER_PAIR iff they lie on opposite strands of one record, forward first, min_insert <= outer distance <= max_insert
+        (insert[p] is that distance, else 0); a mate found by rescue -- within rescue_edits edits where the insert size puts it --
+        carries MAP_RESCUED; a read whose mate has no placement carries MAP_MATE_UNMAPPED and its single-end MAPQ"""
+        qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
+        qo = np.ascontiguousarray(qoff, dtype=np.uint64)
+        n = len(qo) - 1
+        off, mp, ps, coff, cg, st = _u64p(), C.POINTER(_lib.Map)(), C.POINTER(_lib.Pos)(), _u64p(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+        ins = C.POINTER(C.c_uint32)()
+        _check(self._L.awry_map_pairs_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(max_hits), int(max_seeds),
+                                            int(lookback), int(max_gap), int(max_skew), int(min_score), int(chains_per_strand), int(band),
+                                            int(min_insert), int(max_insert), int(unpaired_penalty), int(rescue_anchors), int(rescue_edits),
+                                            C.byref(off), C.byref(mp), C.byref(ps) if want_pos else None, C.byref(coff) if want_cigar else None,
+                                            C.byref(cg) if want_cigar else None, C.byref(st), C.byref(ins)))
+        offs = _adopt(self._L, off, n + 1, np.uint64)
+        tot = int(offs[-1])
+        maps = _adopt(self._L, mp, 32 * tot, np.uint8).view(MAP_DTYPE)
+        pos = _adopt(self._L, ps, 2 * tot, np.uint64).reshape(-1, 2) if want_pos else np.zeros((0, 2), np.uint64)
+        status, insert = _adopt(self._L, st, n, np.uint8), _adopt(self._L, ins, n // 2, np.uint32)
+        if not want_cigar:
+            return offs, maps, pos, np.zeros(0, np.uint64), np.zeros(0, np.uint32), status, insert
+        coffs = _adopt(self._L, coff, tot + 1, np.uint64)
+        return offs, maps, pos, coffs, _adopt(self._L, cg, int(coffs[-1]), np.uint32), status, insert
+
+    def parallel_map_pairs(self, reads1: Iterable, reads2: Iterable, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4, band: int = 4,
+                           min_insert: int = 0, max_insert: int = 1000, unpaired_penalty: int = 4, rescue_anchors: int = 2, rescue_edits: int = 4,
+                           **chain_params):
+        """-> per pair (record of reads1[p] or None, record of reads2[p] or None, insert), a record in parallel_map's form: (record,
+        offset, strand, mapq, edits, "57=1X43=", flags); chain_params: max_seeds, lookback, max_gap, max_skew, min_score"""
+        r1, r2 = list(reads1), list(reads2)
+        if len(r1) != len(r2):
+            raise ValueError("reads1 and reads2 must have one read per pair each")
+        off, mp, pos, coff, cg, _, ins = self.parallel_map_pairs_csr(*pack_queries([q for pair in zip(r1, r2) for q in pair]), min_len, max_hits,
+                                                                     chains_per_strand, band, min_insert, max_insert, unpaired_penalty, rescue_anchors,
+                                                                     rescue_edits, **chain_params)
+
+        def rec(i):
+            if off[i] == off[i + 1]:
+                return None
+            c = int(off[i])
+            return (int(pos[c][0]), int(pos[c][1]), int(mp[c]["strand"]), int(mp[c]["mapq"]), int(mp[c]["edits"]), cigar_string(cg[coff[c]:coff[c + 1]]),
+                    int(mp[c]["flags"]))
+        return [(rec(2 * p), rec(2 * p + 1), int(ins[p])) for p in range(len(r1))]
+
+    def dev_pair_windows(self, d_cand_off, d_cands, d_qoff, n_pairs, min_insert, max_insert, rescue_anchors, rescue_edits, d_win_query, d_win_first,
+                         d_win_count, stream=None, slot=0):
+        """device-resident rescue windows over the kept lists of 2 n_pairs interleaved reads (32-byte records of read i at [d_cand_off[i],
+        d_cand_off[i+1]) in rank order; d_qoff: the reads' own 2 n_pairs + 1 offsets): slot (2p + m) * rescue_anchors + a = candidate a
+        of mate m gets the doubled-batch query it seeks (d_win_query u32) and its window of starts (d_win_first u64, d_win_count u32;
+        count 0 where the candidate is no anchor or the window is empty)"""
+        _check(self._L.awry_dev_pair_windows(self._h, slot, d_cand_off, d_cands, d_qoff, n_pairs, int(min_insert), int(max_insert), int(rescue_anchors),
+                                             int(rescue_edits), d_win_query, d_win_first, d_win_count, stream))
+
+    def dev_pair_select(self, d_cand_off, d_cands, d_resc, d_read_status, n_pairs, min_insert, max_insert, unpaired_penalty, rescue_anchors, d_n_maps,
+                        d_map_off=None, d_maps=None, d_sel=None, d_pos=None, d_insert=None, stream=None, slot=0):
+        """device-resident pair choice over the kept lists and the rescued candidates d_resc[2 * rescue_anchors * n_pairs] (32-byte records
+        per window slot, edits == 0xFFFFFFFF for none): d_map_off None = the count pass (d_n_maps[2 n_pairs] u64); else the fill pass
+        writing read i's record at d_maps[d_map_off[i]] and, optionally, per record d_sel (u32: the index into d_cands, or 0x80000000 |
+        slot for a rescued record) and d_pos (2 u64), and d_insert[n_pairs] (u32); scan d_n_maps with dev_scan_counts in between"""
+        _check(self._L.awry_dev_pair_select(self._h, slot, d_cand_off, d_cands, d_resc, d_read_status, n_pairs, int(min_insert), int(max_insert),
+                                            int(unpaired_penalty), int(rescue_anchors), d_n_maps, d_map_off, d_maps, d_sel, d_pos, d_insert, stream))
 
     def debug_rank_all(self, rows: np.ndarray, slot=0) -> np.ndarray:
         """Occ of every non-sentinel symbol at each row through the kernels' all-symbol rank -> uint64[len(rows), S]

@@ -436,6 +436,54 @@ class FmIndex {
     awry_free_buffer(moff); awry_free_buffer(mp); awry_free_buffer(ps); awry_free_buffer(coff); awry_free_buffer(cg); awry_free_buffer(st);
     return out;
   }
+  // read pairs mapped together (no counterpart in the reference; the definition is in awry_hip.h, "map read pairs"): reads1[p] and
+  // reads2[p] are the mates of pair p.  Per pair at most one Mapping per mate -- the placements of the best pair, with the pair's
+  // mapping quality, AWRY_MAP_PROPER_PAIR when they face each other within [min_insert, max_insert] on one record, AWRY_MAP_RESCUED
+  // on a mate found within rescue_edits edits where its partner implies it, AWRY_MAP_MATE_UNMAPPED on a read whose mate has no
+  // placement -- and the insert size (0 unless proper).
+  struct PairParams {
+    uint64_t min_insert = 0, max_insert = 1000;
+    uint32_t unpaired_penalty = 4, rescue_anchors = 2;
+    int rescue_edits = 4;
+  };
+  struct PairMapping {
+    std::vector<Mapping> mate1, mate2;  // none or one each
+    uint32_t insert;
+  };
+  template <class StrRange>
+  std::vector<PairMapping> parallel_map_pairs(const StrRange& reads1, const StrRange& reads2, uint32_t min_len = 12, uint64_t max_hits = 50,
+                                              uint64_t chains_per_strand = 4, uint32_t band = 4, PairParams pp = PairParams(),
+                                              ChainParams p = ChainParams(), std::vector<uint8_t>* status = nullptr) {
+    std::vector<std::string_view> inter;
+    auto b = std::begin(reads2);
+    for (const auto& q : reads1) {
+      if (b == std::end(reads2)) throw std::invalid_argument("reads1 and reads2 must have one read per pair each");
+      inter.emplace_back(q);
+      inter.emplace_back(*b);
+      ++b;
+    }
+    if (b != std::end(reads2)) throw std::invalid_argument("reads1 and reads2 must have one read per pair each");
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(inter, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* moff = nullptr; awry_map_t* mp = nullptr; awry_pos_t* ps = nullptr; uint64_t* coff = nullptr; uint32_t* cg = nullptr; uint8_t* st = nullptr;
+    uint32_t* ins = nullptr;
+    check(awry_map_pairs_batch(h_, bytes.data(), off.data(), n, min_len, max_hits, p.max_seeds, p.lookback, p.max_gap, p.max_skew, p.min_score,
+                               chains_per_strand, band, pp.min_insert, pp.max_insert, pp.unpaired_penalty, pp.rescue_anchors, pp.rescue_edits, &moff, &mp, &ps,
+                               &coff, &cg, &st, &ins));
+    std::vector<PairMapping> out(n / 2);
+    for (uint64_t i = 0; i < n; i++) {
+      std::vector<Mapping>& to = i % 2 ? out[i / 2].mate2 : out[i / 2].mate1;
+      for (uint64_t j = moff[i]; j < moff[i + 1]; j++)
+        to.push_back({ps[j], mp[j].t_begin, mp[j].t_end, mp[j].edits, mp[j].chain_score, mp[j].chain_index, mp[j].strand, mp[j].mapq, mp[j].flags,
+                      std::vector<uint32_t>(cg + coff[j], cg + coff[j + 1])});
+      if (i % 2) out[i / 2].insert = ins[i / 2];
+    }
+    if (status) status->assign(st, st + n);
+    awry_free_buffer(moff); awry_free_buffer(mp); awry_free_buffer(ps); awry_free_buffer(coff); awry_free_buffer(cg); awry_free_buffer(st);
+    awry_free_buffer(ins);
+    return out;
+  }
   // src/fm_index.rs:559-582, 585-593
   SearchRange update_range_with_symbol(SearchRange r, char symbol) {
     awry_range_t o;

@@ -503,6 +503,63 @@ int awry_map_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qof
                    uint64_t chains_per_strand, uint64_t max_report, uint32_t band, uint64_t **map_off_out, awry_map_t **maps_out,
                    awry_pos_t **pos_out, uint64_t **cigar_off_out, uint32_t **cigar_out, uint8_t **status_out);
 
+/* ---- map read pairs: insert-size pairing, mate rescue, proper-pair flag (no counterpart in the reference) --------
+ * Short reads come in pairs: two reads from the ends of one fragment, on opposite strands, a known distance apart.  The mate places
+ * a read whose own seeds are ambiguous or missing.  This stage joins the ranked candidates of awry_map_batch with the k-edit scan
+ * and aligner of awry_locate_edit_batch / awry_align_edit_batch.  Nucleotide indexes only.  Everything is integer arithmetic and
+ * every tie is broken explicitly.
+ * Input.  n = 2P reads, interleaved: read 2p is mate 0 of pair p, read 2p + 1 is mate 1; odd n => AWRY_ERR_ARG.  Parameters: those
+ *   of awry_map_batch without max_report (min_len, max_hits, the five chain parameters, chains_per_strand = A, band), and min_insert
+ *   <= max_insert <= AWRY_PAIR_MAX_INSERT = 1 << 20; unpaired_penalty = U, in edits, 0 .. 255; rescue_anchors = G, 0 ..
+ *   AWRY_PAIR_MAX_ANCHORS = 4 (0: no rescue); rescue_edits = k, 0 .. AWRY_MAX_EDITS.
+ * Kept lists.  K_m, m in {0, 1}, is the list of ALL kept candidates of mate m in rank order, exactly as awry_map_batch defines rank
+ *   and redundancy: what max_report = 2 A would report, at most 16 entries.  Each read's status is the one awry_map_batch gives.
+ * Proper.  For x in a list of mate 0 and y in a list of mate 1 let f be the one on strand 0 and v the one on strand 1.  proper(x, y)
+ *   iff the strands differ and rec(f.t_begin) == rec(v.t_begin) (rec: the record awry_get_seq_location returns) and f.t_begin <=
+ *   v.t_begin and f.t_end <= v.t_end and min_insert <= v.t_end - f.t_begin <= max_insert.  FR orientation; the insert is the outer
+ *   distance.
+ * Rescue (G > 0).  For mate m, each of the first min(|K_m|, G) candidates x of K_m, at rank index a, is an ANCHOR iff no y in
+ *   K_{1-m} is proper with it and the other mate's length L' satisfies k < L' <= AWRY_EDIT_MAX_LEN.  An anchor seeks the other mate
+ *   on strand 1 - x.strand: query 4p + 2 (1 - m) + (1 - x.strand) of the doubled batch.  Its window of starts, in signed arithmetic,
+ *   both ends inclusive: x on strand 0: lo = x.t_begin + max(0, min_insert - L' - k), hi = x.t_begin + max_insert - L' + k; x on
+ *   strand 1: lo = x.t_end - max_insert, hi = min(x.t_begin, x.t_end - min_insert).  The window is cut to [0, n_text) and to the
+ *   record of x.t_begin, [seq_start[r], seq_start[r+1]) (the last record ends at n_text); it is empty if hi < lo.  The hits in the
+ *   window are the hits of awry_locate_edit_batch's rule at max_edits = k -- local minima of D over the whole text: they do not
+ *   depend on where the window is cut (the candidate cap plays no part: no pieces are looked up).  The anchor's rescue hit is the hit
+ *   with the smallest (D(s), s); its alignment is awry_align_edit_batch's (text_len, runs).  The rescued candidate z: strand 1 -
+ *   x.strand, t_begin = s, t_end = s + text_len, edits = D(s), chain_score = 0, chain_index = AWRY_PAIR_NO_CHAIN = 0xFFFFFFFF, flag
+ *   AWRY_MAP_RESCUED.
+ * Augmented lists.  Only original candidates are anchors.  K'_t is K_t followed by the rescued candidates aimed at mate t = 1 - m,
+ *   in anchor order a = 0, 1, ..; each z is appended unless its span intersects (the redundancy rule's test) the span of a
+ *   same-strand member already in K'_t, originals and earlier appended ones alike.  z is kept whether or not it turns out proper.
+ * Pair choice.  For (x, y) in K'_0 x K'_1: cost = x.edits + y.edits + (proper(x, y) ? 0 : U).  The pairs are ordered ascending by
+ *   (cost, !proper, index of x in K'_0, index of y in K'_1); the first is the best pair, the next, if any, the second.  Pair MAPQ: 0
+ *   if either read's status is AWRY_Q_SEED_CAP; else 60 if there is no second pair; else min(60, 10 * (cost2 - cost1)).
+ * Records.  At most one awry_map_t per read; no secondary or supplementary pair records.  Both K'_0 and K'_1 non-empty: read 2p gets
+ *   x and read 2p + 1 gets y of the best pair, both with the pair MAPQ, both with AWRY_MAP_PROPER_PAIR (= 2) iff the pair is proper,
+ *   a rescued candidate with AWRY_MAP_RESCUED (= 4), no other flag.  Exactly one non-empty (then it is K_m): that read's record is
+ *   K_m[0] exactly as awry_map_batch reports its primary, single-end MAPQ included, plus AWRY_MAP_MATE_UNMAPPED (= 8); the other
+ *   read has no record.  Both empty: no records, not an error.  insert[p] = v.t_end - f.t_begin for a proper best pair, else 0.
+ *   Reverse-strand spans and CIGARs stay as computed on rc(read) against the forward text; the runs of a rescued record are the edit
+ *   aligner's, at most AWRY_ALIGN_MAX_OPS.
+ *
+ * awry_map_pairs_batch: CSR output like awry_map_batch's -- map_off[2P + 1], maps, pos, cigar_off / cigar, status[2P] -- plus
+ * insert[P].  All but map_off_out nullable; cigar_off_out and cigar_out are given or omitted together.  Errors and index
+ * restrictions: awry_map_batch's; a bad new argument => AWRY_ERR_ARG; an invalid read fails the batch with AWRY_ERR_INVALID_QUERY
+ * and names the read's own index in the interleaved batch.  The out-pointers are written only on success.  Shards, chunks and the
+ * capacity fallback cut between pairs, never inside one; a rescue window of more than 64 starts (env AWRY_PAIR_SUB_WINDOW, read per
+ * call) is scanned in pieces.  No accelerator, seed-table length, replica count, chunk capacity, sub-batch size, grid cap or window
+ * cut changes any output. */
+enum { AWRY_PAIR_MAX_INSERT = 1 << 20, AWRY_PAIR_MAX_ANCHORS = 4 };
+enum { AWRY_MAP_PROPER_PAIR = 2, AWRY_MAP_RESCUED = 4, AWRY_MAP_MATE_UNMAPPED = 8 };
+#define AWRY_PAIR_NO_CHAIN 0xFFFFFFFFu
+int awry_map_pairs_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len,
+                         uint64_t max_hits, uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew,
+                         uint32_t min_score, uint64_t chains_per_strand, uint32_t band, uint64_t min_insert, uint64_t max_insert,
+                         uint32_t unpaired_penalty, uint32_t rescue_anchors, int rescue_edits, uint64_t **map_off_out,
+                         awry_map_t **maps_out, awry_pos_t **pos_out, uint64_t **cigar_off_out, uint32_t **cigar_out,
+                         uint8_t **status_out, uint32_t **insert_out);
+
 /* releases an array one of the calls above (or awry_locate / awry_read_query_file) returned.  Result arrays are pinned
  * host memory recycled through a process-wide pool (the device writes results straight into them); never pass them to
  * free().  AWRY_PINNED_CACHE_GB (default 4) bounds what the pool keeps between calls. */
@@ -756,6 +813,27 @@ int awry_dev_map_select(awry_index_t *idx, int slot, const uint64_t *d_aln_off, 
                         const awry_chain_t *d_chains, const uint8_t *d_chain_status, uint64_t n, uint32_t chains_per_strand,
                         uint32_t max_report, uint64_t *d_n_maps, uint8_t *d_read_status, const uint64_t *d_map_off,
                         awry_map_t *d_maps, uint32_t *d_sel, awry_pos_t *d_pos, void *stream);
+/* The rescue windows of awry_map_pairs_batch over a caller's kept lists: the candidates of read i (mate i & 1 of pair i >> 1) are
+ * d_cands[d_cand_off[i] .. d_cand_off[i+1]) in rank order, d_cand_off and d_qoff (the reads' own offsets: only the lengths are read)
+ * have 2 n_pairs + 1 entries.  Output at a fixed stride: slot w = (2p + m) G + a, G = rescue_anchors, is candidate a of mate m.  An
+ * anchor's slot gets d_win_query[w] = 4p + 2 (1 - m) + (1 - strand) (u32, the doubled-batch index of what it seeks), d_win_first[w]
+ * (u64) and d_win_count[w] (u32) = its window of starts after the cuts; a slot that is no anchor gets query 4p + 2 (1 - m), and it
+ * and an anchor with an empty window get first = 0, count = 0.  Nothing is written past 2 G n_pairs slots.  n_pairs < 2^28.  One
+ * slot per lane.  Queued on `stream`, no synchronisation. */
+int awry_dev_pair_windows(awry_index_t *idx, int slot, const uint64_t *d_cand_off, const awry_map_t *d_cands, const uint64_t *d_qoff,
+                          uint64_t n_pairs, uint64_t min_insert, uint64_t max_insert, uint32_t rescue_anchors, int rescue_edits,
+                          uint32_t *d_win_query, uint64_t *d_win_first, uint32_t *d_win_count, void *stream);
+/* Append and redundancy rule, pair order, MAPQ, flags and insert of awry_map_pairs_batch, a pure function of its arrays: the kept
+ * lists as above, d_resc[2 G n_pairs] = slot w's rescued candidate or edits == 0xFFFFFFFF for none (not read when rescue_anchors ==
+ * 0), d_read_status[2 n_pairs] (nullable).  The two-call protocol of awry_dev_map_select: d_map_off == NULL is the count pass ->
+ * d_n_maps[2 n_pairs]; otherwise the fill pass writes read i's record at d_maps[d_map_off[i]] and never a slot at or beyond
+ * d_map_off[i+1], per record (both nullable) d_sel[] (u32: the index into d_cands, or 0x80000000 | w for a rescued record) and
+ * d_pos[], and d_insert[n_pairs] (u32, nullable).  One pair per lane; best and second pair are tracked by re-reading the records, so
+ * no array lives in registers.  Queued on `stream`, no synchronisation. */
+int awry_dev_pair_select(awry_index_t *idx, int slot, const uint64_t *d_cand_off, const awry_map_t *d_cands, const awry_map_t *d_resc,
+                         const uint8_t *d_read_status, uint64_t n_pairs, uint64_t min_insert, uint64_t max_insert,
+                         uint32_t unpaired_penalty, uint32_t rescue_anchors, uint64_t *d_n_maps, const uint64_t *d_map_off,
+                         awry_map_t *d_maps, uint32_t *d_sel, awry_pos_t *d_pos, uint32_t *d_insert, void *stream);
 /* test hook of the all-symbol rank primitive: d_occ[i * S + s - 1] = Occ(s, d_rows[i]) for every non-sentinel symbol index s
  * (S = 5 nucleotide, 21 amino; inclusive of the row, as awry_update_range uses it); rows >= bwt_len give zeros */
 int awry_debug_rank_all(awry_index_t *idx, int slot, const void *d_rows, uint64_t n, void *d_occ, void *stream);

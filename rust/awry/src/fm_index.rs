@@ -217,6 +217,23 @@ impl Default for ChainParams {
     }
 }
 
+/// Parameters of [`FmIndex::parallel_map_pairs`] (include/awry_hip.h, awry_map_pairs_batch): `min_insert` <= `max_insert` <= 2^20,
+/// `unpaired_penalty` 0..=255 edits, `rescue_anchors` 0..=4 (0: no mate rescue), `rescue_edits` 0..=8.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct PairParams {
+    pub min_insert: u64,
+    pub max_insert: u64,
+    pub unpaired_penalty: u32,
+    pub rescue_anchors: u32,
+    pub rescue_edits: i32,
+}
+
+impl Default for PairParams {
+    fn default() -> Self {
+        PairParams { min_insert: 0, max_insert: 1000, unpaired_penalty: 4, rescue_anchors: 2, rescue_edits: 4 }
+    }
+}
+
 /// One chain of [`FmIndex::parallel_chains`]: its score, the spans it covers in query and text, and its seeds `(q_begin, q_len,
 /// t_pos)` first to last.
 #[derive(Clone, Debug, PartialEq, Eq)]
@@ -775,6 +792,76 @@ impl FmIndex {
             sys::awry_free_buffer(cigar_off as *mut std::os::raw::c_void);
             sys::awry_free_buffer(cigar as *mut std::os::raw::c_void);
             sys::awry_free_buffer(st as *mut std::os::raw::c_void);
+        }
+        Ok(out)
+    }
+
+    /// Read pairs mapped together (no counterpart in the reference; the definition is in include/awry_hip.h, "map read pairs"):
+    /// `reads1[p]` and `reads2[p]` are the mates of pair p.  Per pair the placements of the best pair -- none or one `Mapping` per
+    /// mate, with the pair MAPQ, `AWRY_MAP_PROPER_PAIR`, `AWRY_MAP_RESCUED` or `AWRY_MAP_MATE_UNMAPPED` in `flags` -- and the insert
+    /// size (0 unless the pair is proper); and per read (interleaved) whether one of its strands was abandoned at `params.max_seeds`.
+    pub fn parallel_map_pairs(
+        &self,
+        reads1: &[&str],
+        reads2: &[&str],
+        min_len: u32,
+        max_hits: u64,
+        chains_per_strand: u64,
+        band: u32,
+        pair: PairParams,
+        params: ChainParams,
+    ) -> Result<(Vec<(Option<Mapping>, Option<Mapping>, u32)>, Vec<bool>), AwryError> {
+        assert_eq!(reads1.len(), reads2.len(), "reads1 and reads2 must have one read per pair each");
+        let inter: Vec<&str> = reads1.iter().zip(reads2.iter()).flat_map(|(a, b)| [*a, *b]).collect();
+        let csr = to_csr(inter.into_par_iter());
+        let n = csr.offsets.len() - 1;
+        let mut map_off: *mut u64 = std::ptr::null_mut();
+        let mut maps: *mut RawMap = std::ptr::null_mut();
+        let mut pos: *mut RawPos = std::ptr::null_mut();
+        let mut cigar_off: *mut u64 = std::ptr::null_mut();
+        let mut cigar: *mut u32 = std::ptr::null_mut();
+        let mut st: *mut u8 = std::ptr::null_mut();
+        let mut ins: *mut u32 = std::ptr::null_mut();
+        check(unsafe {
+            sys::awry_map_pairs_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, min_len, max_hits, params.max_seeds, params.lookback,
+                                      params.max_gap, params.max_skew, params.min_score, chains_per_strand, band, pair.min_insert, pair.max_insert,
+                                      pair.unpaired_penalty, pair.rescue_anchors, pair.rescue_edits, &mut map_off, &mut maps, &mut pos, &mut cigar_off,
+                                      &mut cigar, &mut st, &mut ins)
+        })?;
+        let out = unsafe {
+            let off = std::slice::from_raw_parts(map_off, n + 1);
+            let total = off[n] as usize;
+            let mp: &[RawMap] = if total == 0 { &[] } else { std::slice::from_raw_parts(maps, total) };
+            let ps: &[RawPos] = if total == 0 { &[] } else { std::slice::from_raw_parts(pos, total) };
+            let coff = std::slice::from_raw_parts(cigar_off, total + 1);
+            let runs: &[u32] = if coff[total] == 0 { &[] } else { std::slice::from_raw_parts(cigar, coff[total] as usize) };
+            let status: &[u8] = if n == 0 { &[] } else { std::slice::from_raw_parts(st, n) };
+            let inserts: &[u32] = if n == 0 { &[] } else { std::slice::from_raw_parts(ins, n / 2) };
+            let record = |i: usize| {
+                (off[i] as usize..off[i + 1] as usize).next().map(|j| Mapping {
+                    position: LocalizedSequencePosition::new(ps[j].seq_idx as usize, ps[j].local_pos as usize),
+                    t_begin: mp[j].t_begin,
+                    t_end: mp[j].t_end,
+                    edits: mp[j].edits,
+                    chain_score: mp[j].chain_score,
+                    chain_index: mp[j].chain_index,
+                    strand: mp[j].strand,
+                    mapq: mp[j].mapq,
+                    flags: mp[j].flags,
+                    cigar: runs[coff[j] as usize..coff[j + 1] as usize].to_vec(),
+                })
+            };
+            let per = (0..n / 2).map(|p| (record(2 * p), record(2 * p + 1), inserts[p])).collect::<Vec<_>>();
+            (per, status.iter().map(|&s| s == 8).collect::<Vec<_>>())  // AWRY_Q_SEED_CAP
+        };
+        unsafe {
+            sys::awry_free_buffer(map_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(maps as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(pos as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(cigar_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(cigar as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(st as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(ins as *mut std::os::raw::c_void);
         }
         Ok(out)
     }
