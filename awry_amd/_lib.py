@@ -44,6 +44,14 @@ class Map(C.Structure):  # awry_map_t
                 ("strand", C.c_uint8), ("mapq", C.c_uint8), ("flags", C.c_uint16)]
 
 
+class AlnClip(C.Structure):  # awry_aln_clip_t
+    _fields_ = Aln._fields_ + [("score", C.c_int32), ("clip_left", C.c_uint16), ("clip_right", C.c_uint16)]
+
+
+class MapClip(C.Structure):  # awry_map_clip_t
+    _fields_ = Map._fields_ + [("score", C.c_int32), ("clip_left", C.c_uint16), ("clip_right", C.c_uint16)]
+
+
 class BuildArgs(C.Structure):
     _fields_ = [("input_path", C.c_char_p), ("sa_tmp_path", C.c_char_p), ("sa_ratio", C.c_uint64),
                 ("kmer_len", C.c_uint8), ("alphabet", C.c_uint8), ("max_query_len", C.c_uint64),
@@ -144,6 +152,13 @@ def load_library():
         C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)), C.POINTER(u8p))
     sig("awry_dev_revcomp", i32, vp, i32, vp, vp, u64, vp, vp, vp)
     sig("awry_dev_map_select", i32, vp, i32, vp, vp, vp, vp, u64, u32, u32, vp, vp, vp, vp, vp, vp, vp)
+    sig("awry_align_chains_clip_batch", i32, vp, vp, u64p, u64, u32, u64, u32, u32, u32, u32, u32, u64, u32, u32, u32, u32, u32, C.POINTER(u64p),
+        C.POINTER(C.POINTER(Chain)), C.POINTER(C.POINTER(AlnClip)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)), C.POINTER(u8p))
+    sig("awry_dev_align_chains_clip", i32, vp, i32, vp, vp, vp, vp, vp, u64, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp)
+    sig("awry_dev_align_chains_clip_tally", i32, vp, i32, vp, vp, vp, vp, vp, u64, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp)
+    sig("awry_map_clip_batch", i32, vp, vp, u64p, u64, u32, u64, u32, u32, u32, u32, u32, u64, u64, u32, u32, u32, u32, u32, u32, C.POINTER(u64p),
+        C.POINTER(C.POINTER(MapClip)), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)), C.POINTER(u8p))
+    sig("awry_dev_map_select_clip", i32, vp, i32, vp, vp, vp, vp, u64, u32, u32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp)
     sig("awry_map_pairs_batch", i32, vp, vp, u64p, u64, u32, u64, u32, u32, u32, u32, u32, u64, u32, u64, u64, u32, u32, i32, C.POINTER(u64p),
         C.POINTER(C.POINTER(Map)), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)), C.POINTER(u8p), C.POINTER(C.POINTER(u32)))
     sig("awry_dev_pair_windows", i32, vp, i32, vp, vp, vp, u64, u64, u64, u32, i32, vp, vp, vp, vp)

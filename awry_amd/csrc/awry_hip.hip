@@ -446,7 +446,25 @@ int awry_align_chains_batch(awry_index_t* idx, const uint8_t* qbytes, const uint
     const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
     require_chain_align_args(max_alignments, band);
     require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
-    align_chains_batch(idx, qbytes, qoff, n, min_len, max_hits, P, max_alignments, band, aln_off_out, chains_out, alns_out, cigar_off_out, cigar_out,
+    align_chains_batch(idx, qbytes, qoff, n, min_len, max_hits, P, max_alignments, band, AlignMode{}, aln_off_out, chains_out, alns_out, cigar_off_out,
+                       cigar_out, status_out);
+  });
+}
+
+int awry_align_chains_clip_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits,
+                                 uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score, uint64_t max_alignments,
+                                 uint32_t band, uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus, uint64_t** aln_off_out,
+                                 awry_chain_t** chains_out, awry_aln_clip_t** alns_out, uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out) {
+  return guarded([&] {
+    require(idx && qoff && aln_off_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_smem_args(min_len);
+    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
+    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    require_chain_align_args(max_alignments, band);
+    const AlignMode md = clip_mode(match, mismatch, gap, end_bonus);
+    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
+    align_chains_batch(idx, qbytes, qoff, n, min_len, max_hits, P, max_alignments, band, md, aln_off_out, chains_out, alns_out, cigar_off_out, cigar_out,
                        status_out);
   });
 }
@@ -462,8 +480,26 @@ int awry_map_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qof
     const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
     require_map_args(chains_per_strand, max_report, band);
     require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
-    map_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, (uint32_t)max_report, band, map_off_out, maps_out, pos_out,
-              cigar_off_out, cigar_out, status_out);
+    map_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, (uint32_t)max_report, band, AlignMode{}, MapMode{}, map_off_out,
+              maps_out, pos_out, cigar_off_out, cigar_out, status_out);
+  });
+}
+
+int awry_map_clip_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits, uint32_t max_seeds,
+                        uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score, uint64_t chains_per_strand, uint64_t max_report,
+                        uint32_t band, uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus, uint32_t min_aln_score, uint64_t** map_off_out,
+                        awry_map_clip_t** maps_out, awry_pos_t** pos_out, uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out) {
+  return guarded([&] {
+    require(idx && qoff && map_off_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_smem_args(min_len);
+    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
+    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    require_map_args(chains_per_strand, max_report, band);
+    const AlignMode md = clip_mode(match, mismatch, gap, end_bonus);
+    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
+    map_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, (uint32_t)max_report, band, md, clip_map_mode(md, min_aln_score),
+              map_off_out, maps_out, pos_out, cigar_off_out, cigar_out, status_out);
   });
 }
 
@@ -1019,8 +1055,31 @@ int awry_dev_align_chains_tally(awry_index_t* idx, int slot, const uint8_t* d_qb
     Replica& r = replica(idx, slot);
     require(m == 0 || (d_qbytes && d_qoff && d_chain_query && d_member_off && d_members && (d_cigar_off ? d_cigar != nullptr : d_alns && d_n_ops)),
             "null device pointer");
-    launch_chain_align(r, edit_text(r), d_qbytes, d_qoff, d_chain_query, d_member_off, reinterpret_cast<const Seed*>(d_members), m, (int)band,
-                       CHAIN_ALIGN_MAX_LEN, reinterpret_cast<Aln*>(d_alns), d_n_ops, d_cigar_off, d_cigar, (hipStream_t)stream, (unsigned long long*)d_tally);
+    launch_chain_align(r, edit_text(r), d_qbytes, d_qoff, d_chain_query, d_member_off, reinterpret_cast<const Seed*>(d_members), m, (int)band, AlignMode{},
+                       CHAIN_ALIGN_MAX_LEN, d_alns, d_n_ops, d_cigar_off, d_cigar, (hipStream_t)stream, (unsigned long long*)d_tally);
+  });
+}
+
+int awry_dev_align_chains_clip(awry_index_t* idx, int slot, const uint8_t* d_qbytes, const uint64_t* d_qoff, const uint32_t* d_chain_query,
+                               const uint64_t* d_member_off, const awry_seed_t* d_members, uint64_t m, uint32_t band, uint32_t match, uint32_t mismatch,
+                               uint32_t gap, uint32_t end_bonus, awry_aln_clip_t* d_alns, uint64_t* d_n_ops, const uint64_t* d_cigar_off, uint32_t* d_cigar,
+                               void* stream) {
+  return awry_dev_align_chains_clip_tally(idx, slot, d_qbytes, d_qoff, d_chain_query, d_member_off, d_members, m, band, match, mismatch, gap, end_bonus,
+                                          d_alns, d_n_ops, d_cigar_off, d_cigar, nullptr, stream);
+}
+
+int awry_dev_align_chains_clip_tally(awry_index_t* idx, int slot, const uint8_t* d_qbytes, const uint64_t* d_qoff, const uint32_t* d_chain_query,
+                                     const uint64_t* d_member_off, const awry_seed_t* d_members, uint64_t m, uint32_t band, uint32_t match,
+                                     uint32_t mismatch, uint32_t gap, uint32_t end_bonus, awry_aln_clip_t* d_alns, uint64_t* d_n_ops,
+                                     const uint64_t* d_cigar_off, uint32_t* d_cigar, uint64_t* d_tally, void* stream) {
+  return guarded([&] {
+    require_chain_align_args(1, band);
+    const AlignMode md = clip_mode(match, mismatch, gap, end_bonus);
+    Replica& r = replica(idx, slot);
+    require(m == 0 || (d_qbytes && d_qoff && d_chain_query && d_member_off && d_members && (d_cigar_off ? d_cigar != nullptr : d_alns && d_n_ops)),
+            "null device pointer");
+    launch_chain_align(r, edit_text(r), d_qbytes, d_qoff, d_chain_query, d_member_off, reinterpret_cast<const Seed*>(d_members), m, (int)band, md,
+                       CHAIN_ALIGN_MAX_LEN, d_alns, d_n_ops, d_cigar_off, d_cigar, (hipStream_t)stream, (unsigned long long*)d_tally);
   });
 }
 
@@ -1042,9 +1101,22 @@ int awry_dev_map_select(awry_index_t* idx, int slot, const uint64_t* d_aln_off, 
     require_map_args(chains_per_strand, max_report, 0);
     Replica& r = replica(idx, slot);
     require(n == 0 || (d_aln_off && d_alns && d_chains && (d_map_off ? d_maps != nullptr : d_n_maps != nullptr)), "null device pointer");
-    launch_map_select(r, d_aln_off, reinterpret_cast<const Aln*>(d_alns), reinterpret_cast<const Chain*>(d_chains), d_chain_status, n, chains_per_strand,
-                      max_report, d_n_maps, d_read_status, d_map_off, reinterpret_cast<MapRec*>(d_maps), d_sel, reinterpret_cast<uint64_t*>(d_pos),
-                      (hipStream_t)stream);
+    launch_map_select(r, d_aln_off, d_alns, reinterpret_cast<const Chain*>(d_chains), d_chain_status, n, chains_per_strand, max_report, MapMode{}, d_n_maps,
+                      d_read_status, d_map_off, d_maps, d_sel, reinterpret_cast<uint64_t*>(d_pos), (hipStream_t)stream);
+  });
+}
+
+int awry_dev_map_select_clip(awry_index_t* idx, int slot, const uint64_t* d_aln_off, const awry_aln_clip_t* d_alns, const awry_chain_t* d_chains,
+                             const uint8_t* d_chain_status, uint64_t n, uint32_t chains_per_strand, uint32_t max_report, uint32_t match, uint32_t mismatch,
+                             uint32_t gap, uint32_t end_bonus, uint32_t min_aln_score, uint64_t* d_n_maps, uint8_t* d_read_status, const uint64_t* d_map_off,
+                             awry_map_clip_t* d_maps, uint32_t* d_sel, awry_pos_t* d_pos, void* stream) {
+  return guarded([&] {
+    require_map_args(chains_per_strand, max_report, 0);
+    const MapMode mm = clip_map_mode(clip_mode(match, mismatch, gap, end_bonus), min_aln_score);
+    Replica& r = replica(idx, slot);
+    require(n == 0 || (d_aln_off && d_alns && d_chains && (d_map_off ? d_maps != nullptr : d_n_maps != nullptr)), "null device pointer");
+    launch_map_select(r, d_aln_off, d_alns, reinterpret_cast<const Chain*>(d_chains), d_chain_status, n, chains_per_strand, max_report, mm, d_n_maps,
+                      d_read_status, d_map_off, d_maps, d_sel, reinterpret_cast<uint64_t*>(d_pos), (hipStream_t)stream);
   });
 }
 

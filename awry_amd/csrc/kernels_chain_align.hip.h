@@ -15,6 +15,13 @@
 // Chains are classified by their widest segment (chain_align_classify_kernel): NB <= 9, <= 17, <= 33.  Each class is one
 // instantiation over the class's list of chain indices, so a lane pays for the cells of its class only.  Chains that are not
 // aligned (AWRY_ALN_BAD_CHAIN, AWRY_ALN_SKEW) get their record from the classify kernel and enter no list.
+//
+// CLIP = true is the clipped mode of the same kernels (include/awry_hip.h, "soft-clip read ends"): pieces and gaps as above, the two
+// extensions scored and local.  The row update minimises a signed cost with per-segment weights (match, mismatch, indel): (0, 1, 1)
+// for gaps and end-to-end extensions, (-a, b, g) for clipped extensions, whose cost is minus the header's score H.  A clipped
+// extension has m = 0 whatever avail is (NB = 2 W + 1), avail is cut at the record of the first piece's text start, the rows beyond
+// J + W do not run, and the best cell is the running minimum over all cells (ties: the largest i, then the smallest j).  It ends at
+// (a, j_e), the first minimum of row a, if C_e - E <= C*, else at the best cell; the query letters beyond are one 'S' run.
 #pragma once
 
 namespace awry {
@@ -25,6 +32,24 @@ constexpr int CHAIN_ALIGN_CLASSES = 3;
 AWRY_HD constexpr int chain_align_class_nb(int cls) { return cls == 0 ? 9 : cls == 1 ? 17 : 33; }
 
 struct Aln { uint64_t t_begin, t_end; uint32_t edits, status; };  // == awry_aln_t (checked in chain_align_host.h)
+struct AlnClip { uint64_t t_begin, t_end; uint32_t edits, status; int32_t score; uint16_t clip_left, clip_right; };  // == awry_aln_clip_t
+template <bool CLIP> using AlnOf = std::conditional_t<CLIP, AlnClip, Aln>;
+template <bool CLIP> __device__ __forceinline__ AlnOf<CLIP> aln_unaligned(uint64_t tb, uint64_t te, uint32_t status) {
+  if constexpr (CLIP) return AlnClip{tb, te, 0, status, 0, 0, 0};
+  else return Aln{tb, te, 0, status};
+}
+
+// The mode of a launch: end to end (the default), or clipped with the header's weights a, b, g and end bonus E.
+struct AlignMode { bool clip = false; int match = 0, mismatch = 1, gap = 1, end_bonus = 0; };
+constexpr int CHAIN_CLIP_INF = 1 << 28;  // the clipped mode's +infinity: |cost| <= 64 * 1024 + 8 * 64 stays far below it
+
+// the record of text position t as [lo, hi): awry_get_seq_location's rule, the last record ends at n_text
+__device__ __forceinline__ void record_bounds(const DevIndex& ix, uint64_t t, uint64_t n_text, int64_t& lo, int64_t& hi) {
+  uint64_t rec[2];
+  localise(ix, t < ix.bwt_len ? t : ix.bwt_len - 1, rec);
+  lo = ix.nseq ? (int64_t)ix.seq_starts[rec[0]] : 0;
+  hi = rec[0] + 1 < ix.nseq ? (int64_t)ix.seq_starts[rec[0] + 1] : (int64_t)n_text;
+}
 
 // the direction words of one row: 2 bits per band cell, cell b at bits [2b, 2b + 2) of the row's bit string
 template <int NBMAX>
@@ -80,10 +105,12 @@ __device__ __forceinline__ bool chain_align_members_ok(const Seed* __restrict__ 
 // One chain per lane, grid-stride: validate the members, walk the pieces for the span and the widest skew, write the record of a
 // chain that is not aligned (alns / n_ops non-null: the count pass) and append the others to their class's list:
 // lists[cls * m + k], k < list_n[cls] (list_n zeroed by the launcher).  The order inside a list is the order of the atomics;
-// every output is indexed by the chain, so it changes nothing.
+// every output is indexed by the chain, so it changes nothing.  CLIP: the class and AWRY_ALN_SKEW come from the gaps' skew only (an
+// extension needs 2 W + 1 cells), and the records are awry_aln_clip_t.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void chain_align_classify_kernel(uint64_t n_text, const uint64_t* __restrict__ off, const uint32_t* __restrict__ chain_query,
                                                                    const uint64_t* __restrict__ member_off, const Seed* __restrict__ members, uint64_t m, int W,
-                                                                   uint32_t max_rows, Aln* __restrict__ alns, uint64_t* __restrict__ n_ops, uint32_t* __restrict__ lists,
+                                                                   uint32_t max_rows, AlnOf<CLIP>* __restrict__ alns, uint64_t* __restrict__ n_ops, uint32_t* __restrict__ lists,
                                                                    uint32_t* __restrict__ list_n) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < m; c += stride) {
@@ -91,14 +118,14 @@ __global__ __launch_bounds__(256) void chain_align_classify_kernel(uint64_t n_te
     const uint64_t ob = off[q], oe = off[q + 1];
     const uint64_t L = oe > ob ? oe - ob : 0;
     const uint64_t mlo = member_off[c], mhi = member_off[c + 1];
-    Aln r{0, 0, 0, ALN_BAD_CHAIN};
+    AlnOf<CLIP> r = aln_unaligned<CLIP>(0, 0, ALN_BAD_CHAIN);
     int64_t skew = 0;
     if (chain_align_members_ok(members, mlo, mhi, L, n_text, max_rows)) {
       ChainPieces p(members, mlo, mhi);
       p.next();
       r.t_begin = (uint64_t)p.tb;
       const int64_t left = p.tb - p.qb;  // avail - a of the left extension
-      skew = left < 0 ? -left : 0;
+      skew = !CLIP && left < 0 ? -left : 0;
       int64_t pqe = p.qb + p.len, pte = p.tb + p.len;
       while (p.next()) {
         const int64_t mm = (p.tb - pte) - (p.qb - pqe);
@@ -108,7 +135,7 @@ __global__ __launch_bounds__(256) void chain_align_classify_kernel(uint64_t n_te
       }
       r.t_end = (uint64_t)pte;
       const int64_t right = ((int64_t)n_text - pte) - ((int64_t)L - pqe);
-      skew = skew > -right ? skew : -right;
+      if (!CLIP) skew = skew > -right ? skew : -right;
       r.status = skew > CHAIN_ALIGN_MAX_SKEW ? ALN_SKEW : ALN_OK;
     }
     if (r.status != ALN_OK) {
@@ -133,16 +160,21 @@ __global__ __launch_bounds__(256) void chain_align_classify_kernel(uint64_t n_te
 // over the rows then emits them.  Runs are merged over the whole script as they are emitted.
 // FILL = false: the count pass -- alns[c] and n_ops[c]; FILL = true: the runs at cigar[cigar_off[c] .. cigar_off[c + 1]).
 // tally (nullable): [0] += chains aligned, [1] += table cells inside band and table.
-template <int A, int NBMAX, bool FILL>
+// CLIP = true: the clipped mode (ix gives the record bounds, md the weights); the cells are signed, the left extension emits its
+// 'S' run before its traceback and the right extension after its forward walk, and score and edits are counted as the operations
+// are emitted, so that they are the script's by construction.  CLIP = false reads neither ix nor md: the weights are constants.
+template <int A, int NBMAX, bool FILL, bool CLIP>
 __global__ __launch_bounds__(256) void chain_align_kernel(const uint8_t* __restrict__ text8, uint64_t n_text, const uint8_t* __restrict__ ascii,
                                                           const uint64_t* __restrict__ off, const uint32_t* __restrict__ chain_query,
                                                           const uint64_t* __restrict__ member_off, const Seed* __restrict__ members,
                                                           const uint32_t* __restrict__ list, const uint32_t* __restrict__ list_n, int W,
-                                                          typename ChainAlignTrace<NBMAX>::word* trace, Aln* __restrict__ alns, uint64_t* __restrict__ n_ops,
-                                                          const uint64_t* __restrict__ cigar_off, uint32_t* __restrict__ cigar,
-                                                          unsigned long long* __restrict__ tally) {
+                                                          typename ChainAlignTrace<NBMAX>::word* trace, AlnOf<CLIP>* __restrict__ alns,
+                                                          uint64_t* __restrict__ n_ops, const uint64_t* __restrict__ cigar_off, uint32_t* __restrict__ cigar,
+                                                          unsigned long long* __restrict__ tally, DevIndex ix, AlignMode md) {
   using TR = ChainAlignTrace<NBMAX>;
   using TW = typename TR::word;
+  using cell = std::conditional_t<CLIP, int32_t, uint32_t>;  // a table cell: a cost, signed where a match earns
+  constexpr cell CINF = CLIP ? (cell)CHAIN_CLIP_INF : (cell)ALIGN_INF;
   constexpr int NW = TR::NW, BITS = TR::BITS;
   constexpr uint32_t S = edit_symbols(A);
   __shared__ uint8_t lut[256];
@@ -174,16 +206,24 @@ __global__ __launch_bounds__(256) void chain_align_kernel(const uint8_t* __restr
         nruns++;
       }
     };
+    int32_t score = 0;    // CLIP: a #'=' - b #'X' - g (#'I' + #'D') of what has been emitted
+    uint32_t edits = 0;   // CLIP: #'X' + #'I' + #'D' of what has been emitted; else the pieces' 'X's and the segments' costs
     auto emit = [&](uint32_t op, uint32_t cnt) {
       if (!cnt) return;
-      if (op != run_op) { flush(); run_op = op; run_len = 0; }
+      if (op != run_op || (CLIP && op == 4u)) { flush(); run_op = op; run_len = 0; }  // (an 'S' run merges with nothing)
       run_len += cnt;
+      if constexpr (CLIP) {
+        if (op == 7u) score += md.match * (int32_t)cnt;
+        else if (op != 4u) { edits += cnt; score -= (op == 8u ? md.mismatch : md.gap) * (int32_t)cnt; }
+      }
     };
     ChainPieces p(members, member_off[c], member_off[c + 1]);
     p.next();
     const int64_t t_first = p.tb;
     int64_t t_begin = p.tb, t_end = p.tb, pqe = 0, pte = 0;
-    uint32_t edits = 0;
+    int64_t rec_lo = 0, rec_hi = (int64_t)n_text;  // what an extension may read: the text, CLIP: the first piece's record
+    if constexpr (CLIP) record_bounds(ix, (uint64_t)p.tb, n_text, rec_lo, rec_hi);
+    uint32_t clip_left = 0, clip_right = 0;
     bool sane = true;
     for (int kind = 0; sane;) {  // 0: the left extension and the first piece; 1: a gap and its piece; 2: the right extension
       // ---- the segment: row i reads query letter xq + xs * i, column j reads T[ty + ts * (j - 1)] ----
@@ -192,8 +232,8 @@ __global__ __launch_bounds__(256) void chain_align_kernel(const uint8_t* __restr
       int xs;
       if (kind == 0) {
         a = (int)p.qb;
-        const int64_t avail = p.tb;
-        msk = avail < a ? (int)(avail - a) : 0;
+        const int64_t avail = p.tb - rec_lo;
+        msk = !CLIP && avail < a ? (int)(avail - a) : 0;
         J = avail < a + W ? (int)avail : a + W;
         end_j = -1;
         xq = p.qb; xs = -1; ty = p.tb - 1;
@@ -205,8 +245,8 @@ __global__ __launch_bounds__(256) void chain_align_kernel(const uint8_t* __restr
         xq = pqe - 1; xs = 1; ty = pte;
       } else {
         a = L - (int)pqe;
-        const int64_t avail = (int64_t)n_text - pte;
-        msk = avail < a ? (int)(avail - a) : 0;
+        const int64_t avail = rec_hi > pte ? rec_hi - pte : 0;
+        msk = !CLIP && avail < a ? (int)(avail - a) : 0;
         J = avail < a + W ? (int)avail : a + W;
         end_j = -1;
         xq = pqe - 1; xs = 1; ty = pte;
@@ -215,15 +255,21 @@ __global__ __launch_bounds__(256) void chain_align_kernel(const uint8_t* __restr
       if (a > 0 || kind == 1) {
         const int lo = (msk < 0 ? msk : 0) - W, hi = (msk > 0 ? msk : 0) + W, NB = hi - lo + 1;
         if (NB > NBMAX) { sane = false; break; }  // (never: the class holds the chain's widest segment)
-        uint32_t cc[NBMAX], tw[NBMAX];  // cc[b] = C[i][i + b + lo]; tw[b] = y of column i + b + lo, the symbol cell b of row i compares
+        const bool local = CLIP && kind != 1;  // a clipped extension: weights (-a, b, g), the best cell tracked, rows up to J + W
+        const cell wm = local ? (cell)-md.match : (cell)0, wx = local ? (cell)md.mismatch : (cell)1, wg = local ? (cell)md.gap : (cell)1;
+        const int rows = local && J + W < a ? J + W : a;
+        cell best = 0;                 // the running minimum over all cells: (0, 0) to begin with
+        int best_i = 0, best_b = -lo;
+        cell cc[NBMAX];      // cc[b] = C[i][i + b + lo]
+        uint32_t tw[NBMAX];  // tw[b] = y of column i + b + lo, the symbol cell b of row i compares
 #pragma unroll
         for (int b = 0; b < NBMAX; b++) {
           const int j = b + lo;
-          cc[b] = b < NB && j >= 0 && j <= J ? (uint32_t)j : ALIGN_INF;  // row 0
-          tw[b] = j >= 0 ? symbol(ty + (int64_t)ts * j) : 0u;             // row 1: column j + 1
+          cc[b] = b < NB && j >= 0 && j <= J ? (cell)j * wg : CINF;  // row 0
+          tw[b] = j >= 0 ? symbol(ty + (int64_t)ts * j) : 0u;        // row 1: column j + 1
         }
         if (tally) t_cells += (unsigned long long)((hi < J ? hi : J) + 1);
-        for (int i = 1; i <= a; i++) {
+        for (int i = 1; i <= rows; i++) {
           if (i > 1) {
 #pragma unroll
             for (int b = 0; b + 1 < NBMAX; b++) tw[b] = tw[b + 1];
@@ -235,17 +281,21 @@ __global__ __launch_bounds__(256) void chain_align_kernel(const uint8_t* __restr
           TW dirs[NW];
 #pragma unroll
           for (int w = 0; w < NW; w++) dirs[w] = 0;
-          uint32_t left = ALIGN_INF;
+          cell left = CINF;
 #pragma unroll
           for (int b = 0; b < NBMAX; b++) {
             const int j = i + b + lo;
             const uint32_t neq = tw[b] == qs && tw[b] - 1u < S ? 0u : 1u;
-            const uint32_t dg = cc[b] + neq, up = (b + 1 < NBMAX ? cc[b + 1] : ALIGN_INF) + 1u, lf = left + 1u;
-            uint32_t v = dg < up ? dg : up;
+            const cell dg = cc[b] + (neq ? wx : wm), up = (b + 1 < NBMAX ? cc[b + 1] : CINF) + wg, lf = left + wg;
+            cell v = dg < up ? dg : up;
             v = v < lf ? v : lf;
             uint32_t dir = dg == v ? neq : (up == v ? 2u : 3u);
-            if (j == 0) { v = (uint32_t)i; dir = 2u; }  // column 0: only 'I' leads back
-            if (b >= NB || j < 0 || j > J) v = ALIGN_INF;
+            if (j == 0) { v = (cell)i * wg; dir = 2u; }  // column 0: only 'I' leads back
+            const bool outside = b >= NB || j < 0 || j > J;
+            if (outside) v = CINF;
+            if constexpr (CLIP) {  // ties: the largest i, then the smallest j -- rows and cells come in that order
+              if (local && !outside && (v < best || (v == best && best_i != i))) { best = v; best_i = i; best_b = b; }
+            }
             cc[b] = v;
             left = v;
             dirs[(2 * b) / BITS] |= (TW)dir << ((2 * b) % BITS);
@@ -258,7 +308,7 @@ __global__ __launch_bounds__(256) void chain_align_kernel(const uint8_t* __restr
           }
         }
         // ---- where it ends ----
-        uint32_t cost = ALIGN_INF;
+        cell cost = CINF;
         int b = 0;
         if (end_j < 0) {
 #pragma unroll
@@ -270,10 +320,19 @@ __global__ __launch_bounds__(256) void chain_align_kernel(const uint8_t* __restr
           for (int x = 0; x < NBMAX; x++)
             if (x == b) cost = cc[x];
         }
-        if (cost >= ALIGN_INF) { sane = false; break; }  // (never: every cell inside band and table is reachable)
-        edits += cost;
-        int i = a, j = a + b + lo;
-        if (kind == 0) t_begin = p.tb - j;
+        int i = a;
+        if constexpr (CLIP) {
+          // cc is row `rows`: row a iff it has a cell.  It ends there unless the best cell beats it by more than the end bonus.
+          if (local && (rows < a || cost - (cell)md.end_bonus > best)) { cost = best; i = best_i; b = best_b; }
+          if (cost >= CINF / 2) { sane = false; break; }  // (never)
+          if (kind == 0) clip_left = (uint32_t)(a - i);
+        } else {
+          if (cost >= CINF) { sane = false; break; }  // (never: every cell inside band and table is reachable)
+          edits += cost;
+        }
+        const int i_end = i;
+        int j = i + b + lo;
+        if (kind == 0) { t_begin = p.tb - j; emit(4u, clip_left); }
         if (kind == 2) t_end = pte + j;
         // ---- the traceback ----
         uint32_t after = 0;  // 'D's met since the last row was left (forward kinds)
@@ -306,11 +365,12 @@ __global__ __launch_bounds__(256) void chain_align_kernel(const uint8_t* __restr
           emit(2u, (uint32_t)j);
         } else {
           emit(2u, (uint32_t)j);
-          for (int r = 1; r <= a; r++) {
+          for (int r = 1; r <= i_end; r++) {
             const TW w0 = trace[(uint64_t)(xq + r) * NW * stride + lane];
             emit(align_bam_op((uint32_t)w0 & 3u), 1u);
             emit(2u, (uint32_t)(w0 >> 2));
           }
+          if (CLIP && kind == 2) { clip_right = (uint32_t)(a - i_end); emit(4u, clip_right); }
         }
       }
       if (kind == 2) break;
@@ -318,7 +378,7 @@ __global__ __launch_bounds__(256) void chain_align_kernel(const uint8_t* __restr
       for (int64_t x = 0; x < p.len; x++) {
         const uint32_t qs = lut[qbytes[q0 + (uint64_t)(p.qb + x)]], tsym = symbol(p.tb + x);
         const uint32_t neq = tsym == qs && tsym - 1u < S ? 0u : 1u;
-        edits += neq;
+        if (!CLIP) edits += neq;
         emit(neq ? 8u : 7u, 1u);
       }
       pqe = p.qb + p.len;
@@ -328,11 +388,12 @@ __global__ __launch_bounds__(256) void chain_align_kernel(const uint8_t* __restr
     }
     flush();
     if (!sane) {  // (never) the record of a chain that is not aligned, and no runs
-      if (!FILL) { alns[c] = Aln{(uint64_t)t_first, (uint64_t)pte, 0, ALN_BAD_CHAIN}; n_ops[c] = 0; }
+      if (!FILL) { alns[c] = aln_unaligned<CLIP>((uint64_t)t_first, (uint64_t)pte, ALN_BAD_CHAIN); n_ops[c] = 0; }
       continue;
     }
     if (!FILL) {
-      alns[c] = Aln{(uint64_t)t_begin, (uint64_t)t_end, edits, ALN_OK};
+      if constexpr (CLIP) alns[c] = AlnClip{(uint64_t)t_begin, (uint64_t)t_end, edits, ALN_OK, score, (uint16_t)clip_left, (uint16_t)clip_right};
+      else alns[c] = Aln{(uint64_t)t_begin, (uint64_t)t_end, edits, ALN_OK};
       n_ops[c] = nruns;
     }
     t_chains++;

@@ -583,9 +583,10 @@ void launch_chain(Replica& r, const uint64_t* d_seed_off, const Seed* d_seeds, u
 // class is cut so that they stay within CHAIN_ALIGN_TRACE_BYTES (at 1024 rows: 512, 256 and 128 blocks of 256 lanes; at the 101 rows
 // of a short-read batch the whole grid), and the scratch grows to what the launch needs, not to the bound.
 constexpr size_t CHAIN_ALIGN_TRACE_BYTES = 512u << 20;
+// md: end to end (d_alns: Aln records) or clipped (AlnClip records): the same kernels, instantiated per mode.
 void launch_chain_align(Replica& r, const uint8_t* text8, const uint8_t* d_q, const uint64_t* d_off, const uint32_t* d_chain_query,
-                        const uint64_t* d_member_off, const Seed* d_members, uint64_t m, int band, uint32_t max_rows, Aln* d_alns, uint64_t* d_n_ops,
-                        const uint64_t* d_cigar_off, uint32_t* d_cigar, hipStream_t s, unsigned long long* d_tally = nullptr) {
+                        const uint64_t* d_member_off, const Seed* d_members, uint64_t m, int band, const AlignMode& md, uint32_t max_rows, void* d_alns,
+                        uint64_t* d_n_ops, const uint64_t* d_cigar_off, uint32_t* d_cigar, hipStream_t s, unsigned long long* d_tally = nullptr) {
   if (m == 0) return;
   require(m < (1ull << 32), "more than 2^32 - 1 chains in one alignment launch");
   require(max_rows >= 1 && max_rows <= (uint32_t)CHAIN_ALIGN_MAX_LEN && band >= 0 && band <= CHAIN_ALIGN_MAX_BAND,
@@ -611,24 +612,28 @@ void launch_chain_align(Replica& r, const uint8_t* text8, const uint8_t* d_q, co
   uint32_t* list_n = lists + (size_t)CHAIN_ALIGN_CLASSES * m;
   HIP_CHECK(hipMemsetAsync(list_n, 0, CHAIN_ALIGN_CLASSES * sizeof(uint32_t), s));
   const bool fill = d_cigar_off != nullptr;
-  hipLaunchKernelGGL(chain_align_classify_kernel, dim3(grid_for(r, m, 256)), dim3(256), 0, s, r.dev.bwt_len - 1, d_off, d_chain_query, d_member_off, d_members,
-                     m, band, max_rows, fill ? nullptr : d_alns, fill ? nullptr : d_n_ops, lists, list_n);
-  with_alphabet(r.dev.alphabet, [&](auto A) {
-    constexpr int AL = decltype(A)::value;
-    with_flags(fill, [&](auto F) {
-      auto align = [&](auto CC) {
-        constexpr int CLS = decltype(CC)::value, NBMAX = chain_align_class_nb(CLS);
-        using TR = ChainAlignTrace<NBMAX>;
-        using TW = typename TR::word;
-        static_assert(TR::NW * sizeof(TW) == ((size_t)4 << CLS), "the trace bytes per row of the class");
-        const uint64_t blocks = blocks_for(TR::NW * sizeof(TW));
-        hipLaunchKernelGGL((chain_align_kernel<AL, NBMAX, decltype(F)::value>), dim3((unsigned)blocks), dim3(256), 0, s, text8, r.dev.bwt_len - 1, d_q, d_off,
-                           d_chain_query, d_member_off, d_members, lists + (size_t)CLS * m, list_n + CLS, band, reinterpret_cast<TW*>(sc->align_trace.p), d_alns,
-                           d_n_ops, d_cigar_off, d_cigar, d_tally);
-      };
-      if (2 * band + 1 <= chain_align_class_nb(0)) align(std::integral_constant<int, 0>{});
-      if (2 * band + 1 <= chain_align_class_nb(1)) align(std::integral_constant<int, 1>{});
-      align(std::integral_constant<int, 2>{});
+  with_flags(md.clip, [&](auto M) {
+    constexpr bool CLIP = decltype(M)::value;
+    AlnOf<CLIP>* alns = static_cast<AlnOf<CLIP>*>(d_alns);
+    hipLaunchKernelGGL(chain_align_classify_kernel<CLIP>, dim3(grid_for(r, m, 256)), dim3(256), 0, s, r.dev.bwt_len - 1, d_off, d_chain_query, d_member_off,
+                       d_members, m, band, max_rows, fill ? nullptr : alns, fill ? nullptr : d_n_ops, lists, list_n);
+    with_alphabet(r.dev.alphabet, [&](auto A) {
+      constexpr int AL = decltype(A)::value;
+      with_flags(fill, [&](auto F) {
+        auto align = [&](auto CC) {
+          constexpr int CLS = decltype(CC)::value, NBMAX = chain_align_class_nb(CLS);
+          using TR = ChainAlignTrace<NBMAX>;
+          using TW = typename TR::word;
+          static_assert(TR::NW * sizeof(TW) == ((size_t)4 << CLS), "the trace bytes per row of the class");
+          const uint64_t blocks = blocks_for(TR::NW * sizeof(TW));
+          hipLaunchKernelGGL((chain_align_kernel<AL, NBMAX, decltype(F)::value, CLIP>), dim3((unsigned)blocks), dim3(256), 0, s, text8, r.dev.bwt_len - 1, d_q,
+                             d_off, d_chain_query, d_member_off, d_members, lists + (size_t)CLS * m, list_n + CLS, band, reinterpret_cast<TW*>(sc->align_trace.p),
+                             alns, d_n_ops, d_cigar_off, d_cigar, d_tally, r.dev, md);
+        };
+        if (2 * band + 1 <= chain_align_class_nb(0)) align(std::integral_constant<int, 0>{});
+        if (2 * band + 1 <= chain_align_class_nb(1)) align(std::integral_constant<int, 1>{});
+        align(std::integral_constant<int, 2>{});
+      });
     });
   });
   HIP_CHECK(hipGetLastError());
@@ -644,13 +649,16 @@ void launch_strand_expand(Replica& r, const uint8_t* d_q, const uint64_t* d_off,
 
 // Rank, redundancy, report and MAPQ over the alignment records of a doubled batch of n reads (kernels_map.hip.h).  d_map_off ==
 // nullptr: the count pass (d_n_maps, d_read_status nullable); else the fill pass (d_maps; d_sel, d_pos nullable).
-void launch_map_select(Replica& r, const uint64_t* d_aln_off, const Aln* d_alns, const Chain* d_chains, const uint8_t* d_chain_status, uint64_t n,
-                       uint32_t chains_per_strand, uint32_t max_report, uint64_t* d_n_maps, uint8_t* d_read_status, const uint64_t* d_map_off, MapRec* d_maps,
-                       uint32_t* d_sel, uint64_t* d_pos, hipStream_t s) {
+// md: end to end (Aln in, MapRec out) or clipped (AlnClip in, MapClipRec out): the same kernel, instantiated per mode.
+void launch_map_select(Replica& r, const uint64_t* d_aln_off, const void* d_alns, const Chain* d_chains, const uint8_t* d_chain_status, uint64_t n,
+                       uint32_t chains_per_strand, uint32_t max_report, const MapMode& md, uint64_t* d_n_maps, uint8_t* d_read_status,
+                       const uint64_t* d_map_off, void* d_maps, uint32_t* d_sel, uint64_t* d_pos, hipStream_t s) {
   if (n == 0) return;
-  with_flags(d_map_off != nullptr, [&](auto F) {
-    hipLaunchKernelGGL(map_select_kernel<F()>, dim3(grid_for(r, n, 256)), dim3(256), 0, s, r.dev, d_aln_off, d_alns, d_chains, d_chain_status, n,
-                       chains_per_strand, max_report, d_n_maps, d_read_status, d_map_off, d_maps, d_sel, d_pos);
+  with_flags(d_map_off != nullptr, md.clip, [&](auto F, auto M) {
+    constexpr bool CLIP = decltype(M)::value;
+    hipLaunchKernelGGL((map_select_kernel<F(), CLIP>), dim3(grid_for(r, n, 256)), dim3(256), 0, s, r.dev, d_aln_off, static_cast<const AlnOf<CLIP>*>(d_alns),
+                       d_chains, d_chain_status, n, chains_per_strand, max_report, d_n_maps, d_read_status, d_map_off, static_cast<MapRecOf<CLIP>*>(d_maps),
+                       d_sel, d_pos, md);
   });
   HIP_CHECK(hipGetLastError());
 }

@@ -60,14 +60,14 @@ void pair_chunk(Replica& r, const uint8_t* text8, const ChainOnDevice& v, uint32
   if (total) {
     const uint64_t sub = std::min(chain_align_sub_batch(), total);
     for (uint64_t at = 0; at < total; at += sub)
-      launch_chain_align(r, text8, v.cb.q.p, v.cb.off.p, S.query.p + at, S.moff.p + at, S.members.p, std::min(sub, total - at), band, (uint32_t)Lmax,
-                         alns.p + at, nops.p + at, nullptr, nullptr, s);
+      launch_chain_align(r, text8, v.cb.q.p, v.cb.off.p, S.query.p + at, S.moff.p + at, S.members.p, std::min(sub, total - at), band, AlignMode{},
+                         (uint32_t)Lmax, alns.p + at, nops.p + at, nullptr, nullptr, s);
     S.release_scratch();
   }
   // the kept lists: every read's candidates in rank order, and per candidate the index of its alignment
   DevBuf<uint64_t> nkept(n), koff(n + 1);
   DevBuf<uint8_t> rstatus(n);
-  launch_map_select(r, S.aoff.p, alns.p, S.chains.p, v.status, n, A, 2 * A, nkept.p, rstatus.p, nullptr, nullptr, nullptr, nullptr, s);
+  launch_map_select(r, S.aoff.p, alns.p, S.chains.p, v.status, n, A, 2 * A, MapMode{}, nkept.p, rstatus.p, nullptr, nullptr, nullptr, nullptr, s);
   launch_scan(r, nkept.p, n, koff.p, S.scratch.p, s);
   uint64_t ncand = 0;
   const size_t at_q = out.n_maps.size(), at_m = out.maps.size(), at_p = out.insert.size();
@@ -81,7 +81,7 @@ void pair_chunk(Replica& r, const uint8_t* text8, const ChainOnDevice& v, uint32
   if (!ncand) return;  // (n_maps stays zero)
   DevBuf<MapRec> cands(ncand);
   DevBuf<uint32_t> cand_aln(ncand);
-  launch_map_select(r, S.aoff.p, alns.p, S.chains.p, v.status, n, A, 2 * A, nullptr, nullptr, koff.p, cands.p, cand_aln.p, nullptr, s);
+  launch_map_select(r, S.aoff.p, alns.p, S.chains.p, v.status, n, A, 2 * A, MapMode{}, nullptr, nullptr, koff.p, cands.p, cand_aln.p, nullptr, s);
   // mate rescue: windows, cut for the scan; the scan's count pass, scan, fill pass; the best hit of each window; its alignment
   const uint64_t slots = n * pp.rescue_anchors;
   DevBuf<MapRec> resc;
@@ -163,7 +163,7 @@ void pair_chunk(Replica& r, const uint8_t* text8, const ChainOnDevice& v, uint32
   if (nwin) {
     DevBuf<uint32_t> d_win(nwin);
     HIP_CHECK(hipMemcpyAsync(d_win.p, h_win.data(), nwin * 4, hipMemcpyHostToDevice, s));
-    fill_reported_cigars(r, text8, v, S, nops.p, d_win.p, nwin, band, (uint32_t)Lmax, c_nops.data(), c_cigar);
+    fill_reported_cigars(r, text8, v, S, nops.p, d_win.p, nwin, band, AlignMode{}, (uint32_t)Lmax, c_nops.data(), c_cigar);
   }
   if (any_rescued) {
     require(resc.p != nullptr, "internal: a rescued record without a rescue pass");

@@ -36,7 +36,8 @@ ALN_OK, ALN_SKEW, ALN_BAD_CHAIN = 0, 1, 2  # AWRY_ALN_OK, AWRY_ALN_SKEW, AWRY_AL
 MAP_MAX_CHAINS, MAP_SECONDARY = 8, 1  # AWRY_MAP_MAX_CHAINS, AWRY_MAP_SECONDARY
 MAP_PROPER_PAIR, MAP_RESCUED, MAP_MATE_UNMAPPED = 2, 4, 8  # AWRY_MAP_PROPER_PAIR, AWRY_MAP_RESCUED, AWRY_MAP_MATE_UNMAPPED
 PAIR_MAX_INSERT, PAIR_MAX_ANCHORS, PAIR_NO_CHAIN = 1 << 20, 4, 0xFFFFFFFF  # AWRY_PAIR_MAX_INSERT, AWRY_PAIR_MAX_ANCHORS, AWRY_PAIR_NO_CHAIN
-CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}  # the BAM op codes the alignment pass produces
+CLIP_MAX_MATCH, CLIP_MAX_PENALTY, CLIP_MAX_END_BONUS = 16, 64, 1024  # AWRY_CLIP_MAX_MATCH, AWRY_CLIP_MAX_PENALTY, AWRY_CLIP_MAX_END_BONUS
+CIGAR_OPS = {1: "I", 2: "D", 4: "S", 7: "=", 8: "X"}  # the BAM op codes the alignment passes produce ('S': the clipped mode)
 
 
 def cigar_string(ops) -> str:
@@ -113,6 +114,9 @@ CHAIN_DTYPE = np.dtype([("score", np.uint32), ("n_seeds", np.uint32), ("q_begin"
 ALN_DTYPE = np.dtype([("t_begin", np.uint64), ("t_end", np.uint64), ("edits", np.uint32), ("status", np.uint32)])  # awry_aln_t
 MAP_DTYPE = np.dtype([("t_begin", np.uint64), ("t_end", np.uint64), ("edits", np.uint32), ("chain_score", np.uint32), ("chain_index", np.uint32),
                       ("strand", np.uint8), ("mapq", np.uint8), ("flags", np.uint16)])  # awry_map_t
+_CLIP_FIELDS = [("score", np.int32), ("clip_left", np.uint16), ("clip_right", np.uint16)]
+ALN_CLIP_DTYPE = np.dtype(ALN_DTYPE.descr + _CLIP_FIELDS)  # awry_aln_clip_t, 32 bytes
+MAP_CLIP_DTYPE = np.dtype(MAP_DTYPE.descr + _CLIP_FIELDS)  # awry_map_clip_t, 40 bytes
 
 
 class _Owned:
@@ -738,18 +742,24 @@ class FmIndex:
         reports them, each aligned base by base (include/awry_hip.h states the definition): alignment c covers
         T[alns[c].t_begin .. alns[c].t_end) with alns[c].edits edits by the runs cigar[cigar_off[c] .. cigar_off[c+1]), each
         len << 4 | BAM op; alns[c].status is ALN_OK, ALN_SKEW or ALN_BAD_CHAIN; want_cigar=False leaves cigar_off and cigar empty"""
+        return self._align_chains_csr(None, qbytes, qoff, min_len, max_hits, max_alignments, band, max_seeds, lookback, max_gap, max_skew, min_score,
+                                      want_cigar)
+
+    def _align_chains_csr(self, clip, qbytes, qoff, min_len, max_hits, max_alignments, band, max_seeds, lookback, max_gap, max_skew, min_score, want_cigar):
+        """awry_align_chains_batch (clip None), or awry_align_chains_clip_batch with clip = (match, mismatch, gap, end_bonus)"""
         qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
         qo = np.ascontiguousarray(qoff, dtype=np.uint64)
         n = len(qo) - 1
-        off, ch, al, coff, cg, st = _u64p(), C.POINTER(_lib.Chain)(), C.POINTER(_lib.Aln)(), _u64p(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
-        _check(self._L.awry_align_chains_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(max_hits), int(max_seeds),
-                                               int(lookback), int(max_gap), int(max_skew), int(min_score), int(max_alignments), int(band),
-                                               C.byref(off), C.byref(ch), C.byref(al), C.byref(coff) if want_cigar else None,
-                                               C.byref(cg) if want_cigar else None, C.byref(st)))
+        fn, rec, dt = ((self._L.awry_align_chains_batch, _lib.Aln, ALN_DTYPE) if clip is None else
+                       (self._L.awry_align_chains_clip_batch, _lib.AlnClip, ALN_CLIP_DTYPE))
+        off, ch, al, coff, cg, st = _u64p(), C.POINTER(_lib.Chain)(), C.POINTER(rec)(), _u64p(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+        _check(fn(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(max_hits), int(max_seeds), int(lookback), int(max_gap),
+                  int(max_skew), int(min_score), int(max_alignments), int(band), *(() if clip is None else [int(x) for x in clip]), C.byref(off),
+                  C.byref(ch), C.byref(al), C.byref(coff) if want_cigar else None, C.byref(cg) if want_cigar else None, C.byref(st)))
         offs = _adopt(self._L, off, n + 1, np.uint64)
         tot = int(offs[-1])
         chains = _adopt(self._L, ch, 32 * tot, np.uint8).view(CHAIN_DTYPE)
-        alns = _adopt(self._L, al, 24 * tot, np.uint8).view(ALN_DTYPE)
+        alns = _adopt(self._L, al, dt.itemsize * tot, np.uint8).view(dt)
         status = _adopt(self._L, st, n, np.uint8)
         if not want_cigar:
             return offs, chains, alns, np.zeros(0, np.uint64), np.zeros(0, np.uint32), status
@@ -768,6 +778,26 @@ class FmIndex:
         """alignments of one query's chains"""
         return self.parallel_align_chains([query], min_len, max_hits, max_alignments, band, **chain_params)[0]
 
+    def parallel_align_chains_clip_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 12, max_hits: int = 50, max_alignments: int = 1,
+                                       band: int = 4, match: int = 1, mismatch: int = 4, gap: int = 6, end_bonus: int = 5, max_seeds: int = 1024,
+                                       lookback: int = 32, max_gap: int = 1000, max_skew: int = 100, min_score: int = 20, want_cigar: bool = True):
+        """parallel_align_chains_csr in the clipped mode (include/awry_hip.h, "soft-clip read ends"): the two end extensions are scored
+        (match, mismatch, gap) and local, and may stop early unless the whole extension scores within end_bonus of the best cell; alns
+        is ALN_CLIP_DTYPE -- t_begin / t_end span the aligned part, score, clip_left / clip_right -- and the runs may begin and end with
+        an 'S' run (BAM op 4); an extension never reaches into another record"""
+        return self._align_chains_csr((match, mismatch, gap, end_bonus), qbytes, qoff, min_len, max_hits, max_alignments, band, max_seeds, lookback,
+                                      max_gap, max_skew, min_score, want_cigar)
+
+    def parallel_align_chains_clip(self, queries: Iterable, min_len: int = 12, max_hits: int = 50, max_alignments: int = 1, band: int = 4,
+                                   match: int = 1, mismatch: int = 4, gap: int = 6, end_bonus: int = 5, **chain_params):
+        """-> per query, [(chain score, t_begin, t_end, edits, "70=31S", status, score, clip_left, clip_right)] of its first max_alignments
+        chains in the clipped mode; chain_params: max_seeds, lookback, max_gap, max_skew, min_score"""
+        off, ch, al, coff, cg, _ = self.parallel_align_chains_clip_csr(*pack_queries(queries), min_len, max_hits, max_alignments, band, match, mismatch,
+                                                                       gap, end_bonus, **chain_params)
+        return [[(int(ch[c]["score"]), int(al[c]["t_begin"]), int(al[c]["t_end"]), int(al[c]["edits"]), cigar_string(cg[coff[c]:coff[c + 1]]),
+                  int(al[c]["status"]), int(al[c]["score"]), int(al[c]["clip_left"]), int(al[c]["clip_right"]))
+                 for c in range(int(off[i]), int(off[i + 1]))] for i in range(len(off) - 1)]
+
     def dev_align_chains(self, d_qbytes, d_qoff, d_chain_query, d_member_off, d_members, m, band, d_alns, d_n_ops, d_cigar_off=None, d_cigar=None,
                          stream=None, slot=0):
         """device-resident alignment of the caller's chains (chain c: query d_chain_query[c] u32, members d_members[d_member_off[c] ..
@@ -782,6 +812,12 @@ class FmIndex:
         _check(self._L.awry_dev_align_chains_tally(self._h, slot, d_qbytes, d_qoff, d_chain_query, d_member_off, d_members, m, int(band), d_alns,
                                                    d_n_ops, d_cigar_off, d_cigar, d_tally, stream))
 
+    def dev_align_chains_clip(self, d_qbytes, d_qoff, d_chain_query, d_member_off, d_members, m, band, match, mismatch, gap, end_bonus, d_alns, d_n_ops,
+                              d_cigar_off=None, d_cigar=None, stream=None, slot=0, d_tally=None):
+        """dev_align_chains in the clipped mode: d_alns holds 32-byte ALN_CLIP_DTYPE records; d_tally (optional) as in dev_align_chains_tally"""
+        _check(self._L.awry_dev_align_chains_clip_tally(self._h, slot, d_qbytes, d_qoff, d_chain_query, d_member_off, d_members, m, int(band), int(match),
+                                                        int(mismatch), int(gap), int(end_bonus), d_alns, d_n_ops, d_cigar_off, d_cigar, d_tally, stream))
+
     # ------------------------------------------------------------------ map reads on both strands: ranked alignments, MAPQ
     def parallel_map_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4,
                          max_report: int = 1, band: int = 4, max_seeds: int = 1024, lookback: int = 32, max_gap: int = 1000, max_skew: int = 100,
@@ -792,17 +828,24 @@ class FmIndex:
         the read's reverse complement against the forward text -- pos[c] is the record and offset of t_begin, mapq the mapping
         quality (0 for secondaries, which carry MAP_SECONDARY in flags); status[i] == Q_SEED_CAP marks a read one of whose strands
         was abandoned at max_seeds; want_pos / want_cigar = False leave those arrays empty"""
+        return self._map_csr(None, qbytes, qoff, min_len, max_hits, chains_per_strand, max_report, band, max_seeds, lookback, max_gap, max_skew, min_score,
+                             want_pos, want_cigar)
+
+    def _map_csr(self, clip, qbytes, qoff, min_len, max_hits, chains_per_strand, max_report, band, max_seeds, lookback, max_gap, max_skew, min_score,
+                 want_pos, want_cigar):
+        """awry_map_batch (clip None), or awry_map_clip_batch with clip = (match, mismatch, gap, end_bonus, min_aln_score)"""
         qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
         qo = np.ascontiguousarray(qoff, dtype=np.uint64)
         n = len(qo) - 1
-        off, mp, ps, coff, cg, st = _u64p(), C.POINTER(_lib.Map)(), C.POINTER(_lib.Pos)(), _u64p(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
-        _check(self._L.awry_map_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(max_hits), int(max_seeds), int(lookback),
-                                      int(max_gap), int(max_skew), int(min_score), int(chains_per_strand), int(max_report), int(band), C.byref(off),
-                                      C.byref(mp), C.byref(ps) if want_pos else None, C.byref(coff) if want_cigar else None,
-                                      C.byref(cg) if want_cigar else None, C.byref(st)))
+        fn, rec, dt = (self._L.awry_map_batch, _lib.Map, MAP_DTYPE) if clip is None else (self._L.awry_map_clip_batch, _lib.MapClip, MAP_CLIP_DTYPE)
+        off, mp, ps, coff, cg, st = _u64p(), C.POINTER(rec)(), C.POINTER(_lib.Pos)(), _u64p(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+        _check(fn(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(max_hits), int(max_seeds), int(lookback), int(max_gap),
+                  int(max_skew), int(min_score), int(chains_per_strand), int(max_report), int(band), *(() if clip is None else [int(x) for x in clip]),
+                  C.byref(off), C.byref(mp), C.byref(ps) if want_pos else None, C.byref(coff) if want_cigar else None,
+                  C.byref(cg) if want_cigar else None, C.byref(st)))
         offs = _adopt(self._L, off, n + 1, np.uint64)
         tot = int(offs[-1])
-        maps = _adopt(self._L, mp, 32 * tot, np.uint8).view(MAP_DTYPE)
+        maps = _adopt(self._L, mp, dt.itemsize * tot, np.uint8).view(dt)
         pos = _adopt(self._L, ps, 2 * tot, np.uint64).reshape(-1, 2) if want_pos else np.zeros((0, 2), np.uint64)
         status = _adopt(self._L, st, n, np.uint8)
         if not want_cigar:
@@ -822,6 +865,33 @@ class FmIndex:
         """alignments of one read over both strands"""
         return self.parallel_map([query], min_len, max_hits, chains_per_strand, max_report, band, **chain_params)[0]
 
+    def parallel_map_clip_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4,
+                              max_report: int = 1, band: int = 4, match: int = 1, mismatch: int = 4, gap: int = 6, end_bonus: int = 5,
+                              min_aln_score: int = 0, max_seeds: int = 1024, lookback: int = 32, max_gap: int = 1000, max_skew: int = 100,
+                              min_score: int = 20, want_pos: bool = True, want_cigar: bool = True):
+        """parallel_map_csr in the clipped mode (include/awry_hip.h, "soft-clip read ends"): maps is MAP_CLIP_DTYPE -- the aligned part's
+        span, its score and the letters clipped at either end (for strand 1 of the read's reverse complement) -- a candidate needs score
+        >= min_aln_score, the rank is by (-score, edits, strand, t_begin, chain index), mapq = min(60, 10 (s1 - s2) // (match + mismatch));
+        with max_report >= 2 a chimeric read comes out as a primary and a secondary covering different parts of the read"""
+        return self._map_csr((match, mismatch, gap, end_bonus, min_aln_score), qbytes, qoff, min_len, max_hits, chains_per_strand, max_report, band,
+                             max_seeds, lookback, max_gap, max_skew, min_score, want_pos, want_cigar)
+
+    def parallel_map_clip(self, queries: Iterable, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4, max_report: int = 1, band: int = 4,
+                          match: int = 1, mismatch: int = 4, gap: int = 6, end_bonus: int = 5, min_aln_score: int = 0, **chain_params):
+        """-> per read, [(record, offset, strand, mapq, edits, "70=31S", flags, score, clip_left, clip_right)] of its reported alignments in
+        the clipped mode, the primary first; chain_params: max_seeds, lookback, max_gap, max_skew, min_score"""
+        off, mp, pos, coff, cg, _ = self.parallel_map_clip_csr(*pack_queries(queries), min_len, max_hits, chains_per_strand, max_report, band, match,
+                                                               mismatch, gap, end_bonus, min_aln_score, **chain_params)
+        return [[(int(pos[c][0]), int(pos[c][1]), int(mp[c]["strand"]), int(mp[c]["mapq"]), int(mp[c]["edits"]), cigar_string(cg[coff[c]:coff[c + 1]]),
+                  int(mp[c]["flags"]), int(mp[c]["score"]), int(mp[c]["clip_left"]), int(mp[c]["clip_right"]))
+                 for c in range(int(off[i]), int(off[i + 1]))] for i in range(len(off) - 1)]
+
+    def map_clip_string(self, query, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4, max_report: int = 1, band: int = 4, match: int = 1,
+                        mismatch: int = 4, gap: int = 6, end_bonus: int = 5, min_aln_score: int = 0, **chain_params):
+        """clipped alignments of one read over both strands"""
+        return self.parallel_map_clip([query], min_len, max_hits, chains_per_strand, max_report, band, match, mismatch, gap, end_bonus, min_aln_score,
+                                      **chain_params)[0]
+
     def dev_revcomp(self, d_qbytes, d_qoff, n, d_out_bytes, d_out_off, stream=None, slot=0):
         """device-resident doubled batch: query 2i of (d_out_bytes, d_out_off) is read i as given, query 2i + 1 its reverse
         complement; the caller sizes d_out_bytes at 2 x the reads' bytes and d_out_off at 2 n + 1 u64"""
@@ -836,6 +906,13 @@ class FmIndex:
         dev_scan_counts in between"""
         _check(self._L.awry_dev_map_select(self._h, slot, d_aln_off, d_alns, d_chains, d_chain_status, n, int(chains_per_strand), int(max_report),
                                            d_n_maps, d_read_status, d_map_off, d_maps, d_sel, d_pos, stream))
+
+    def dev_map_select_clip(self, d_aln_off, d_alns, d_chains, d_chain_status, n, chains_per_strand, max_report, match, mismatch, gap, end_bonus,
+                            min_aln_score, d_n_maps, d_read_status=None, d_map_off=None, d_maps=None, d_sel=None, d_pos=None, stream=None, slot=0):
+        """dev_map_select in the clipped mode: 32-byte ALN_CLIP_DTYPE records in, 40-byte MAP_CLIP_DTYPE records out"""
+        _check(self._L.awry_dev_map_select_clip(self._h, slot, d_aln_off, d_alns, d_chains, d_chain_status, n, int(chains_per_strand), int(max_report),
+                                                int(match), int(mismatch), int(gap), int(end_bonus), int(min_aln_score), d_n_maps, d_read_status,
+                                                d_map_off, d_maps, d_sel, d_pos, stream))
 
     # ------------------------------------------------------------------ map read pairs: insert-size pairing, mate rescue, proper-pair flag
     def parallel_map_pairs_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4,

@@ -193,6 +193,16 @@ class FmIndex {
     awry_free_buffer(hoff); awry_free_buffer(hits); awry_free_buffer(gp); awry_free_buffer(ed); awry_free_buffer(st);
     return out;
   }
+  // runs (len << 4 | BAM op: I 1, D 2, S 4, = 7, X 8) -> "57=1X43="
+  static std::string cigar_text(const std::vector<uint32_t>& runs) {
+    std::string out;
+    for (uint32_t run : runs) {
+      const uint32_t op = run & 15u;
+      out += std::to_string(run >> 4);
+      out += op == 7 ? '=' : op == 8 ? 'X' : op == 1 ? 'I' : op == 4 ? 'S' : 'D';
+    }
+    return out;
+  }
   // the same hits aligned (awry_hip.h states the canonical script): the length of the text span each matches and its CIGAR,
   // one run per entry, len << 4 | BAM op (I 1, D 2, = 7, X 8)
   struct EditAlignment {
@@ -201,15 +211,7 @@ class FmIndex {
     uint8_t edits;
     uint32_t text_len;
     std::vector<uint32_t> cigar;
-    std::string cigar_string() const {
-      std::string out;
-      for (uint32_t run : cigar) {
-        const uint32_t op = run & 15u;
-        out += std::to_string(run >> 4);
-        out += op == 7 ? '=' : op == 8 ? 'X' : op == 1 ? 'I' : 'D';
-      }
-      return out;
-    }
+    std::string cigar_string() const { return cigar_text(cigar); }
   };
   template <class StrRange>
   std::vector<std::vector<EditAlignment>> parallel_align_edit(const StrRange& queries, int k, uint64_t max_candidates,
@@ -367,15 +369,7 @@ class FmIndex {
     uint64_t t_begin, t_end;
     uint32_t edits, status;
     std::vector<uint32_t> cigar;
-    std::string cigar_string() const {
-      std::string out;
-      for (uint32_t run : cigar) {
-        const uint32_t op = run & 15u;
-        out += std::to_string(run >> 4);
-        out += op == 7 ? '=' : op == 8 ? 'X' : op == 1 ? 'I' : 'D';
-      }
-      return out;
-    }
+    std::string cigar_string() const { return cigar_text(cigar); }
   };
   template <class StrRange>
   std::vector<std::vector<ChainAlignment>> parallel_align_chains(const StrRange& queries, uint32_t min_len = 12, uint64_t max_hits = 50,
@@ -407,15 +401,7 @@ class FmIndex {
     uint8_t strand, mapq;
     uint16_t flags;
     std::vector<uint32_t> cigar;
-    std::string cigar_string() const {
-      std::string out;
-      for (uint32_t run : cigar) {
-        const uint32_t op = run & 15u;
-        out += std::to_string(run >> 4);
-        out += op == 7 ? '=' : op == 8 ? 'X' : op == 1 ? 'I' : 'D';
-      }
-      return out;
-    }
+    std::string cigar_string() const { return cigar_text(cigar); }
   };
   template <class StrRange>
   std::vector<std::vector<Mapping>> parallel_map(const StrRange& queries, uint32_t min_len = 12, uint64_t max_hits = 50, uint64_t chains_per_strand = 4,
@@ -435,6 +421,66 @@ class FmIndex {
     if (status) status->assign(st, st + n);
     awry_free_buffer(moff); awry_free_buffer(mp); awry_free_buffer(ps); awry_free_buffer(coff); awry_free_buffer(cg); awry_free_buffer(st);
     return out;
+  }
+  // The clipped mode of the two calls above (the definition is in awry_hip.h, "soft-clip read ends"): the end extensions are scored
+  // and local, what they leave out is soft-clipped ('S' runs, BAM op 4), and no extension reaches into another record.  t_begin /
+  // t_end span the aligned part; score = match #'=' - mismatch #'X' - gap (#'I' + #'D').  In parallel_map_clip a candidate needs
+  // score >= min_aln_score, the rank is by score first, and a chimeric read comes out as a primary and a secondary (max_report >= 2).
+  struct ClipParams {
+    uint32_t match = 1, mismatch = 4, gap = 6, end_bonus = 5, min_aln_score = 0;
+  };
+  struct ClippedChainAlignment {
+    awry_chain_t chain;
+    awry_aln_clip_t aln;
+    std::vector<uint32_t> cigar;
+    std::string cigar_string() const { return cigar_text(cigar); }
+  };
+  template <class StrRange>
+  std::vector<std::vector<ClippedChainAlignment>> parallel_align_chains_clip(const StrRange& queries, uint32_t min_len = 12, uint64_t max_hits = 50,
+                                                                             uint64_t max_alignments = 1, uint32_t band = 4, ClipParams c = ClipParams(),
+                                                                             ChainParams p = ChainParams(), std::vector<uint8_t>* status = nullptr) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* aoff = nullptr; awry_chain_t* ch = nullptr; awry_aln_clip_t* al = nullptr; uint64_t* coff = nullptr; uint32_t* cg = nullptr; uint8_t* st = nullptr;
+    check(awry_align_chains_clip_batch(h_, bytes.data(), off.data(), n, min_len, max_hits, p.max_seeds, p.lookback, p.max_gap, p.max_skew, p.min_score,
+                                       max_alignments, band, c.match, c.mismatch, c.gap, c.end_bonus, &aoff, &ch, &al, &coff, &cg, &st));
+    std::vector<std::vector<ClippedChainAlignment>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = aoff[i]; j < aoff[i + 1]; j++) out[i].push_back({ch[j], al[j], std::vector<uint32_t>(cg + coff[j], cg + coff[j + 1])});
+    if (status) status->assign(st, st + n);
+    awry_free_buffer(aoff); awry_free_buffer(ch); awry_free_buffer(al); awry_free_buffer(coff); awry_free_buffer(cg); awry_free_buffer(st);
+    return out;
+  }
+  struct ClippedMapping {
+    awry_pos_t pos;
+    awry_map_clip_t map;
+    std::vector<uint32_t> cigar;
+    std::string cigar_string() const { return cigar_text(cigar); }
+  };
+  template <class StrRange>
+  std::vector<std::vector<ClippedMapping>> parallel_map_clip(const StrRange& queries, uint32_t min_len = 12, uint64_t max_hits = 50,
+                                                             uint64_t chains_per_strand = 4, uint64_t max_report = 1, uint32_t band = 4,
+                                                             ClipParams c = ClipParams(), ChainParams p = ChainParams(),
+                                                             std::vector<uint8_t>* status = nullptr) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* moff = nullptr; awry_map_clip_t* mp = nullptr; awry_pos_t* ps = nullptr; uint64_t* coff = nullptr; uint32_t* cg = nullptr; uint8_t* st = nullptr;
+    check(awry_map_clip_batch(h_, bytes.data(), off.data(), n, min_len, max_hits, p.max_seeds, p.lookback, p.max_gap, p.max_skew, p.min_score,
+                              chains_per_strand, max_report, band, c.match, c.mismatch, c.gap, c.end_bonus, c.min_aln_score, &moff, &mp, &ps, &coff, &cg,
+                              &st));
+    std::vector<std::vector<ClippedMapping>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = moff[i]; j < moff[i + 1]; j++) out[i].push_back({ps[j], mp[j], std::vector<uint32_t>(cg + coff[j], cg + coff[j + 1])});
+    if (status) status->assign(st, st + n);
+    awry_free_buffer(moff); awry_free_buffer(mp); awry_free_buffer(ps); awry_free_buffer(coff); awry_free_buffer(cg); awry_free_buffer(st);
+    return out;
+  }
+  template <class Str>
+  std::vector<ClippedMapping> map_clip_string(const Str& query, uint32_t min_len = 12, uint64_t max_hits = 50, uint64_t chains_per_strand = 4,
+                                              uint64_t max_report = 1, uint32_t band = 4, ClipParams c = ClipParams(), ChainParams p = ChainParams()) {
+    return parallel_map_clip(std::vector<std::string_view>{std::string_view(query)}, min_len, max_hits, chains_per_strand, max_report, band, c, p)[0];
   }
   // read pairs mapped together (no counterpart in the reference; the definition is in awry_hip.h, "map read pairs"): reads1[p] and
   // reads2[p] are the mates of pair p.  Per pair at most one Mapping per mate -- the placements of the best pair, with the pair's

@@ -503,6 +503,66 @@ int awry_map_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qof
                    uint64_t chains_per_strand, uint64_t max_report, uint32_t band, uint64_t **map_off_out, awry_map_t **maps_out,
                    awry_pos_t **pos_out, uint64_t **cigar_off_out, uint32_t **cigar_out, uint8_t **status_out);
 
+/* ---- soft-clip read ends: scored local extension in chain align and map (no counterpart in the reference) --------
+ * A clipped mode beside the end-to-end one.  The end-to-end pass consumes the query whole; a read with an adapter tail, a read that
+ * hangs over a record's end and a chimeric read then pay for letters that belong nowhere near.  Here the two end extensions are
+ * scored and local: an extension may stop early and the rest of the read is soft-clipped ('S').  No end-to-end entry point
+ * changes its output.  Everything is integer arithmetic and every tie is broken explicitly.
+ * Parameters, passed after band: match = a, 1 .. AWRY_CLIP_MAX_MATCH = 16, the score of an '='; mismatch = b, 0 ..
+ *   AWRY_CLIP_MAX_PENALTY = 64, the penalty of an 'X'; gap = g, 0 .. 64, the penalty per inserted or deleted letter; end_bonus = E,
+ *   0 .. AWRY_CLIP_MAX_END_BONUS = 1024, how much score an end-to-end extension may lose and still win; at the map level also
+ *   min_aln_score = T >= 0, the lowest score a candidate may have.  Out of range => AWRY_ERR_ARG.
+ * Score of a script: a #'=' - b #'X' - g (#'I' + #'D'); 'S' letters score nothing.  Every score fits 32 bits (L <= 1024).
+ * What stays.  Pieces, and the gaps between pieces, are exactly "align chains"'s: gaps stay global, unit cost, same band, same
+ *   traceback priority.  edits counts 'X' + 'I' + 'D' of the aligned part.  Letters compare as there: a text sentinel matches
+ *   nothing, query N equals text N.
+ * Record bounds.  r = the record of the first piece's text start tb_first by awry_get_seq_location's rule; the record is
+ *   [seq_start[r], seq_start[r+1]), the last one ends at n.  Left avail = tb_first - seq_start[r]; right avail = max(0, record end -
+ *   te_last).  So a clipped extension never reaches into another record.
+ * Clipped extension.  x = the a query letters outward from the piece, y_j the text outward from it (the left extension on reversed
+ *   strings, as in "align chains").  J = min(a + W, avail).  The band is -W <= j - i <= W whatever avail is: the extension's skew term
+ *   is gone.  Cells outside the band, or with j > J, are -infinity.  H[0][0] = 0; H[i][j] = max(H[i-1][j-1] + (a if the letters match
+ *   else -b), H[i-1][j] - g, H[i][j-1] - g).  Rows beyond J + W have no cell.
+ * Where it ends.  (i*, j*) maximises H over all cells; ties go to the largest i, then the smallest j; H* >= 0 because of (0, 0).  If
+ *   row a has a finite cell, j_e is the smallest j that maximises H[a][j] and H_e its value; if H_e + E >= H* the extension ends at
+ *   (a, j_e) and nothing is clipped.  Otherwise it ends at (i*, j*) and a - i* letters are clipped.
+ * Traceback from the end cell: the diagonal first, then 'I', then 'D', on banded values, as everywhere else.
+ * Skew.  AWRY_ALN_SKEW arises from gaps only: a read hanging 17 or 100 letters over an end is AWRY_ALN_OK and clipped.
+ * Record.  awry_aln_clip_t, 32 bytes: awry_aln_t's fields, then score and clip_left / clip_right.  t_begin / t_end span the aligned
+ *   part.  A chain that is not aligned has score 0 and clips 0.
+ * Runs.  The encoding of "align chains" plus S = BAM op 4: at most one 'S' run first and one last; an 'S' run never merges with
+ *   another run; the 'S' letters plus the query letters of the aligned part are always L.
+ * Properties.  (1) Replaying the CIGAR over q and T[t_begin .. t_end) reproduces both strings, edits, score and both clips.
+ *   (2) rec(t_begin) == rec(t_end - 1) whenever the chain's pieces lie in one record.  (3) An extension whose letters all match is
+ *   never clipped: H <= a i, and ties go to the largest i.  (4) With b, g >= 1 the aligned part of a clipped extension is empty or
+ *   ends, at its outer end, with '='.  (5) An extension is clipped iff H* > H_e + E; its score is H* then and H_e otherwise, so it is at
+ *   least H* - E and at least H_e, and at least max(0, H_e) when E = 0 (a kept end-to-end extension may score below 0 by up to E).
+ * Map level: awry_map_batch's rules except that a candidate must also have score >= T; the rank is ascending by (-score, edits,
+ *   strand, t_begin, j); MAPQ of the primary is 0 under AWRY_Q_SEED_CAP, 60 without a second kept candidate, else min(60, 10 (s1 -
+ *   s2) / (a + b)) with floor division, s1 and s2 the scores of the first and second kept candidates.  Redundancy, report, the
+ *   secondary flag and status are unchanged.  Reverse-strand clips are those computed on rc(read).  Record awry_map_clip_t, 40 bytes:
+ *   awry_map_t's fields, then score and clip_left / clip_right.  With R >= 2 a chimeric read comes out as a primary and a secondary
+ *   that cover different parts of the read at two loci: that is intended.
+ *
+ * awry_align_chains_clip_batch and awry_map_clip_batch mirror awry_align_chains_batch and awry_map_batch: the same arguments plus the
+ * scalars above, the same CSR output with the clipped records, the same errors and index restrictions.  awry_map_pairs_batch is
+ * untouched: pairing clipped records is a later change. */
+enum { AWRY_CLIP_MAX_MATCH = 16, AWRY_CLIP_MAX_PENALTY = 64, AWRY_CLIP_MAX_END_BONUS = 1024 };
+enum { AWRY_CIGAR_SOFT_CLIP = 4 };
+typedef struct { uint64_t t_begin, t_end; uint32_t edits, status; int32_t score; uint16_t clip_left, clip_right; } awry_aln_clip_t;
+typedef struct { uint64_t t_begin, t_end; uint32_t edits, chain_score, chain_index; uint8_t strand, mapq; uint16_t flags; int32_t score; uint16_t clip_left, clip_right; } awry_map_clip_t;
+int awry_align_chains_clip_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len,
+                                 uint64_t max_hits, uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew,
+                                 uint32_t min_score, uint64_t max_alignments, uint32_t band, uint32_t match, uint32_t mismatch,
+                                 uint32_t gap, uint32_t end_bonus, uint64_t **aln_off_out, awry_chain_t **chains_out,
+                                 awry_aln_clip_t **alns_out, uint64_t **cigar_off_out, uint32_t **cigar_out, uint8_t **status_out);
+int awry_map_clip_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len,
+                        uint64_t max_hits, uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew,
+                        uint32_t min_score, uint64_t chains_per_strand, uint64_t max_report, uint32_t band, uint32_t match,
+                        uint32_t mismatch, uint32_t gap, uint32_t end_bonus, uint32_t min_aln_score, uint64_t **map_off_out,
+                        awry_map_clip_t **maps_out, awry_pos_t **pos_out, uint64_t **cigar_off_out, uint32_t **cigar_out,
+                        uint8_t **status_out);
+
 /* ---- map read pairs: insert-size pairing, mate rescue, proper-pair flag (no counterpart in the reference) --------
  * Short reads come in pairs: two reads from the ends of one fragment, on opposite strands, a known distance apart.  The mate places
  * a read whose own seeds are ambiguous or missing.  This stage joins the ranked candidates of awry_map_batch with the k-edit scan
@@ -792,6 +852,20 @@ int awry_dev_align_chains_tally(awry_index_t *idx, int slot, const uint8_t *d_qb
                                 const uint32_t *d_chain_query, const uint64_t *d_member_off, const awry_seed_t *d_members,
                                 uint64_t m, uint32_t band, awry_aln_t *d_alns, uint64_t *d_n_ops, const uint64_t *d_cigar_off,
                                 uint32_t *d_cigar, uint64_t *d_tally, void *stream);
+/* The clipped mode of the two entry points above ("soft-clip read ends" states it): the same arguments and protocol plus the four
+ * weights after band; d_alns holds awry_aln_clip_t records, and the runs may begin and end with an 'S' run.  The same kernels,
+ * instantiated per mode; the classes are cut by the gaps' skew only (an extension needs 2 W + 1 cells).  The census counts the same
+ * things; a clipped extension's rows beyond J + W have no cell and do not run. */
+int awry_dev_align_chains_clip(awry_index_t *idx, int slot, const uint8_t *d_qbytes, const uint64_t *d_qoff,
+                               const uint32_t *d_chain_query, const uint64_t *d_member_off, const awry_seed_t *d_members, uint64_t m,
+                               uint32_t band, uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus,
+                               awry_aln_clip_t *d_alns, uint64_t *d_n_ops, const uint64_t *d_cigar_off, uint32_t *d_cigar,
+                               void *stream);
+int awry_dev_align_chains_clip_tally(awry_index_t *idx, int slot, const uint8_t *d_qbytes, const uint64_t *d_qoff,
+                                     const uint32_t *d_chain_query, const uint64_t *d_member_off, const awry_seed_t *d_members,
+                                     uint64_t m, uint32_t band, uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus,
+                                     awry_aln_clip_t *d_alns, uint64_t *d_n_ops, const uint64_t *d_cigar_off, uint32_t *d_cigar,
+                                     uint64_t *d_tally, void *stream);
 /* The doubled batch of awry_map_batch, device-resident: query 2i of the output is read i as given, query 2i + 1 is rc(read i) (the
  * definition is stated there); d_out_off[2i] = 2 (d_qoff[i] - d_qoff[0]), d_out_off[2i+1] = that + L_i, d_out_off[2n] = 2
  * (d_qoff[n] - d_qoff[0]).  The caller sizes d_out_bytes at 2 x the reads' bytes (plus what the consuming entry point wants
@@ -813,6 +887,14 @@ int awry_dev_map_select(awry_index_t *idx, int slot, const uint64_t *d_aln_off, 
                         const awry_chain_t *d_chains, const uint8_t *d_chain_status, uint64_t n, uint32_t chains_per_strand,
                         uint32_t max_report, uint64_t *d_n_maps, uint8_t *d_read_status, const uint64_t *d_map_off,
                         awry_map_t *d_maps, uint32_t *d_sel, awry_pos_t *d_pos, void *stream);
+/* The clipped mode of awry_dev_map_select ("soft-clip read ends", map level): the same arguments and protocol plus the five
+ * scalars after max_report (all are checked; MAPQ divides by match + mismatch, min_aln_score is the threshold, gap and end_bonus
+ * play no part in the selection); it reads awry_aln_clip_t and writes awry_map_clip_t records. */
+int awry_dev_map_select_clip(awry_index_t *idx, int slot, const uint64_t *d_aln_off, const awry_aln_clip_t *d_alns,
+                             const awry_chain_t *d_chains, const uint8_t *d_chain_status, uint64_t n, uint32_t chains_per_strand,
+                             uint32_t max_report, uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus,
+                             uint32_t min_aln_score, uint64_t *d_n_maps, uint8_t *d_read_status, const uint64_t *d_map_off,
+                             awry_map_clip_t *d_maps, uint32_t *d_sel, awry_pos_t *d_pos, void *stream);
 /* The rescue windows of awry_map_pairs_batch over a caller's kept lists: the candidates of read i (mate i & 1 of pair i >> 1) are
  * d_cands[d_cand_off[i] .. d_cand_off[i+1]) in rank order, d_cand_off and d_qoff (the reads' own offsets: only the lengths are read)
  * have 2 n_pairs + 1 entries.  Output at a fixed stride: slot w = (2p + m) G + a, G = rescue_anchors, is candidate a of mate m.  An
