@@ -163,6 +163,11 @@ def load_library():
         C.POINTER(C.POINTER(Map)), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)), C.POINTER(u8p), C.POINTER(C.POINTER(u32)))
     sig("awry_dev_pair_windows", i32, vp, i32, vp, vp, vp, u64, u64, u64, u32, i32, vp, vp, vp, vp)
     sig("awry_dev_pair_select", i32, vp, i32, vp, vp, vp, vp, u64, u64, u64, u32, u32, vp, vp, vp, vp, vp, vp, vp)
+    sig("awry_map_pairs_clip_batch", i32, vp, vp, u64p, u64, u32, u64, u32, u32, u32, u32, u32, u64, u32, u64, u64, u32, u32, i32, u32, u32, u32, u32, u32,
+        C.POINTER(u64p), C.POINTER(C.POINTER(MapClip)), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)), C.POINTER(u8p),
+        C.POINTER(C.POINTER(u32)))
+    sig("awry_dev_pair_windows_clip", i32, vp, i32, vp, vp, vp, u64, u64, u64, u32, i32, vp, vp, vp, vp)
+    sig("awry_dev_pair_select_clip", i32, vp, i32, vp, vp, vp, vp, u64, u64, u64, u32, u32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp)
     sig("awry_locate_edit_batch", i32, vp, vp, u64p, u64, i32, u64, C.POINTER(u64p), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(u8p),
         C.POINTER(u8p))
     sig("awry_dev_edit_windows", i32, vp, i32, vp, vp, vp, vp, vp, u64, i32, vp, vp, vp, vp, vp)

@@ -67,6 +67,38 @@ int checked_symbol(const awry_index* ix, uint8_t ascii) {
   return index_of_ascii(ix->host.alphabet, ascii);
 }
 
+// awry_dev_pair_windows and its clipped mode: Rec is the kernels' record of the caller's MapT
+template <class Rec, class MapT>
+void dev_pair_windows(awry_index_t* idx, int slot, const uint64_t* d_cand_off, const MapT* d_cands, const uint64_t* d_qoff, uint64_t n_pairs,
+                      uint64_t min_insert, uint64_t max_insert, uint32_t rescue_anchors, int rescue_edits, uint32_t* d_win_query, uint64_t* d_win_first,
+                      uint32_t* d_win_count, void* stream) {
+  const PairParams pp = pair_params(min_insert, max_insert, 0, rescue_anchors, rescue_edits);
+  require(idx != nullptr, "null argument");
+  if (idx->host.alphabet != NUCLEOTIDE) throw ArgError("mapping read pairs needs a nucleotide index");
+  Replica& r = replica(idx, slot);
+  require_chain_index(r.dev.bwt_len);
+  require(n_pairs < (1ull << 28), "more than 2^28 - 1 pairs in one launch");
+  require(n_pairs == 0 || rescue_anchors == 0 || (d_cand_off && d_cands && d_qoff && d_win_query && d_win_first && d_win_count), "null device pointer");
+  launch_pair_windows(r, d_cand_off, reinterpret_cast<const Rec*>(d_cands), d_qoff, 1, n_pairs, pp, d_win_query, d_win_first, d_win_count,
+                      (hipStream_t)stream);
+}
+
+// awry_dev_pair_select and its clipped mode
+template <class Rec, class MapT>
+void dev_pair_select(awry_index_t* idx, int slot, const uint64_t* d_cand_off, const MapT* d_cands, const MapT* d_resc, const uint8_t* d_read_status,
+                     uint64_t n_pairs, const PairParams& pp, const PairMode& pm, uint64_t* d_n_maps, const uint64_t* d_map_off, MapT* d_maps, uint32_t* d_sel,
+                     awry_pos_t* d_pos, uint32_t* d_insert, void* stream) {
+  require(idx != nullptr, "null argument");
+  if (idx->host.alphabet != NUCLEOTIDE) throw ArgError("mapping read pairs needs a nucleotide index");
+  Replica& r = replica(idx, slot);
+  require(n_pairs < (1ull << 28), "more than 2^28 - 1 pairs in one launch");
+  require(n_pairs == 0 || (d_cand_off && d_cands && (pp.rescue_anchors == 0 || d_resc) && (d_map_off ? d_maps != nullptr : d_n_maps != nullptr)),
+          "null device pointer");
+  launch_pair_select<Rec>(r, d_cand_off, reinterpret_cast<const Rec*>(d_cands), pp.rescue_anchors ? reinterpret_cast<const Rec*>(d_resc) : nullptr,
+                          d_read_status, n_pairs, pp, pm, d_n_maps, d_map_off, reinterpret_cast<Rec*>(d_maps), d_sel, reinterpret_cast<uint64_t*>(d_pos),
+                          d_insert, (hipStream_t)stream);
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -517,8 +549,30 @@ int awry_map_pairs_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_
     require_map_args(chains_per_strand, 1, band);
     const PairParams pp = pair_params(min_insert, max_insert, unpaired_penalty, rescue_anchors, rescue_edits);
     require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
-    map_pairs_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, band, pp, map_off_out, maps_out, pos_out, cigar_off_out,
-                    cigar_out, status_out, insert_out);
+    map_pairs_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, band, AlignMode{}, MapMode{}, PairMode{}, pp, map_off_out,
+                    maps_out, pos_out, cigar_off_out, cigar_out, status_out, insert_out);
+  });
+}
+
+int awry_map_pairs_clip_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits,
+                              uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score, uint64_t chains_per_strand,
+                              uint32_t band, uint64_t min_insert, uint64_t max_insert, uint32_t unpaired_penalty, uint32_t rescue_anchors, int rescue_edits,
+                              uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus, uint32_t min_aln_score, uint64_t** map_off_out,
+                              awry_map_clip_t** maps_out, awry_pos_t** pos_out, uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out,
+                              uint32_t** insert_out) {
+  return guarded([&] {
+    require(idx && qoff && map_off_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_smem_args(min_len);
+    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
+    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    require_map_args(chains_per_strand, 1, band);
+    const PairParams pp = pair_params(min_insert, max_insert, unpaired_penalty, rescue_anchors, rescue_edits, true);
+    const AlignMode md = clip_mode(match, mismatch, gap, end_bonus);
+    const MapMode mm = clip_map_mode(md, min_aln_score);
+    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
+    map_pairs_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, band, md, mm, clip_pair_mode(md, mm), pp, map_off_out, maps_out,
+                    pos_out, cigar_off_out, cigar_out, status_out, insert_out);
   });
 }
 
@@ -1124,15 +1178,17 @@ int awry_dev_pair_windows(awry_index_t* idx, int slot, const uint64_t* d_cand_of
                           uint64_t min_insert, uint64_t max_insert, uint32_t rescue_anchors, int rescue_edits, uint32_t* d_win_query, uint64_t* d_win_first,
                           uint32_t* d_win_count, void* stream) {
   return guarded([&] {
-    const PairParams pp = pair_params(min_insert, max_insert, 0, rescue_anchors, rescue_edits);
-    require(idx != nullptr, "null argument");
-    if (idx->host.alphabet != NUCLEOTIDE) throw ArgError("mapping read pairs needs a nucleotide index");
-    Replica& r = replica(idx, slot);
-    require_chain_index(r.dev.bwt_len);
-    require(n_pairs < (1ull << 28), "more than 2^28 - 1 pairs in one launch");
-    require(n_pairs == 0 || rescue_anchors == 0 || (d_cand_off && d_cands && d_qoff && d_win_query && d_win_first && d_win_count), "null device pointer");
-    launch_pair_windows(r, d_cand_off, reinterpret_cast<const MapRec*>(d_cands), d_qoff, 1, n_pairs, pp, d_win_query, d_win_first, d_win_count,
-                        (hipStream_t)stream);
+    dev_pair_windows<MapRec>(idx, slot, d_cand_off, d_cands, d_qoff, n_pairs, min_insert, max_insert, rescue_anchors, rescue_edits, d_win_query, d_win_first,
+                             d_win_count, stream);
+  });
+}
+
+int awry_dev_pair_windows_clip(awry_index_t* idx, int slot, const uint64_t* d_cand_off, const awry_map_clip_t* d_cands, const uint64_t* d_qoff,
+                               uint64_t n_pairs, uint64_t min_insert, uint64_t max_insert, uint32_t rescue_anchors, int rescue_edits, uint32_t* d_win_query,
+                               uint64_t* d_win_first, uint32_t* d_win_count, void* stream) {
+  return guarded([&] {
+    dev_pair_windows<MapClipRec>(idx, slot, d_cand_off, d_cands, d_qoff, n_pairs, min_insert, max_insert, rescue_anchors, rescue_edits, d_win_query,
+                                 d_win_first, d_win_count, stream);
   });
 }
 
@@ -1142,15 +1198,21 @@ int awry_dev_pair_select(awry_index_t* idx, int slot, const uint64_t* d_cand_off
                          uint32_t* d_insert, void* stream) {
   return guarded([&] {
     const PairParams pp = pair_params(min_insert, max_insert, unpaired_penalty, rescue_anchors, 0);
-    require(idx != nullptr, "null argument");
-    if (idx->host.alphabet != NUCLEOTIDE) throw ArgError("mapping read pairs needs a nucleotide index");
-    Replica& r = replica(idx, slot);
-    require(n_pairs < (1ull << 28), "more than 2^28 - 1 pairs in one launch");
-    require(n_pairs == 0 || (d_cand_off && d_cands && (rescue_anchors == 0 || d_resc) && (d_map_off ? d_maps != nullptr : d_n_maps != nullptr)),
-            "null device pointer");
-    launch_pair_select(r, d_cand_off, reinterpret_cast<const MapRec*>(d_cands), rescue_anchors ? reinterpret_cast<const MapRec*>(d_resc) : nullptr,
-                       d_read_status, n_pairs, pp, d_n_maps, d_map_off, reinterpret_cast<MapRec*>(d_maps), d_sel, reinterpret_cast<uint64_t*>(d_pos), d_insert,
-                       (hipStream_t)stream);
+    dev_pair_select<MapRec>(idx, slot, d_cand_off, d_cands, d_resc, d_read_status, n_pairs, pp, PairMode{}, d_n_maps, d_map_off, d_maps, d_sel, d_pos,
+                            d_insert, stream);
+  });
+}
+
+int awry_dev_pair_select_clip(awry_index_t* idx, int slot, const uint64_t* d_cand_off, const awry_map_clip_t* d_cands, const awry_map_clip_t* d_resc,
+                              const uint8_t* d_read_status, uint64_t n_pairs, uint64_t min_insert, uint64_t max_insert, uint32_t unpaired_penalty,
+                              uint32_t rescue_anchors, uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus, uint32_t min_aln_score,
+                              uint64_t* d_n_maps, const uint64_t* d_map_off, awry_map_clip_t* d_maps, uint32_t* d_sel, awry_pos_t* d_pos, uint32_t* d_insert,
+                              void* stream) {
+  return guarded([&] {
+    const PairParams pp = pair_params(min_insert, max_insert, unpaired_penalty, rescue_anchors, 0, true);
+    const AlignMode md = clip_mode(match, mismatch, gap, end_bonus);
+    dev_pair_select<MapClipRec>(idx, slot, d_cand_off, d_cands, d_resc, d_read_status, n_pairs, pp, clip_pair_mode(md, clip_map_mode(md, min_aln_score)),
+                                d_n_maps, d_map_off, d_maps, d_sel, d_pos, d_insert, stream);
   });
 }
 

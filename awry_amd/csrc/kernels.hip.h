@@ -53,12 +53,13 @@
 //                         + MAP_SELECT_KERNEL<FILL>          one read per lane: rank the aligned chains of both strands by selection, drop
 //                                                            redundant spans, MAPQ; count pass, scan, fill pass [kernels_map]
 //                         + MAP_GATHER_KERNEL                the reported alignments as a chain list for the CIGAR fill pass [kernels_map]
-//   map read pairs        PAIR_WINDOWS_KERNEL                one candidate slot per lane: is it an anchor, and the window of starts in which it
+//   map read pairs        PAIR_WINDOWS_KERNEL<Rec>           one candidate slot per lane: is it an anchor, and the window of starts in which it
 //                                                            expects the other mate [kernels_pair]
-//                         + pair_sub_windows / PAIR_BEST_HIT / PAIR_RESCUED kernels: windows cut for the edit scan, the smallest (distance,
+//                         + pair_sub_windows / PAIR_BEST_HIT / PAIR_RESCUED<Rec> kernels: windows cut for the edit scan, the smallest (distance,
 //                                                            position) hit of a window, the rescued candidate [kernels_pair]
-//                         + PAIR_SELECT_KERNEL<FILL>         one pair per lane: rescued candidates appended, the pair of smallest cost, pair
+//                         + PAIR_SELECT_KERNEL<FILL, Rec>    one pair per lane: rescued candidates appended, the pair of smallest cost, pair
 //                                                            MAPQ, flags, insert; count pass, scan, fill pass [kernels_pair]
+//                                                            (Rec = MapClipRec: the clipped mode -- inserts through the clips, pairs by score)
 //   count, wide rows      count_nt2_wide_kernel, count_nt2_wide_probe_kernel   64-bit rows [kernels_wide]
 //   locate                LOCATE_TILE_KERNEL<A>              hit -> row, sampled / verified hits finished [this file]
 //                         + LOCATE_WALK_NT_LANE_KERNEL       LF walks of the rest, one hit per lane, whole block per step [this file]

@@ -664,25 +664,29 @@ void launch_map_select(Replica& r, const uint64_t* d_aln_off, const void* d_alns
 }
 
 // The rescue windows of P pairs (kernels_pair.hip.h): 2 P rescue_anchors slots at a fixed stride.  qstride: 1 when d_qoff holds the
-// reads' own 2 P + 1 offsets, 2 when it holds the doubled batch's.
-void launch_pair_windows(Replica& r, const uint64_t* d_cand_off, const MapRec* d_cands, const uint64_t* d_qoff, uint32_t qstride, uint64_t P,
+// reads' own 2 P + 1 offsets, 2 when it holds the doubled batch's.  Rec: MapRec end to end, MapClipRec in the clipped mode.
+template <class Rec>
+void launch_pair_windows(Replica& r, const uint64_t* d_cand_off, const Rec* d_cands, const uint64_t* d_qoff, uint32_t qstride, uint64_t P,
                          const PairParams& pp, uint32_t* d_win_query, uint64_t* d_win_first, uint32_t* d_win_count, hipStream_t s) {
   const uint64_t slots = 2 * P * pp.rescue_anchors;
   if (slots == 0) return;
-  hipLaunchKernelGGL(pair_windows_kernel, dim3(grid_for(r, slots, 256)), dim3(256), 0, s, r.dev, d_cand_off, d_cands, d_qoff, qstride, P, pp, d_win_query,
+  hipLaunchKernelGGL(pair_windows_kernel<Rec>, dim3(grid_for(r, slots, 256)), dim3(256), 0, s, r.dev, d_cand_off, d_cands, d_qoff, qstride, P, pp, d_win_query,
                      d_win_first, d_win_count);
   HIP_CHECK(hipGetLastError());
 }
 
 // Pair choice over the kept lists and the rescued candidates of P pairs (kernels_pair.hip.h).  d_map_off == nullptr: the count pass
 // (d_n_maps[2 P]); else the fill pass (d_maps; d_sel, d_pos, d_insert nullable).  d_resc == nullptr: no rescued candidates.
-void launch_pair_select(Replica& r, const uint64_t* d_cand_off, const MapRec* d_cands, const MapRec* d_resc, const uint8_t* d_read_status, uint64_t P,
-                        const PairParams& pp, uint64_t* d_n_maps, const uint64_t* d_map_off, MapRec* d_maps, uint32_t* d_sel, uint64_t* d_pos,
-                        uint32_t* d_insert, hipStream_t s) {
+// Rec and md: MapRec end to end, MapClipRec with the clipped mode's scalars.
+template <class Rec>
+void launch_pair_select(Replica& r, const uint64_t* d_cand_off, const Rec* d_cands, const Rec* d_resc, const uint8_t* d_read_status, uint64_t P,
+                        const PairParams& pp, const PairMode& md, uint64_t* d_n_maps, const uint64_t* d_map_off, Rec* d_maps, uint32_t* d_sel,
+                        uint64_t* d_pos, uint32_t* d_insert, hipStream_t s) {
   if (P == 0) return;
+  require(md.clip == pair_clipped<Rec>, "internal: the pair records are not the mode's");
   with_flags(d_map_off != nullptr, [&](auto F) {
-    hipLaunchKernelGGL(pair_select_kernel<F()>, dim3(grid_for(r, P, 256)), dim3(256), 0, s, r.dev, d_cand_off, d_cands, d_resc, d_read_status, P, pp, d_n_maps,
-                       d_map_off, d_maps, d_sel, d_pos, d_insert);
+    hipLaunchKernelGGL((pair_select_kernel<F(), Rec>), dim3(grid_for(r, P, 256)), dim3(256), 0, s, r.dev, d_cand_off, d_cands, d_resc, d_read_status, P, pp,
+                       d_n_maps, d_map_off, d_maps, d_sel, d_pos, d_insert, md);
   });
   HIP_CHECK(hipGetLastError());
 }

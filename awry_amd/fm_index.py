@@ -925,19 +925,27 @@ class FmIndex:
         MAP_PROPER_PAIR iff they lie on opposite strands of one record, forward first, min_insert <= outer distance <= max_insert
         (insert[p] is that distance, else 0); a mate found by rescue -- within rescue_edits edits where the insert size puts it --
         carries MAP_RESCUED; a read whose mate has no placement carries MAP_MATE_UNMAPPED and its single-end MAPQ"""
+        return self._map_pairs_csr(None, qbytes, qoff, min_len, max_hits, chains_per_strand, band, min_insert, max_insert, unpaired_penalty, rescue_anchors,
+                                   rescue_edits, max_seeds, lookback, max_gap, max_skew, min_score, want_pos, want_cigar)
+
+    def _map_pairs_csr(self, clip, qbytes, qoff, min_len, max_hits, chains_per_strand, band, min_insert, max_insert, unpaired_penalty, rescue_anchors,
+                       rescue_edits, max_seeds, lookback, max_gap, max_skew, min_score, want_pos, want_cigar):
+        """awry_map_pairs_batch (clip None), or awry_map_pairs_clip_batch with clip = (match, mismatch, gap, end_bonus, min_aln_score)"""
         qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
         qo = np.ascontiguousarray(qoff, dtype=np.uint64)
         n = len(qo) - 1
-        off, mp, ps, coff, cg, st = _u64p(), C.POINTER(_lib.Map)(), C.POINTER(_lib.Pos)(), _u64p(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
+        fn, rec, dt = ((self._L.awry_map_pairs_batch, _lib.Map, MAP_DTYPE) if clip is None else
+                       (self._L.awry_map_pairs_clip_batch, _lib.MapClip, MAP_CLIP_DTYPE))
+        off, mp, ps, coff, cg, st = _u64p(), C.POINTER(rec)(), C.POINTER(_lib.Pos)(), _u64p(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
         ins = C.POINTER(C.c_uint32)()
-        _check(self._L.awry_map_pairs_batch(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(max_hits), int(max_seeds),
-                                            int(lookback), int(max_gap), int(max_skew), int(min_score), int(chains_per_strand), int(band),
-                                            int(min_insert), int(max_insert), int(unpaired_penalty), int(rescue_anchors), int(rescue_edits),
-                                            C.byref(off), C.byref(mp), C.byref(ps) if want_pos else None, C.byref(coff) if want_cigar else None,
-                                            C.byref(cg) if want_cigar else None, C.byref(st), C.byref(ins)))
+        _check(fn(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(max_hits), int(max_seeds), int(lookback), int(max_gap),
+                  int(max_skew), int(min_score), int(chains_per_strand), int(band), int(min_insert), int(max_insert), int(unpaired_penalty),
+                  int(rescue_anchors), int(rescue_edits), *(() if clip is None else [int(x) for x in clip]), C.byref(off), C.byref(mp),
+                  C.byref(ps) if want_pos else None, C.byref(coff) if want_cigar else None, C.byref(cg) if want_cigar else None, C.byref(st),
+                  C.byref(ins)))
         offs = _adopt(self._L, off, n + 1, np.uint64)
         tot = int(offs[-1])
-        maps = _adopt(self._L, mp, 32 * tot, np.uint8).view(MAP_DTYPE)
+        maps = _adopt(self._L, mp, dt.itemsize * tot, np.uint8).view(dt)
         pos = _adopt(self._L, ps, 2 * tot, np.uint64).reshape(-1, 2) if want_pos else np.zeros((0, 2), np.uint64)
         status, insert = _adopt(self._L, st, n, np.uint8), _adopt(self._L, ins, n // 2, np.uint32)
         if not want_cigar:
@@ -982,6 +990,57 @@ class FmIndex:
         slot for a rescued record) and d_pos (2 u64), and d_insert[n_pairs] (u32); scan d_n_maps with dev_scan_counts in between"""
         _check(self._L.awry_dev_pair_select(self._h, slot, d_cand_off, d_cands, d_resc, d_read_status, n_pairs, int(min_insert), int(max_insert),
                                             int(unpaired_penalty), int(rescue_anchors), d_n_maps, d_map_off, d_maps, d_sel, d_pos, d_insert, stream))
+
+    def parallel_map_pairs_clip_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4,
+                                    band: int = 4, min_insert: int = 0, max_insert: int = 1000, unpaired_penalty: int = 20, rescue_anchors: int = 2,
+                                    rescue_edits: int = 4, match: int = 1, mismatch: int = 4, gap: int = 6, end_bonus: int = 5, min_aln_score: int = 0,
+                                    max_seeds: int = 1024, lookback: int = 32, max_gap: int = 1000, max_skew: int = 100, min_score: int = 20,
+                                    want_pos: bool = True, want_cigar: bool = True):
+        """parallel_map_pairs_csr in the clipped mode (include/awry_hip.h, "map read pairs, clipped"): maps is MAP_CLIP_DTYPE, the kept
+        lists are parallel_map_clip_csr's, the insert is measured between the mates' 5' ends projected through their clips (t_begin -
+        clip_left of the forward mate to t_end + clip_right of the reverse one), unpaired_penalty is in score units, the best pair has the
+        largest score + score - (unpaired_penalty if improper), mapq = min(60, 10 (S1 - S2) // (match + mismatch)); a rescued mate is a
+        whole-read alignment within rescue_edits edits with score >= min_aln_score and clips 0"""
+        return self._map_pairs_csr((match, mismatch, gap, end_bonus, min_aln_score), qbytes, qoff, min_len, max_hits, chains_per_strand, band, min_insert,
+                                   max_insert, unpaired_penalty, rescue_anchors, rescue_edits, max_seeds, lookback, max_gap, max_skew, min_score, want_pos,
+                                   want_cigar)
+
+    def parallel_map_pairs_clip(self, reads1: Iterable, reads2: Iterable, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4,
+                                band: int = 4, min_insert: int = 0, max_insert: int = 1000, unpaired_penalty: int = 20, rescue_anchors: int = 2,
+                                rescue_edits: int = 4, match: int = 1, mismatch: int = 4, gap: int = 6, end_bonus: int = 5, min_aln_score: int = 0,
+                                **chain_params):
+        """-> per pair (record of reads1[p] or None, record of reads2[p] or None, insert), a record in parallel_map_clip's form: (record,
+        offset, strand, mapq, edits, "60=41S", flags, score, clip_left, clip_right); chain_params: max_seeds, lookback, max_gap, max_skew,
+        min_score"""
+        r1, r2 = list(reads1), list(reads2)
+        if len(r1) != len(r2):
+            raise ValueError("reads1 and reads2 must have one read per pair each")
+        off, mp, pos, coff, cg, _, ins = self.parallel_map_pairs_clip_csr(*pack_queries([q for pair in zip(r1, r2) for q in pair]), min_len, max_hits,
+                                                                          chains_per_strand, band, min_insert, max_insert, unpaired_penalty,
+                                                                          rescue_anchors, rescue_edits, match, mismatch, gap, end_bonus, min_aln_score,
+                                                                          **chain_params)
+
+        def rec(i):
+            if off[i] == off[i + 1]:
+                return None
+            c = int(off[i])
+            return (int(pos[c][0]), int(pos[c][1]), int(mp[c]["strand"]), int(mp[c]["mapq"]), int(mp[c]["edits"]), cigar_string(cg[coff[c]:coff[c + 1]]),
+                    int(mp[c]["flags"]), int(mp[c]["score"]), int(mp[c]["clip_left"]), int(mp[c]["clip_right"]))
+        return [(rec(2 * p), rec(2 * p + 1), int(ins[p])) for p in range(len(r1))]
+
+    def dev_pair_windows_clip(self, d_cand_off, d_cands, d_qoff, n_pairs, min_insert, max_insert, rescue_anchors, rescue_edits, d_win_query, d_win_first,
+                              d_win_count, stream=None, slot=0):
+        """dev_pair_windows in the clipped mode: 40-byte MAP_CLIP_DTYPE records in, the windows measured from the clipped fragment ends"""
+        _check(self._L.awry_dev_pair_windows_clip(self._h, slot, d_cand_off, d_cands, d_qoff, n_pairs, int(min_insert), int(max_insert),
+                                                  int(rescue_anchors), int(rescue_edits), d_win_query, d_win_first, d_win_count, stream))
+
+    def dev_pair_select_clip(self, d_cand_off, d_cands, d_resc, d_read_status, n_pairs, min_insert, max_insert, unpaired_penalty, rescue_anchors, match,
+                             mismatch, gap, end_bonus, min_aln_score, d_n_maps, d_map_off=None, d_maps=None, d_sel=None, d_pos=None, d_insert=None,
+                             stream=None, slot=0):
+        """dev_pair_select in the clipped mode: 40-byte MAP_CLIP_DTYPE records in d_cands, d_resc and d_maps, unpaired_penalty in score units"""
+        _check(self._L.awry_dev_pair_select_clip(self._h, slot, d_cand_off, d_cands, d_resc, d_read_status, n_pairs, int(min_insert), int(max_insert),
+                                                 int(unpaired_penalty), int(rescue_anchors), int(match), int(mismatch), int(gap), int(end_bonus),
+                                                 int(min_aln_score), d_n_maps, d_map_off, d_maps, d_sel, d_pos, d_insert, stream))
 
     def debug_rank_all(self, rows: np.ndarray, slot=0) -> np.ndarray:
         """Occ of every non-sentinel symbol at each row through the kernels' all-symbol rank -> uint64[len(rows), S]

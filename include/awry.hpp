@@ -496,10 +496,9 @@ class FmIndex {
     std::vector<Mapping> mate1, mate2;  // none or one each
     uint32_t insert;
   };
+  // reads1[p], reads2[p], reads1[p + 1], ..: the interleaved batch of the pair calls
   template <class StrRange>
-  std::vector<PairMapping> parallel_map_pairs(const StrRange& reads1, const StrRange& reads2, uint32_t min_len = 12, uint64_t max_hits = 50,
-                                              uint64_t chains_per_strand = 4, uint32_t band = 4, PairParams pp = PairParams(),
-                                              ChainParams p = ChainParams(), std::vector<uint8_t>* status = nullptr) {
+  static std::vector<std::string_view> interleave(const StrRange& reads1, const StrRange& reads2) {
     std::vector<std::string_view> inter;
     auto b = std::begin(reads2);
     for (const auto& q : reads1) {
@@ -509,8 +508,14 @@ class FmIndex {
       ++b;
     }
     if (b != std::end(reads2)) throw std::invalid_argument("reads1 and reads2 must have one read per pair each");
+    return inter;
+  }
+  template <class StrRange>
+  std::vector<PairMapping> parallel_map_pairs(const StrRange& reads1, const StrRange& reads2, uint32_t min_len = 12, uint64_t max_hits = 50,
+                                              uint64_t chains_per_strand = 4, uint32_t band = 4, PairParams pp = PairParams(),
+                                              ChainParams p = ChainParams(), std::vector<uint8_t>* status = nullptr) {
     std::vector<uint8_t> bytes; std::vector<uint64_t> off;
-    pack(inter, bytes, off);
+    pack(interleave(reads1, reads2), bytes, off);
     const uint64_t n = off.size() - 1;
     uint64_t* moff = nullptr; awry_map_t* mp = nullptr; awry_pos_t* ps = nullptr; uint64_t* coff = nullptr; uint32_t* cg = nullptr; uint8_t* st = nullptr;
     uint32_t* ins = nullptr;
@@ -523,6 +528,44 @@ class FmIndex {
       for (uint64_t j = moff[i]; j < moff[i + 1]; j++)
         to.push_back({ps[j], mp[j].t_begin, mp[j].t_end, mp[j].edits, mp[j].chain_score, mp[j].chain_index, mp[j].strand, mp[j].mapq, mp[j].flags,
                       std::vector<uint32_t>(cg + coff[j], cg + coff[j + 1])});
+      if (i % 2) out[i / 2].insert = ins[i / 2];
+    }
+    if (status) status->assign(st, st + n);
+    awry_free_buffer(moff); awry_free_buffer(mp); awry_free_buffer(ps); awry_free_buffer(coff); awry_free_buffer(cg); awry_free_buffer(st);
+    awry_free_buffer(ins);
+    return out;
+  }
+  // The clipped mode of parallel_map_pairs (the definition is in awry_hip.h, "map read pairs, clipped"): the mates' candidates are
+  // parallel_map_clip's, the insert is measured between the mates' 5' ends projected through their clips (map.t_begin - map.clip_left
+  // of the forward mate to map.t_end + map.clip_right of the reverse one), so a fragment shorter than the reads comes out proper with
+  // its own length as insert; pp.unpaired_penalty is in score units here (0 .. AWRY_PAIR_CLIP_MAX_UNPAIRED), the best pair has the
+  // largest score + score - penalty, and a rescued mate is a whole-read alignment with score >= c.min_aln_score.
+  struct ClippedPairMapping {
+    std::vector<ClippedMapping> mate1, mate2;  // none or one each
+    uint32_t insert;
+  };
+  static PairParams clipped_pair_defaults() {
+    PairParams pp;
+    pp.unpaired_penalty = 20;
+    return pp;
+  }
+  template <class StrRange>
+  std::vector<ClippedPairMapping> parallel_map_pairs_clip(const StrRange& reads1, const StrRange& reads2, uint32_t min_len = 12, uint64_t max_hits = 50,
+                                                          uint64_t chains_per_strand = 4, uint32_t band = 4, PairParams pp = clipped_pair_defaults(),
+                                                          ClipParams c = ClipParams(), ChainParams p = ChainParams(),
+                                                          std::vector<uint8_t>* status = nullptr) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(interleave(reads1, reads2), bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* moff = nullptr; awry_map_clip_t* mp = nullptr; awry_pos_t* ps = nullptr; uint64_t* coff = nullptr; uint32_t* cg = nullptr; uint8_t* st = nullptr;
+    uint32_t* ins = nullptr;
+    check(awry_map_pairs_clip_batch(h_, bytes.data(), off.data(), n, min_len, max_hits, p.max_seeds, p.lookback, p.max_gap, p.max_skew, p.min_score,
+                                    chains_per_strand, band, pp.min_insert, pp.max_insert, pp.unpaired_penalty, pp.rescue_anchors, pp.rescue_edits, c.match,
+                                    c.mismatch, c.gap, c.end_bonus, c.min_aln_score, &moff, &mp, &ps, &coff, &cg, &st, &ins));
+    std::vector<ClippedPairMapping> out(n / 2);
+    for (uint64_t i = 0; i < n; i++) {
+      std::vector<ClippedMapping>& to = i % 2 ? out[i / 2].mate2 : out[i / 2].mate1;
+      for (uint64_t j = moff[i]; j < moff[i + 1]; j++) to.push_back({ps[j], mp[j], std::vector<uint32_t>(cg + coff[j], cg + coff[j + 1])});
       if (i % 2) out[i / 2].insert = ins[i / 2];
     }
     if (status) status->assign(st, st + n);

@@ -546,7 +546,7 @@ int awry_map_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qof
  *
  * awry_align_chains_clip_batch and awry_map_clip_batch mirror awry_align_chains_batch and awry_map_batch: the same arguments plus the
  * scalars above, the same CSR output with the clipped records, the same errors and index restrictions.  awry_map_pairs_batch is
- * untouched: pairing clipped records is a later change. */
+ * untouched: pairing clipped records is a later change, awry_map_pairs_clip_batch of "map read pairs, clipped" below. */
 enum { AWRY_CLIP_MAX_MATCH = 16, AWRY_CLIP_MAX_PENALTY = 64, AWRY_CLIP_MAX_END_BONUS = 1024 };
 enum { AWRY_CIGAR_SOFT_CLIP = 4 };
 typedef struct { uint64_t t_begin, t_end; uint32_t edits, status; int32_t score; uint16_t clip_left, clip_right; } awry_aln_clip_t;
@@ -619,6 +619,54 @@ int awry_map_pairs_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_
                          uint32_t unpaired_penalty, uint32_t rescue_anchors, int rescue_edits, uint64_t **map_off_out,
                          awry_map_t **maps_out, awry_pos_t **pos_out, uint64_t **cigar_off_out, uint32_t **cigar_out,
                          uint8_t **status_out, uint32_t **insert_out);
+
+/* ---- map read pairs, clipped: clipped pairing and rescue (no counterpart in the reference) ------------------------------
+ * The clipped mode of "map read pairs", beside the end-to-end one.  A fragment shorter than the reads makes both mates read through
+ * into the adapter: mate 0 is I genomic letters and then L - I adapter letters, rc(mate 1) the same I letters after L - I adapter
+ * letters.  End to end both alignments run through the adapter, the forward record ends after the reverse one and begins after it,
+ * and the pair that is easiest to place comes out improper.  Here the kept lists are those of "soft-clip read ends", both mates
+ * align to the fragment, and the insert is measured between the mates' 5' ends projected through their clips.  No other entry point
+ * changes its output.  All arithmetic is signed integer and every tie is broken explicitly.
+ * Parameters.  Those of awry_map_pairs_batch and, after rescue_edits, the five clip scalars of awry_map_clip_batch: match = a,
+ *   mismatch = b, gap = g, end_bonus = E, min_aln_score = T, with the same ranges and the same AWRY_ERR_ARG.  unpaired_penalty = U is
+ *   in score units here, 0 .. AWRY_PAIR_CLIP_MAX_UNPAIRED = 16384: the largest score a read of AWRY_CHAIN_ALIGN_MAX_LEN letters can
+ *   reach at a = 16.
+ * Kept lists.  K_m is what awry_map_clip_batch would report for mate m at max_report = 2 A: awry_map_clip_t records in that
+ *   section's rank order, the threshold T applied, at most 16 entries.  Each read's status is the one awry_map_clip_batch gives.
+ * Fragment ends.  For a record x on strand 0, fb(x) = x.t_begin - x.clip_left; for a record on strand 1, ve(x) = x.t_end +
+ *   x.clip_right: the 5' ends of the two mates projected through their clips.  Reverse-strand clips are those computed on rc(read), so
+ *   clip_left is always the text-left side.  Either value may lie outside the record or below 0; they are used only in differences.
+ * Proper.  f the record on strand 0, v the one on strand 1.  proper_clip(x, y) iff the strands differ and rec(f.t_begin) ==
+ *   rec(v.t_begin) and f.t_begin <= v.t_begin and f.t_end <= v.t_end (on the aligned spans, as end to end) and min_insert <= ve(v) -
+ *   fb(f) <= max_insert.  The insert is ve(v) - fb(f).  With all clips 0 this is proper of the end-to-end section, to the letter.
+ * Rescue.  The anchor rule is unchanged, with proper_clip in place of proper.  The windows: x on strand 0: lo = max(x.t_begin, fb(x)
+ *   + min_insert - L' - k), hi = fb(x) + max_insert - L' + k; x on strand 1: lo = ve(x) - max_insert, hi = min(x.t_begin, ve(x) -
+ *   min_insert); cut to the text and to the record of x.t_begin as there.  Scan and aligner are the existing ones: a rescue hit is a
+ *   whole-mate alignment within k edits, exactly as in awry_map_pairs_batch.  The rescued candidate z additionally carries score = a
+ *   #'=' - b #'X' - g (#'I' + #'D') of the aligner's runs and clip_left = clip_right = 0, and exists only if score >= T.  A mate
+ *   whose junk tail exceeds k edits is therefore not rescuable: a stated limit (scored local rescue is a later change).
+ * Augmented lists.  As end to end; the span-intersection test uses the aligned spans.
+ * Pair choice.  S(x, y) = x.score + y.score - (proper_clip(x, y) ? 0 : U).  The pairs are ordered ascending by (-S, !proper, index
+ *   of x in K'_0, index of y in K'_1).  Pair MAPQ: 0 if either read's status is AWRY_Q_SEED_CAP; else 60 if there is no second pair;
+ *   else min(60, 10 (S1 - S2) / (a + b)) with floor division.
+ * Records.  At most one awry_map_clip_t per read, with the flags of the end-to-end section.  Exactly one mate with candidates: its
+ *   record is the primary of awry_map_clip_batch plus AWRY_MAP_MATE_UNMAPPED.  insert[p] = ve(v) - fb(f) for a proper best pair,
+ *   else 0.  The runs of a chain-derived record are the clipped aligner's ('S' runs included), those of a rescued record the edit
+ *   aligner's.
+ * Properties.  (1) Replaying a record's CIGAR over the read (rc(read) on strand 1) and T[t_begin .. t_end) reproduces edits, score
+ *   and both clips; rescued records too.  (2) If every record of both lists has clips 0, the windows and proper_clip are those of
+ *   the end-to-end section.  (3) A proper best pair has min_insert <= insert[p] <= max_insert.
+ *
+ * awry_map_pairs_clip_batch: awry_map_pairs_batch's arguments with the five scalars after rescue_edits, the same CSR output with
+ * awry_map_clip_t records, the same errors, index restrictions and invariances. */
+enum { AWRY_PAIR_CLIP_MAX_UNPAIRED = 16384 };
+int awry_map_pairs_clip_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len,
+                              uint64_t max_hits, uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew,
+                              uint32_t min_score, uint64_t chains_per_strand, uint32_t band, uint64_t min_insert,
+                              uint64_t max_insert, uint32_t unpaired_penalty, uint32_t rescue_anchors, int rescue_edits,
+                              uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus, uint32_t min_aln_score,
+                              uint64_t **map_off_out, awry_map_clip_t **maps_out, awry_pos_t **pos_out, uint64_t **cigar_off_out,
+                              uint32_t **cigar_out, uint8_t **status_out, uint32_t **insert_out);
 
 /* releases an array one of the calls above (or awry_locate / awry_read_query_file) returned.  Result arrays are pinned
  * host memory recycled through a process-wide pool (the device writes results straight into them); never pass them to
@@ -916,6 +964,20 @@ int awry_dev_pair_select(awry_index_t *idx, int slot, const uint64_t *d_cand_off
                          const uint8_t *d_read_status, uint64_t n_pairs, uint64_t min_insert, uint64_t max_insert,
                          uint32_t unpaired_penalty, uint32_t rescue_anchors, uint64_t *d_n_maps, const uint64_t *d_map_off,
                          awry_map_t *d_maps, uint32_t *d_sel, awry_pos_t *d_pos, uint32_t *d_insert, void *stream);
+/* The clipped modes of awry_dev_pair_windows and awry_dev_pair_select ("map read pairs, clipped"): the same arguments and protocol
+ * over awry_map_clip_t, d_resc included (a slot without a candidate: edits == 0xFFFFFFFF).  The windows are measured from fb and ve;
+ * the select takes unpaired_penalty in score units and the five clip scalars after rescue_anchors (all are checked; MAPQ divides by
+ * match + mismatch; the others play no part in the choice: the rescued records come with their scores). */
+int awry_dev_pair_windows_clip(awry_index_t *idx, int slot, const uint64_t *d_cand_off, const awry_map_clip_t *d_cands,
+                               const uint64_t *d_qoff, uint64_t n_pairs, uint64_t min_insert, uint64_t max_insert,
+                               uint32_t rescue_anchors, int rescue_edits, uint32_t *d_win_query, uint64_t *d_win_first,
+                               uint32_t *d_win_count, void *stream);
+int awry_dev_pair_select_clip(awry_index_t *idx, int slot, const uint64_t *d_cand_off, const awry_map_clip_t *d_cands,
+                              const awry_map_clip_t *d_resc, const uint8_t *d_read_status, uint64_t n_pairs, uint64_t min_insert,
+                              uint64_t max_insert, uint32_t unpaired_penalty, uint32_t rescue_anchors, uint32_t match,
+                              uint32_t mismatch, uint32_t gap, uint32_t end_bonus, uint32_t min_aln_score, uint64_t *d_n_maps,
+                              const uint64_t *d_map_off, awry_map_clip_t *d_maps, uint32_t *d_sel, awry_pos_t *d_pos,
+                              uint32_t *d_insert, void *stream);
 /* test hook of the all-symbol rank primitive: d_occ[i * S + s - 1] = Occ(s, d_rows[i]) for every non-sentinel symbol index s
  * (S = 5 nucleotide, 21 amino; inclusive of the row, as awry_update_range uses it); rows >= bwt_len give zeros */
 int awry_debug_rank_all(awry_index_t *idx, int slot, const void *d_rows, uint64_t n, void *d_occ, void *stream);

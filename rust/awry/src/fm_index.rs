@@ -15,7 +15,7 @@ use std::os::raw::c_char;
 use std::path::{Path, PathBuf};
 use std::sync::Arc;
 
-use awry_hip_sys::{self as sys, awry_aln_t as RawAln, awry_anchor_t as RawAnchor, awry_chain_t as RawChain, awry_map_t as RawMap, awry_pos_t as RawPos,
+use awry_hip_sys::{self as sys, awry_aln_t as RawAln, awry_anchor_t as RawAnchor, awry_chain_t as RawChain, awry_map_clip_t as RawMapClip, awry_map_t as RawMap, awry_pos_t as RawPos,
                    awry_seed_t as RawSeed};
 use rayon::iter::{IndexedParallelIterator, IntoParallelIterator, IntoParallelRefIterator, ParallelIterator};
 
@@ -274,6 +274,33 @@ pub struct Mapping {
     pub mapq: u8,
     pub flags: u16,
     pub cigar: Vec<u32>,
+}
+
+/// The five scalars of the clipped mode (include/awry_hip.h, "soft-clip read ends"): `match_score` 1..=16 per '=', `mismatch` and `gap`
+/// 0..=64 per 'X' and per inserted or deleted letter, `end_bonus` 0..=1024, `min_aln_score` the lowest score a candidate may have.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct ClipParams {
+    pub match_score: u32,
+    pub mismatch: u32,
+    pub gap: u32,
+    pub end_bonus: u32,
+    pub min_aln_score: u32,
+}
+
+impl Default for ClipParams {
+    fn default() -> Self {
+        ClipParams { match_score: 1, mismatch: 4, gap: 6, end_bonus: 5, min_aln_score: 0 }
+    }
+}
+
+/// One record of [`FmIndex::parallel_map_pairs_clip`]: a [`Mapping`] whose span is the aligned part of the read, with the
+/// alignment's score and the letters soft-clipped at either end (of the read's reverse complement on strand 1; 'S' runs in `cigar`).
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct ClippedMapping {
+    pub mapping: Mapping,
+    pub score: i32,
+    pub clip_left: u16,
+    pub clip_right: u16,
 }
 
 /// The CIGAR string of the runs [`FmIndex::parallel_align_edit`] returns (`len << 4 | op`, BAM's op codes): `"57=1X43="`.
@@ -849,6 +876,84 @@ impl FmIndex {
                     mapq: mp[j].mapq,
                     flags: mp[j].flags,
                     cigar: runs[coff[j] as usize..coff[j + 1] as usize].to_vec(),
+                })
+            };
+            let per = (0..n / 2).map(|p| (record(2 * p), record(2 * p + 1), inserts[p])).collect::<Vec<_>>();
+            (per, status.iter().map(|&s| s == 8).collect::<Vec<_>>())  // AWRY_Q_SEED_CAP
+        };
+        unsafe {
+            sys::awry_free_buffer(map_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(maps as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(pos as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(cigar_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(cigar as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(st as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(ins as *mut std::os::raw::c_void);
+        }
+        Ok(out)
+    }
+
+    /// [`FmIndex::parallel_map_pairs`] in the clipped mode (include/awry_hip.h, "map read pairs, clipped"): the mates' candidates are
+    /// clipped alignments, the insert is measured between the mates' 5' ends projected through their clips, so a fragment shorter than
+    /// the reads comes out proper with its own length as insert; `pair.unpaired_penalty` is in score units here (0..=16384,
+    /// `AWRY_PAIR_CLIP_MAX_UNPAIRED`), and a rescued mate is a whole-read alignment with score >= `clip.min_aln_score`.
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn parallel_map_pairs_clip(
+        &self,
+        reads1: &[&str],
+        reads2: &[&str],
+        min_len: u32,
+        max_hits: u64,
+        chains_per_strand: u64,
+        band: u32,
+        pair: PairParams,
+        clip: ClipParams,
+        params: ChainParams,
+    ) -> Result<(Vec<(Option<ClippedMapping>, Option<ClippedMapping>, u32)>, Vec<bool>), AwryError> {
+        assert_eq!(reads1.len(), reads2.len(), "reads1 and reads2 must have one read per pair each");
+        let inter: Vec<&str> = reads1.iter().zip(reads2.iter()).flat_map(|(a, b)| [*a, *b]).collect();
+        let csr = to_csr(inter.into_par_iter());
+        let n = csr.offsets.len() - 1;
+        let mut map_off: *mut u64 = std::ptr::null_mut();
+        let mut maps: *mut RawMapClip = std::ptr::null_mut();
+        let mut pos: *mut RawPos = std::ptr::null_mut();
+        let mut cigar_off: *mut u64 = std::ptr::null_mut();
+        let mut cigar: *mut u32 = std::ptr::null_mut();
+        let mut st: *mut u8 = std::ptr::null_mut();
+        let mut ins: *mut u32 = std::ptr::null_mut();
+        check(unsafe {
+            sys::awry_map_pairs_clip_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, min_len, max_hits, params.max_seeds,
+                                           params.lookback, params.max_gap, params.max_skew, params.min_score, chains_per_strand, band, pair.min_insert,
+                                           pair.max_insert, pair.unpaired_penalty, pair.rescue_anchors, pair.rescue_edits, clip.match_score, clip.mismatch,
+                                           clip.gap, clip.end_bonus, clip.min_aln_score, &mut map_off, &mut maps, &mut pos, &mut cigar_off, &mut cigar,
+                                           &mut st, &mut ins)
+        })?;
+        let out = unsafe {
+            let off = std::slice::from_raw_parts(map_off, n + 1);
+            let total = off[n] as usize;
+            let mp: &[RawMapClip] = if total == 0 { &[] } else { std::slice::from_raw_parts(maps, total) };
+            let ps: &[RawPos] = if total == 0 { &[] } else { std::slice::from_raw_parts(pos, total) };
+            let coff = std::slice::from_raw_parts(cigar_off, total + 1);
+            let runs: &[u32] = if coff[total] == 0 { &[] } else { std::slice::from_raw_parts(cigar, coff[total] as usize) };
+            let status: &[u8] = if n == 0 { &[] } else { std::slice::from_raw_parts(st, n) };
+            let inserts: &[u32] = if n == 0 { &[] } else { std::slice::from_raw_parts(ins, n / 2) };
+            let record = |i: usize| {
+                (off[i] as usize..off[i + 1] as usize).next().map(|j| ClippedMapping {
+                    mapping: Mapping {
+                        position: LocalizedSequencePosition::new(ps[j].seq_idx as usize, ps[j].local_pos as usize),
+                        t_begin: mp[j].t_begin,
+                        t_end: mp[j].t_end,
+                        edits: mp[j].edits,
+                        chain_score: mp[j].chain_score,
+                        chain_index: mp[j].chain_index,
+                        strand: mp[j].strand,
+                        mapq: mp[j].mapq,
+                        flags: mp[j].flags,
+                        cigar: runs[coff[j] as usize..coff[j + 1] as usize].to_vec(),
+                    },
+                    score: mp[j].score,
+                    clip_left: mp[j].clip_left,
+                    clip_right: mp[j].clip_right,
                 })
             };
             let per = (0..n / 2).map(|p| (record(2 * p), record(2 * p + 1), inserts[p])).collect::<Vec<_>>();

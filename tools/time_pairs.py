@@ -16,7 +16,12 @@ The public scan and aligner primitives run at their widest (4 words per column w
 driver runs them at the chunk's longest rescuable read (2 words, masks per query, 96 rows here), so the two rescue stages are upper
 bounds of what the driver pays.  And the rate of awry_map_pairs_batch across the host boundary next to awry_map_batch on the same
 reads (one warmed call each on a part of the pairs).
-usage: time_pairs.py [text_len] [n_pairs]   -> one JSON object on stdout (profiles/pair_rates.json)"""
+The clipped leg (host_legs): awry_map_pairs_clip_batch next to awry_map_pairs_batch across the host boundary on the same reads, 7
+alternating repetitions of one call each after a warming call, median and spread of the wall time; the yardstick is the end-to-end
+call of the same library.  --host-only runs nothing but this leg; --end-to-end-only leaves the clipped call out of it (for a
+library from before the clipped mode).
+usage: time_pairs.py [text_len] [n_pairs] [--host-only] [--end-to-end-only]
+       -> one JSON object on stdout (profiles/pair_rates.json; the clipped leg alone: profiles/pair_clip_rates.json)"""
 import json
 import os
 import sys
@@ -25,15 +30,20 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
+ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
+HOST_ONLY, E2E_ONLY = "--host-only" in sys.argv, "--end-to-end-only" in sys.argv
+sys.argv = sys.argv[:1] + ARGS  # (tools/time_map.py reads its sizes from the same positions when it is imported)
+
 import awry_amd
 from tests import synth
 from tools import time_map as tm
 from tools.read_sets import plant
 
-n = int(float(sys.argv[1])) if len(sys.argv) > 1 else 250_000_000
-n_pairs = int(float(sys.argv[2])) if len(sys.argv) > 2 else 500_000
+n = int(float(ARGS[0])) if len(ARGS) > 0 else 250_000_000
+n_pairs = int(float(ARGS[1])) if len(ARGS) > 1 else 500_000
 L, A, BAND, MIN_LEN, MAX_HITS = 96, tm.A, tm.BAND, tm.MIN_LEN, tm.MAX_HITS
 MN, MX, U, G, K, SUB = 0, 1000, 4, 2, 8, 64
+CLIP, U_CLIP = (1, 4, 6, 5, 30), 20  # match, mismatch, gap, end_bonus, min_aln_score; the penalty in score units: U (a + b)
 PARAMS = tm.PARAMS["short"]
 dev, stream, i64 = tm.dev, tm.stream, tm.i64
 i32 = dict(dtype=torch.int32, device=dev)
@@ -67,6 +77,34 @@ def simulated_pairs(text_d, P, seed):
     return q, int(hard.sum().item())
 
 
+def host_legs(ix, q, nb, pv, clipped=True):
+    """wall time of the batch calls on the first nb pairs of q, positions and CIGARs included -> the clipped leg's JSON object"""
+    qb = q[:2 * nb].reshape(-1).cpu().numpy()
+    qo = (torch.arange(2 * nb + 1, dtype=torch.int64) * L).numpy().astype("uint64")
+    legs = {"end_to_end": lambda: ix.parallel_map_pairs_csr(qb, qo, MIN_LEN, MAX_HITS, A, BAND, MN, MX, U, G, K, *pv)}
+    if clipped:
+        legs["clipped"] = lambda: ix.parallel_map_pairs_clip_csr(qb, qo, MIN_LEN, MAX_HITS, A, BAND, MN, MX, U_CLIP, G, K, *CLIP, *pv)
+    res = {k: fn() for k, fn in legs.items()}  # the warming call, and what the legs return
+    s = {k: [] for k in legs}
+    for _ in range(7):
+        for k, fn in legs.items():
+            t = time.time()
+            fn()
+            s[k].append(time.time() - t)
+    out = {"n_pairs": nb, "read_len": L, "timing": "wall time of one batch call, 7 alternating repetitions after a warming call: median and spread ((max - min) / median)",
+           "unpaired_penalty_clipped": U_CLIP, "match_mismatch_gap_end_bonus_min_aln_score": list(CLIP)}
+    for k, v in s.items():
+        r, med = res[k], sorted(v)[3]
+        out[k] = {"seconds": sorted(v), "median_seconds": med, "spread": (max(v) - min(v)) / med, "pairs_per_s": nb / med, "records": int(r[0][-1]),
+                  "records_proper": int(((r[1]["flags"] & 2) != 0).sum()), "records_rescued": int(((r[1]["flags"] & 4) != 0).sum()),
+                  "records_mate_unmapped": int(((r[1]["flags"] & 8) != 0).sum())}
+    if clipped:
+        c = res["clipped"][1]
+        out["clipped"]["records_with_a_clip"] = int(((c["clip_left"] != 0) | (c["clip_right"] != 0)).sum())
+        out["clipped_seconds_over_end_to_end_seconds"] = out["clipped"]["median_seconds"] / out["end_to_end"]["median_seconds"]
+    return out
+
+
 def main():
     t = time.time()
     text, starts, headers, info = synth.repeat_rich_text(n, 11, 25, device="cuda")
@@ -78,6 +116,14 @@ def main():
     q, n_hard = simulated_pairs(text_d, P, 909)
     del text_d
     nq = 2 * P
+    if HOST_ONLY:
+        p = PARAMS
+        pv = (p["max_seeds"], p["lookback"], p["max_gap"], p["max_skew"], p["min_score"])
+        print(json.dumps({"text": "synth.repeat_rich_text(%d, 11, 25)" % n, "text_len": n, "min_len": MIN_LEN, "max_hits": MAX_HITS, "band": BAND,
+                          "chains_per_strand": A, "min_insert": MN, "max_insert": MX, "unpaired_penalty": U, "rescue_anchors": G, "rescue_edits": K,
+                          "params": PARAMS, "seed_k": ix.seed_kmer_len(), "pairs_with_an_unseedable_mate": n_hard,
+                          "clipped_leg": host_legs(ix, q, min(P, 100_000), pv, not E2E_ONLY)}))
+        return
 
     def once(fn):
         for _ in range(2):
@@ -284,6 +330,7 @@ def main():
     dt1 = time.time() - t
     out["host_boundary"] = {"n_pairs": nb, "map_pairs_batch_seconds": dt, "pairs_per_s": nb / dt, "records": int(r[0][-1]),
                             "records_rescued": int(((r[1]["flags"] & 4) != 0).sum()), "map_batch_seconds_same_reads": dt1, "records_single_end": int(r1[0][-1])}
+    out["clipped_leg"] = host_legs(ix, q, nb, pv, not E2E_ONLY)
     print(json.dumps(out))
 
 
