@@ -125,6 +125,9 @@ void launch_scan(Replica& r, const uint64_t* d_counts, uint64_t n, uint64_t* d_h
 void launch_locate(Replica& r, const uint64_t* d_range_start, int rs_stride, const uint64_t* d_hit_off, uint64_t n, uint64_t total,
                    uint64_t* d_gpos, uint64_t* d_pos, hipStream_t s, unsigned long long* d_tally = nullptr) {
   if (total == 0) return;
+  // from the first head to the last kernel queued: a head's memset and the kernel that draws from it stay next to each other
+  // on the stream when two host threads drive it (next_counter, replica.h)
+  const ScratchLock scratch_lock(r, s);
   unsigned long long* ctr = next_counter(r, s);
   const uint64_t tiles = (total + LOC_TILE - 1) / LOC_TILE;
   const dim3 g((unsigned)std::min<uint64_t>(tiles, bound_blocks((uint64_t)r.num_cus * 8))), b(256);
@@ -404,8 +407,8 @@ void launch_count_leaves(Replica& r, bool classes, const uint8_t* d_q, const uin
                          uint64_t* d_totals, uint64_t* d_nleaves, uint8_t* d_status, hipStream_t s, unsigned long long* d_tally = nullptr,
                          const uint64_t* d_leaf_off = nullptr, uint64_t* d_key = nullptr, uint64_t* d_val = nullptr) {
   if (n == 0) return;
-  std::optional<ScratchLock> scratch_lock;  // the workspace is the class mode's: the letter mode touches no scratch
-  if (classes) scratch_lock.emplace(r, s);
+  // the class mode's workspace, and in both modes the work-queue head: its memset and the kernel are queued as one step
+  const ScratchLock scratch_lock(r, s);
   unsigned long long* ctr = next_counter(r, s);
   const bool emit = d_leaf_off != nullptr;
   const uint64_t want = (n + 255) / 256, max_exp = classes ? pattern_max_expansions() : 0;

@@ -252,6 +252,9 @@ struct ScratchLock {
   ScratchLock(Replica& r, hipStream_t s) : lk(surv_scratch(r, s)->mu) {}
 };
 
+// The next head of the stream's ring of 8, zeroed by a memset queued on the stream.  The caller holds the stream's ScratchLock
+// from here until the kernel that draws from the head is queued: otherwise a second host thread on the stream could take 8 heads
+// in between, and two kernels would be queued behind both memsets of one head -- the second starts from the count the first left.
 unsigned long long* next_counter(Replica& r, hipStream_t s) {
   Replica::SurvScratch* sc = surv_scratch(r, s);
   unsigned long long* ctr;

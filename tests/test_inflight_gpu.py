@@ -10,7 +10,13 @@ Every expected array comes from the CPU oracle (or from tests/mismatch_ref.py, w
 and is computed before anything is queued; no GPU result serves as the reference for another.  All comparisons are
 bit-exact.  Every stream carries different data and every output buffer is pre-filled with a sentinel, so a list shared
 between two streams, a list sized from the wrong launch, a head reused too early or a buffer that grew under a queued launch
-changes an answer."""
+changes an answer.
+
+This module covers the count, locate and mismatch families.  tests/test_inflight_reads_gpu.py does the same, under the same rules
+and behind this module's long first launch, for the read pipelines -- anchors, SMEMs, edit locate and align, chaining, chain
+alignment, map, pairs and the clipped modes: every device entry point on four streams, the workspaces edit_masks, align_trace,
+chain_slabs and chain_align_lists growing and changing owner with work queued, twelve host threads inside the batch calls, the
+first use of the edit scan's private text copy under load, and one stream driven by two host threads."""
 import os
 import subprocess
 import sys
