@@ -220,6 +220,9 @@ def load_library():
     sig("awry_set_lcx", i32, vp, i32)
     sig("awry_lcx_enabled", i32, vp)
     sig("awry_debug_lcx", i32, vp, i32, vpp, vpp)
+    sig("awry_set_kmer_table", i32, vp, i32)
+    sig("awry_kmer_table_info", i32, vp, i32, u64p)
+    sig("awry_debug_set_kmer_table_lines", i32, u64)
     sig("awry_dev_stream_copy", i32, vp, i32, vp, vp, u64, vp)
     sig("awry_dev_malloc", i32, vp, i32, u64, vpp)
     sig("awry_dev_free", i32, vp, i32, vp)

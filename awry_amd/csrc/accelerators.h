@@ -106,7 +106,96 @@ const SeedEntry* seed_rung(Replica& r, int L) {
   return p;
 }
 
+// ---- the k-mer count table (layout.h KT_*, kmer_table.hip.h) ----
+// awry_debug_set_kmer_table_lines: the number of lines of tables built afterwards (rounded down to a power of two), whatever
+// their load; 0 (the default): the policy below.  For tests: a table far too small overflows in most lines, and an L-mer whose
+// tag does not fit beside so few line bits marks its line the same way -- both are searched as without the table.
+std::atomic<uint64_t> g_kt_debug_lines{0};
+
+void drop_kmer_table(Replica& r) {
+  std::unique_lock<std::shared_mutex> lock(r.kt_mu);
+  r.kt.tab.reset();  // (hipFree waits for the kernels that are queued)
+  r.kt = Replica::KmerTable{};
+  r.kt_refused.clear();
+}
+
+// Builds the table for length L in place of the one that is there; the caller holds r.kt_mu exclusively.  Like a rung
+// (seed_rung): on the replica's own stream, synchronous, the table within half of the HBM that is free now (the only build
+// scratch is one counter line), a refused length is remembered, an allocation that fails means "not available".
+void build_kmer_table(Replica& r, int L) {
+  r.kt.tab.reset();
+  r.kt = Replica::KmerTable{};
+  if (r.wide || !r.dev.lcx_key || !r.dev.lcx_rowpos || !r.dev.text4 || !r.dense_sa.p || r.dense_ratio != 1 || !r.seed.p || L <= r.seed_k || L > 32) return;
+  int cur_dev = 0;
+  HIP_CHECK(hipGetDevice(&cur_dev));
+  if (cur_dev != r.device) HIP_CHECK(hipSetDevice(r.device));
+  struct Restore { int dev, mine; ~Restore() { if (dev != mine) (void)hipSetDevice(dev); } } restore{cur_dev, r.device};  // the caller's device
+  const auto t_begin = std::chrono::steady_clock::now();
+  try {
+    DevBuf<unsigned long long> stats(4);
+    unsigned long long h[4] = {0, 0, 0, 0};
+    HIP_CHECK(hipMemsetAsync(stats.p, 0, 32, r.stream));
+    const dim3 g(grid_for(r, r.dev.bwt_len, 256)), b(256);
+    hipLaunchKernelGGL(kt_scan_kernel<false>, g, b, 0, r.stream, r.dev, L, (uint64_t*)nullptr, 0u, stats.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h, stats.p, 32, hipMemcpyDeviceToHost, r.stream));
+    HIP_CHECK(hipStreamSynchronize(r.stream));
+    // lines: at most 8 keys per line on average (then a line of 16 slots overflows once in ~250), a power of two, and so many
+    // that the tag -- the 2L - bits upper bits of the mixed key -- fits its field: for small texts that is the size
+    uint32_t bits = 0;
+    while ((8ull << bits) < h[2]) bits++;
+    while (2 * L - (int)bits > KT_TAG_BITS) bits++;
+    if (const uint64_t forced = g_kt_debug_lines.load()) {
+      bits = 0;
+      while ((2ull << bits) <= forced && bits < 40) bits++;
+    }
+    const uint64_t bytes = 128ull << bits;
+    size_t free_b = 0;
+    if (!hbm_budget(&free_b) || (double)bytes + 4096.0 > 0.5 * (double)free_b) { r.kt_refused.insert(L); return; }
+    DevBuf<uint64_t> tab(16ull << bits);
+    HIP_CHECK(hipMemsetAsync(tab.p, 0, bytes, r.stream));
+    hipLaunchKernelGGL(kt_scan_kernel<true>, g, b, 0, r.stream, r.dev, L, tab.p, bits, stats.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h, stats.p, 32, hipMemcpyDeviceToHost, r.stream));
+    HIP_CHECK(hipStreamSynchronize(r.stream));
+    r.kt.tab = std::move(tab);
+    r.kt.L = L;
+    r.kt.bits = bits;
+    r.kt.entries = h[0];
+    r.kt.overflowed = h[1];
+  } catch (const HipError&) {  // (hipMalloc: the budget was an estimate)
+    (void)hipGetLastError();
+    r.kt.tab.reset();
+    r.kt = Replica::KmerTable{};
+    r.kt_refused.insert(L);
+    return;
+  }
+  r.kt.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  static const bool verbose = getenv("AWRY_VERBOSE") != nullptr;
+  if (verbose) fprintf(stderr, "[awry replica %d] k-mer count table for L = %d: %llu entries in %llu lines (%llu overflowed), %.2f GB, built in %.1f ms\n", r.device, L,
+                       (unsigned long long)r.kt.entries, 1ull << r.kt.bits, (unsigned long long)r.kt.overflowed, (double)(128ull << r.kt.bits) / 1e9, r.kt.build_ms);
+}
+
+// The table of length L for a launch: nullptr when it is not resident and is not to be built (or cannot be).  On success
+// `lock` is held (shared): the caller keeps it until the kernel that takes the pointer is queued.
+const Replica::KmerTable* kmer_table(Replica& r, int L, bool build, std::shared_lock<std::shared_mutex>& lock) {
+  lock = std::shared_lock<std::shared_mutex>(r.kt_mu);
+  if (r.kt.L == L && r.kt.tab.p) return &r.kt;
+  const bool refused = r.kt_refused.count(L) != 0;
+  lock.unlock();
+  if (!build || refused) return nullptr;
+  {
+    std::unique_lock<std::shared_mutex> excl(r.kt_mu);
+    if (!(r.kt.L == L && r.kt.tab.p) && !r.kt_refused.count(L)) build_kmer_table(r, L);
+  }
+  lock.lock();
+  if (r.kt.L == L && r.kt.tab.p) return &r.kt;
+  lock.unlock();
+  return nullptr;
+}
+
 void drop_lcx(Replica& r) {
+  drop_kmer_table(r);  // it is made of the index's keys and the seed table's flags
   r.lcx_key.reset(); r.lcx_rowpos.reset(); r.lcx_inner.reset();
   r.dev.lcx_key = r.dev.lcx_rowpos = r.dev.lcx_inner = nullptr;
   for (auto& o : r.dev.lcx_off) o = 0;
@@ -147,6 +236,7 @@ void build_seed(awry_index* ix, Replica& r, int k) {
 
 // dense device SA for locate: ratio 0 = off (walk to the file's samples), r >= 1 = keep SA[j r] for every j as u32
 void build_dense_sa(awry_index* ix, Replica& r, int ratio) {
+  drop_kmer_table(r);  // (built from the ratio-1 dense SA and the text)
   r.text4.reset();  // the verify shortcut rides on the ratio-1 dense SA; it is re-enabled by build_verify()
   r.text8.reset();
   r.dev.text4 = nullptr;
@@ -196,6 +286,7 @@ void refresh_nblock(awry_index* ix, Replica& r) {
 // codes for the packed nucleotide kernels (text4) and as one symbol index per byte for the generic kernel (text8, any
 // alphabet).  after_steps < 0 switches it off.
 void build_verify(awry_index* ix, Replica& r, int after_steps) {
+  drop_kmer_table(r);
   r.text4.reset();
   r.text8.reset();
   r.dev.text4 = nullptr;
@@ -492,6 +583,7 @@ std::unique_ptr<Replica> make_replica(awry_index* ix, int device) {
   if (vreq >= 0) build_verify(ix, *r, vreq);
   lap("verify accelerators (dense SA at ratio 1, text)");
   r->verify_kmers = ix->verify_kmers_request;
+  r->kt_mode = ix->kmer_table_request;
   refresh_nblock(ix, *r);
   sync_seed_mode(ix, *r);
   lap("block-of-sample table, seed mode");

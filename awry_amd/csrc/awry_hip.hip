@@ -295,6 +295,8 @@ const char* awry_count_schedule(const awry_index_t* idx, int L) {
     return "count_nt2_probe_resume_kernel (table of its own for this length; batches of 4096 queries and more)";
   int m = count_kernel_mode(r.dev.bwt_len, r.seed_k, seeded);
   if (m >= 3 && m <= 5 && !seeded) m = 2;
+  if (m == 3 && L > r.seed_k && r.dev.lcx_key && r.dev.text4 && r.dev.dense_ratio == 1 && (r.kt_mode == 1 || (r.kt_mode < 0 && count_kernel_override() < 0)))
+    return "count_nt2_probe_resume_kernel (k-mer count table of this length: on first use with awry_set_kmer_table(1), else for batches of 65536 queries and more)";
   return names[m >= 0 && m <= 5 ? m : 0];  // (other modes launch the strided quads)
 }
 
@@ -890,6 +892,33 @@ int awry_set_lcx(awry_index_t* idx, int on) {
   });
 }
 int awry_lcx_enabled(const awry_index_t* idx) { return idx && !idx->reps.empty() && idx->reps[0]->dev.lcx_key != nullptr; }
+int awry_set_kmer_table(awry_index_t* idx, int mode) {
+  return guarded([&] {
+    require(idx != nullptr, "null index");
+    require(mode >= -1 && mode <= 1, "k-mer table mode must be -1 (policy), 0 (off) or 1 (build for the next length)");
+    idx->kmer_table_request = mode;
+    for (size_t s = 0; s < idx->reps.size(); s++) {
+      Replica& r = replica(idx, (int)s);
+      r.kt_mode = mode;
+      if (mode == 0) drop_kmer_table(r);
+    }
+  });
+}
+int awry_kmer_table_info(awry_index_t* idx, int slot, uint64_t* info) {
+  return guarded([&] {
+    require(idx != nullptr && info != nullptr, "null argument");
+    Replica& r = replica(idx, slot);
+    std::shared_lock<std::shared_mutex> lock(r.kt_mu);
+    const bool have = r.kt.tab.p != nullptr;
+    info[0] = have ? (uint64_t)r.kt.L : 0;
+    info[1] = r.kt.entries;
+    info[2] = have ? 1ull << r.kt.bits : 0;
+    info[3] = r.kt.overflowed;
+    info[4] = have ? 128ull << r.kt.bits : 0;
+    info[5] = (uint64_t)(r.kt.build_ms * 1000.0);
+  });
+}
+int awry_debug_set_kmer_table_lines(uint64_t lines) { g_kt_debug_lines.store(lines); return AWRY_OK; }
 int awry_debug_lcx(const awry_index_t* idx, int slot, const void** d_keys, const void** d_rowpos) {
   if (!idx || slot < 0 || slot >= (int)idx->reps.size() || !d_keys || !d_rowpos) return AWRY_ERR_ARG;
   *d_keys = idx->reps[slot]->lcx_key.p;

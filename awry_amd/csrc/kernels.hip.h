@@ -67,7 +67,8 @@
 //                         LOCATE_WALK_KERNEL<AMINO>          generic walk, the amino indexes' second pass [this file]
 //   accelerators          seed_level1/extend<Entry>, seed_finalize, seed64_finalize (+aa_seed_*), seed_rows_to_positions_kernel [kernels_seed];
 //                         densify_sa_kernel, nblock_sa_kernel, text4_scatter_kernel, text8_scatter_kernel [this file];
-//                         text8_chains_kernel (the text without the dense SA, for the edit scan) [edit_kernels]
+//                         text8_chains_kernel (the text without the dense SA, for the edit scan) [edit_kernels];
+//                         kt_scan_kernel<INSERT> (the k-mer count table of one query length, from the left-context index) [kmer_table]
 //   glue                  pack_nt2_tile_kernel<R> [kernels_pack]; scan_*_kernel, stream_copy_kernel, phase_marker_kernel,
 //                         narrow_counts_kernel, status_first_bad_kernel [kernels_scan]; ref_kmer_table_kernel, scalar_ops_kernel [kernels_count]
 //   device helpers        scalar rank / step / backstep, ByteStream, text_equals_query [kernels_rank]; wave / block scans [kernels_scan];
@@ -89,6 +90,7 @@
 #include "kernels_quad.hip.h"      // slice_mask
 #include "lcx.hip.h"               // quad_sum, Text20
 #include "kernels_nt2_kmer.hip.h"  // quad_step, verify_part, lcx_quad_step
+#include "kmer_table.hip.h"        // lcx_text_letters, LCX_LANE_ROWS
 #include "kernels_seed.hip.h"      // quad_step, step_scalar, symbol_at, Text20
 #include "kernels_pack.hip.h"
 #include "kernels_reads.hip.h"     // Nt2Survivors

@@ -398,7 +398,9 @@ __global__ __launch_bounds__(256) void count_nt2_probe_kernel(DevIndex ix, const
 // with the text costs ~2 lines per candidate instead of one line per letter).  Random batches barely reach this kernel,
 // so the extra state costs them nothing -- which is why the k-mer path can keep verify on by default.
 // (the body of count_nt2_resume_kernel as a block-level function, with the set of list positions a quad walks as parameters)
-template <bool TALLY, bool VERIFY>
+// TABLE: a survivor whose bucket the k-mer count table (layout.h, KT_*) covers asks the table first -- one line -- and is searched
+// only where the table says so.  The one launch takes it; the resume kernel of the two-launch schedules (A/B) stays as it is.
+template <bool TALLY, bool VERIFY, bool TABLE = false>
 __device__ __forceinline__ void resume_block_list(const DevIndex& ix, const Nt2Survivors& sv, uint64_t region, uint64_t ns, int L,
                                                   uint64_t* __restrict__ counts, unsigned long long* __restrict__ tally, bool allow_lcx,
                                                   uint64_t r_start, uint64_t r_stride) {
@@ -416,7 +418,7 @@ __device__ __forceinline__ void resume_block_list(const DevIndex& ix, const Nt2S
   int i = 0, steps_done = 0;
   // 0 = LF steps, 1 = read SA of candidate vj, 2 = compare its text window (seed-and-verify);
   // left-context index: 3 = read the number of incomplete entries, 4 = search the keys, 5 = text position of incomplete
-  // entry vj, 6 = compare it with the text
+  // entry vj, 6 = compare it with the text; 7 (TABLE) = read the k-mer's line of the count table, the search's first mode waiting in steps_done
   int mode = 0, vj = 0;
   uint32_t vhits = 0, vp = 0;
   // The search of a bucket's keys keeps its state in the variables the LF modes do not use meanwhile -- this kernel runs
@@ -457,6 +459,7 @@ __device__ __forceinline__ void resume_block_list(const DevIndex& ix, const Nt2S
               steps_done = 0;  // (incomplete rows of the bucket)
               if (cf & SEED_LCX_TAIL) mode = 3;
               else { vp = ub_a = sp; vhits = ub_b = sp + cnt; vj = lcx_top_level(sp, cnt); mode = 4; }
+              if (TABLE && ix.kmer_tab && cnt > (uint32_t)LCX_LANE_ROWS) { steps_done = mode; mode = 7; }  // the table of this length covers the bucket: the search waits
             }
           }
         }
@@ -515,6 +518,24 @@ __device__ __forceinline__ void resume_block_list(const DevIndex& ix, const Nt2S
         if (TALLY) t_rp++;
         if (vp >= (uint32_t)i) mode = 6;
         else vj++;
+      } else if (TABLE && mode == 7) {  // the count table: the k-mer's line, 4 entries per lane (the two 16-B loads of a node read)
+        const uint64_t mx = kt_mix(w, L);
+        const ulonglong2* p = reinterpret_cast<const ulonglong2*>(ix.kmer_tab + ((mx & ((1ull << ix.kmer_tab_bits) - 1)) << 4) + 4 * l);
+        const ulonglong2 x = p[0], y = p[1];
+        const uint64_t tag = mx >> ix.kmer_tab_bits;
+        const uint64_t want = tag >= KT_TAG_NONE ? ~0ull : tag << KT_TAG_SHIFT;  // (KT_TAG_NONE and wider tags are never stored: no entry matches)
+        uint32_t c = l == 0 ? ((uint32_t)x.x >> KT_CNT_BITS & 1u) << 24 : 0u;  // the line's overflow mark lives in its first slot
+        c += ((x.x ^ want) >> KT_TAG_SHIFT) == 0 ? (uint32_t)x.x & (uint32_t)KT_CNT_MASK : 0u;  // (an empty slot has count 0)
+        c += ((x.y ^ want) >> KT_TAG_SHIFT) == 0 ? (uint32_t)x.y & (uint32_t)KT_CNT_MASK : 0u;
+        c += ((y.x ^ want) >> KT_TAG_SHIFT) == 0 ? (uint32_t)y.x & (uint32_t)KT_CNT_MASK : 0u;
+        c += ((y.y ^ want) >> KT_TAG_SHIFT) == 0 ? (uint32_t)y.y & (uint32_t)KT_CNT_MASK : 0u;
+        c = quad_sum(c);
+        if (TALLY) t_lcx++;
+        const uint32_t found = c & 0xFFFFFFu;
+        if (found == (uint32_t)KT_ASK || (found == 0u && (c >> 24))) {  // "ask the index", or a miss in a line that overflowed: the search
+          mode = steps_done;
+          steps_done = 0;
+        } else { finished = true; out_count = found; steps_done = 0; }
       } else {
         const uint32_t bad = quad_sum(verify_part(ix.text4, (uint64_t)vp - (uint64_t)i, i, 0, l, w));
         if (TALLY) t_vtxt++;
@@ -561,7 +582,7 @@ template <bool TALLY, bool VERIFY>
 __global__ __launch_bounds__(256) void count_nt2_probe_resume_kernel(DevIndex ix, const uint64_t* __restrict__ queries, uint64_t n, int L, uint64_t* __restrict__ counts,
                                    Nt2Survivors sv, unsigned long long* __restrict__ tally) {
   const unsigned ns = probe_block<TALLY, VERIFY>(ix, queries, n, L, counts, sv, tally);
-  resume_block_list<TALLY, VERIFY>(ix, sv, (uint64_t)blockIdx.x * sv.cap, (uint64_t)ns, L, counts, tally, true, threadIdx.x >> 2, 64);
+  resume_block_list<TALLY, VERIFY, true>(ix, sv, (uint64_t)blockIdx.x * sv.cap, (uint64_t)ns, L, counts, tally, true, threadIdx.x >> 2, 64);
 }
 // v2 of the hot kernel: the query and result streams are staged through LDS in wave-private chunks so that
 // both move as whole 128-B lines (v1 fetched one line per 8-B query word and wrote one partial line per

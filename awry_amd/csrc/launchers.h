@@ -281,6 +281,17 @@ void launch_count_nt2_long(Replica& r, const uint64_t* d_words, uint64_t n, int 
   HIP_CHECK(hipGetLastError());
 }
 
+// Does a launch of n packed k-mers take the k-mer count table (and build it when its length has none)?  The policy: batches of
+// KMER_TABLE_MIN_BATCH queries and more, with no schedule forced by awry_debug_set_count_kernel / AWRY_COUNT_KERNEL -- small
+// batches and forced schedules keep the searches whose census the tests of those schedules read.  awry_set_kmer_table(1):
+// whatever the batch; (0): never.
+constexpr uint64_t KMER_TABLE_MIN_BATCH = 65536;
+bool kmer_table_wanted(const Replica& r, uint64_t n) {
+  static const bool off = getenv("AWRY_KMER_TABLE") && !strcmp(getenv("AWRY_KMER_TABLE"), "0");
+  if (off || r.kt_mode == 0) return false;
+  return r.kt_mode == 1 || (n >= KMER_TABLE_MIN_BATCH && count_kernel_override() < 0);
+}
+
 void launch_count_nt2(Replica& r, const uint64_t* d_words, uint64_t n, int L, uint64_t* d_counts, bool use_seed, hipStream_t s,
                       unsigned long long* d_tally = nullptr) {
   require(r.dev.alphabet == NUCLEOTIDE, "packed 2-bit queries need a nucleotide index");
@@ -323,6 +334,11 @@ void launch_count_nt2(Replica& r, const uint64_t* d_words, uint64_t n, int L, ui
     const unsigned nblk = (unsigned)r.num_cus * (kmode == 4 ? 8u : (unsigned)r.probe_resume_per_cu[2 * (d_tally != nullptr) + vfy]);
     Nt2Survivors sv, fb;
     two_phase_lists(r, s, n, nblk, 0u, &sv, &fb);
+    // survivors with a bucket of the left-context index: the count table of this length answers them from one line
+    // (kmer_table_wanted: built on the first large batch of a length, replacing the table of another length)
+    std::shared_lock<std::shared_mutex> kt_lock;
+    if (!pair && vfy && !rung && dv.lcx_key && L > r.seed_k && kmer_table_wanted(r, n))
+      if (const Replica::KmerTable* kt = kmer_table(r, L, true, kt_lock)) { dv.kmer_tab = kt->tab.p; dv.kmer_tab_bits = kt->bits; }
     const dim3 gp(nblk);
     with_flags(d_tally != nullptr, vfy, [&](auto T, auto V) {
       if (pair) {

@@ -174,8 +174,31 @@ struct DevIndex {
   const uint64_t* lcx_rowpos;
   const uint64_t* lcx_inner;
   uint32_t lcx_off[8];
+  // The k-mer count table of ONE query length L (KT_* below; nullptr in the replica's own copy: a launch of that length gets
+  // it in the launcher's local copy, like a rung): 2^kmer_tab_bits lines of 16 entries.
+  const uint64_t* kmer_tab;
+  uint32_t kmer_tab_bits, kmer_tab_pad;
 };
 constexpr int LCX_CTX = 32;  // letters of left context in a key
+
+// The k-mer count table: for one query length L (seed_k < L <= 32) and every seed bucket phase 2 of the k-mer count would
+// search in the left-context index, every distinct L-mer of the bucket -> its count.  Open-addressed by 128-B line: a
+// bijective mix of the 2L-bit query word picks the line with its low bits, the rest of the mixed word is the entry's tag, so
+// a hit is exact.  Entry: tag << 21 | overflow << 20 | count; count 0 = empty slot, KT_ASK = "ask the index" (the count does
+// not fit).  The overflow bit (kept in slot 0 of a line) says that some key found the line full: a miss in such a line
+// proves nothing and the query is searched as without the table.  A miss in any other line is count 0.
+constexpr int KT_CNT_BITS = 20, KT_TAG_SHIFT = 21, KT_TAG_BITS = 64 - KT_TAG_SHIFT;
+constexpr uint64_t KT_CNT_MASK = (1ull << KT_CNT_BITS) - 1, KT_ASK = KT_CNT_MASK, KT_OVERFLOW = 1ull << KT_CNT_BITS;
+constexpr uint64_t KT_TAG_NONE = (1ull << KT_TAG_BITS) - 1;  // this tag and wider ones (a table forced too small for its keys) are not stored: their lines are marked
+// bijective on 2L-bit words (odd multiplier, xor of the high half into the low one, twice)
+AWRY_HD uint64_t kt_mix(uint64_t w, int L) {
+  const uint64_t m = L >= 32 ? ~0ull : (1ull << (2 * L)) - 1;
+  w = (w * 0x9E3779B97F4A7C15ull) & m;
+  w ^= w >> L;
+  w = (w * 0xD6E8FEB86659FD93ull) & m;
+  w ^= w >> L;
+  return w;
+}
 
 // encoding of a query's "range start" word handed from the count pass to the locate pass
 constexpr uint64_t RS_MODE_SHIFT = 62;

@@ -145,6 +145,9 @@ void prewarm_host_paths(Replica& r) {
     PackedPlan plan;
     plan.ok = true;
     plan.Lmax = 31;
+    // (a warm-up, not a caller's batch of 31-mers: it neither builds nor finds a k-mer count table)
+    struct TableOff { Replica& r; int mode; ~TableOff() { r.kt_mode = mode; } } table_off{r, r.kt_mode};
+    r.kt_mode = 0;
     count_shard_hostpacked(r, nullptr, nullptr, Shard{0, n}, plan, counts.data(), words.data());
   }
 }

@@ -101,7 +101,20 @@ struct Replica {
   std::map<int, DevBuf<SeedEntry>> rungs;
   std::set<int> rungs_refused;  // lengths whose table did not fit the HBM budget when first asked for
   std::mutex rung_mu;
-  bool wide = false;           // 64-bit rows: wide kernels, no 32-bit accelerators
+  // The k-mer count table (layout.h, KT_*): ONE per replica, for the query length it was last built for (accelerators.h,
+  // kmer_table).  A launcher reads it under a shared lock that it holds until its kernel is queued; building, replacing and
+  // dropping take the lock exclusively, and freeing the old table waits for the device -- so no kernel runs on a freed table.
+  struct KmerTable {
+    DevBuf<uint64_t> tab;
+    int L = 0;
+    uint32_t bits = 0;  // 2^bits lines of 16 entries
+    uint64_t entries = 0, overflowed = 0;
+    double build_ms = 0;
+  } kt;
+  std::set<int> kt_refused;  // lengths whose table did not fit the HBM budget when first asked for (forgotten with the table)
+  std::shared_mutex kt_mu;
+  int kt_mode = -1;          // awry_set_kmer_table: -1 policy, 0 off, 1 build for the next length whatever the batch size
+  bool wide = false;          // 64-bit rows: wide kernels, no 32-bit accelerators
   DevBuf<uint32_t> text4;                     // 4-bit text for seed-and-verify (device-only accelerator)
   DevBuf<uint8_t> text8;                      // the text as symbol indices, for the generic kernel's verify (any alphabet)
   DevBuf<uint32_t> dense_sa;                  // SA[j * dense_ratio] as u32 (device-only accelerator for locate)
@@ -171,6 +184,7 @@ struct Replica {
       scratch.clear();
       sa_nblock.reset(); text8.reset(); edit_text8.reset();
       lcx_key.reset(); lcx_rowpos.reset(); lcx_inner.reset();
+      kt.tab.reset();
     }
   }
 };
@@ -185,6 +199,7 @@ struct awry_index {
   int verify_request = -2;      // -2: policy; -1: seed-and-verify off; >= 0: LF steps before switching to text comparison
   bool verify_kmers_request = false;
   int lcx_request = -1;         // -1: policy (on when it fits); 0: no left-context index; 1: as -1
+  int kmer_table_request = -1;  // awry_set_kmer_table (Replica::kt_mode)
 };
 
 namespace {

@@ -1142,6 +1142,18 @@ class FmIndex:
     def lcx_enabled(self) -> bool:
         return bool(self._L.awry_lcx_enabled(self._h))
 
+    def set_kmer_table(self, mode: int):
+        """k-mer count table (performance knob; results do not depend on it): -1 the policy (built by the first batch of 65536
+        k-mers or more of a length), 0 off, 1 build for the length of the next launch whatever its size"""
+        _check(self._L.awry_set_kmer_table(self._h, mode))
+
+    def kmer_table_info(self, slot=0) -> dict:
+        """the table resident on replica `slot`: its k-mer length (0: none), entries, lines, overflowed lines, bytes, build time"""
+        info = (C.c_uint64 * 6)()
+        _check(self._L.awry_kmer_table_info(self._h, slot, info))
+        return {"length": int(info[0]), "entries": int(info[1]), "lines": int(info[2]), "overflowed_lines": int(info[3]),
+                "bytes": int(info[4]), "build_ms": int(info[5]) / 1000.0}
+
     def debug_lcx(self, slot=0):
         """-> (keys uint64[bwt_len], rowpos uint64[bwt_len]) copied from replica `slot`, or None when it is not resident"""
         k, rp = C.c_void_p(), C.c_void_p()

@@ -140,6 +140,26 @@ int awry_lcx_enabled(const awry_index_t *idx);
 /* device pointers of replica `slot`'s left-context index for tests that dump it: keys[bwt_len] (u64) and
  * rowpos[bwt_len] (u64: text position | BWT row << 32); NULL when it is not resident */
 int awry_debug_lcx(const awry_index_t *idx, int slot, const void **d_keys, const void **d_rowpos);
+/* k-mer count table (performance knob only; counts do not depend on it): with the left-context index resident, a replica keeps,
+ * for ONE k-mer length L (seed k < L <= 32) at a time, every distinct L-mer of every seed bucket of more than 4 rows with its
+ * count, in a hash table of 128-B lines (16 entries of 8 B; about 8 keys per line; for small texts at least 2^(2L - 43)
+ * lines).  Like the tables of k-mers shorter than the seed k, it is built on first use -- on the replica's own stream, from the
+ * left-context index, within half of the HBM then free; a length it does not fit is remembered and searched as before -- and
+ * a k-mer of a repeat family then costs one random line instead of a search of 4..6 dependent ones.  Entries whose count does
+ * not fit and lines that took more than 16 keys send their queries to the search.
+ * mode -1 (default): built by the first awry_dev_count_nt2 launch (or host batch chunk) of a length with 65536 queries or more
+ * and no awry_debug_set_count_kernel / AWRY_COUNT_KERNEL override, and used by such launches; a large batch of another length
+ * replaces it.  mode 0: off (drops it).  mode 1: built for the length of the next launch, whatever its size, and used by every
+ * launch of that length.  env AWRY_KMER_TABLE=0 disables.  Whatever drops or rebuilds the left-context index or the seed table
+ * (awry_set_lcx, awry_set_verify, awry_set_locate_sa_ratio, awry_set_seed_kmer_len, awry_set_devices) drops the table; the
+ * warm-up batch of awry_set_devices builds none.  The reads (L > 32) and amino paths do not use it. */
+int awry_set_kmer_table(awry_index_t *idx, int mode);
+/* the table resident on replica `slot`: info[0] its length L (0: none), [1] distinct L-mers kept, [2] 128-B lines, [3] lines that
+ * could not take all their keys, [4] bytes, [5] wall time of its construction in microseconds */
+int awry_kmer_table_info(awry_index_t *idx, int slot, uint64_t *info);
+/* lines of k-mer count tables built afterwards (process-wide; rounded down to a power of two; 0, the default: the policy).
+ * For tests: a table far too small overflows in most lines.  Results do not depend on it. */
+int awry_debug_set_kmer_table_lines(uint64_t lines);
 int awry_num_devices(const awry_index_t *idx);
 
 /* ---- batch queries --------------------------------------------------------------------------------- */
