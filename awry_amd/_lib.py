@@ -223,6 +223,7 @@ def load_library():
     sig("awry_set_kmer_table", i32, vp, i32)
     sig("awry_kmer_table_info", i32, vp, i32, u64p)
     sig("awry_debug_set_kmer_table_lines", i32, u64)
+    sig("awry_debug_kmer_table", i32, vp, i32, vp, u64, C.POINTER(i32), C.POINTER(C.c_uint32))
     sig("awry_dev_stream_copy", i32, vp, i32, vp, vp, u64, vp)
     sig("awry_dev_malloc", i32, vp, i32, u64, vpp)
     sig("awry_dev_free", i32, vp, i32, vp)

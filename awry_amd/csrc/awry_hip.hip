@@ -919,6 +919,19 @@ int awry_kmer_table_info(awry_index_t* idx, int slot, uint64_t* info) {
   });
 }
 int awry_debug_set_kmer_table_lines(uint64_t lines) { g_kt_debug_lines.store(lines); return AWRY_OK; }
+int awry_debug_kmer_table(awry_index_t* idx, int slot, uint64_t* host_out, uint64_t capacity_words, int* L_out, uint32_t* bits_out) {
+  return guarded([&] {
+    require(idx != nullptr && L_out != nullptr && bits_out != nullptr, "null argument");
+    Replica& r = replica(idx, slot);
+    std::shared_lock<std::shared_mutex> lock(r.kt_mu);  // (held over the copy: a launch of another length frees the table)
+    const bool have = r.kt.tab.p != nullptr;
+    *L_out = have ? r.kt.L : 0;
+    *bits_out = have ? r.kt.bits : 0u;
+    if (!have || !host_out || capacity_words < (16ull << r.kt.bits)) return;
+    HIP_CHECK(hipMemcpyAsync(host_out, r.kt.tab.p, 128ull << r.kt.bits, hipMemcpyDeviceToHost, r.stream));
+    HIP_CHECK(hipStreamSynchronize(r.stream));
+  });
+}
 int awry_debug_lcx(const awry_index_t* idx, int slot, const void** d_keys, const void** d_rowpos) {
   if (!idx || slot < 0 || slot >= (int)idx->reps.size() || !d_keys || !d_rowpos) return AWRY_ERR_ARG;
   *d_keys = idx->reps[slot]->lcx_key.p;

@@ -12,6 +12,10 @@ void prewarm_host_paths(Replica& r) {
   static const bool off = getenv("AWRY_PREWARM") && !strcmp(getenv("AWRY_PREWARM"), "0");
   if (off) return;
   HIP_CHECK(hipSetDevice(r.device));
+  // (warm-ups, not a caller's batches of k-mers: they neither build nor find a k-mer count table -- with awry_set_kmer_table(1)
+  // inherited by a new replica, the 64 k-mers of length k + 1 of the count lanes' round trip below used to build one)
+  struct TableOff { Replica& r; int mode; ~TableOff() { r.kt_mode = mode; } } table_off{r, r.kt_mode};
+  r.kt_mode = 0;
   (void)HostPool::instance();
   const bool nt = r.dev.alphabet == NUCLEOTIDE;
   const uint64_t cap = 1u << 20, W = 4;  // one chunk of the host paths; W words per query cover reads of up to 128 letters
@@ -145,9 +149,6 @@ void prewarm_host_paths(Replica& r) {
     PackedPlan plan;
     plan.ok = true;
     plan.Lmax = 31;
-    // (a warm-up, not a caller's batch of 31-mers: it neither builds nor finds a k-mer count table)
-    struct TableOff { Replica& r; int mode; ~TableOff() { r.kt_mode = mode; } } table_off{r, r.kt_mode};
-    r.kt_mode = 0;
     count_shard_hostpacked(r, nullptr, nullptr, Shard{0, n}, plan, counts.data(), words.data());
   }
 }

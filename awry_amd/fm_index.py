@@ -1154,6 +1154,23 @@ class FmIndex:
         return {"length": int(info[0]), "entries": int(info[1]), "lines": int(info[2]), "overflowed_lines": int(info[3]),
                 "bytes": int(info[4]), "build_ms": int(info[5]) / 1000.0}
 
+    def debug_kmer_table(self, slot=0):
+        """-> (uint64[lines * 16] the table resident on replica `slot`, copied; bits = log2(lines); its k-mer length L), or None
+        when none is resident"""
+        L, bits = C.c_int(0), C.c_uint32(0)
+        for _ in range(4):  # (another launch may replace the table between the size query and the copy)
+            _check(self._L.awry_debug_kmer_table(self._h, slot, None, 0, C.byref(L), C.byref(bits)))
+            if L.value == 0:
+                return None
+            want = bits.value
+            tab = np.empty(16 << want, np.uint64)
+            _check(self._L.awry_debug_kmer_table(self._h, slot, tab.ctypes.data, len(tab), C.byref(L), C.byref(bits)))
+            if L.value == 0:
+                return None
+            if bits.value <= want:  # (a larger one was not copied)
+                return tab[:16 << bits.value], int(bits.value), int(L.value)
+        raise AwryError(ERR_ARG, "the k-mer count table kept changing size while it was read")
+
     def debug_lcx(self, slot=0):
         """-> (keys uint64[bwt_len], rowpos uint64[bwt_len]) copied from replica `slot`, or None when it is not resident"""
         k, rp = C.c_void_p(), C.c_void_p()

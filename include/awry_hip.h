@@ -160,6 +160,11 @@ int awry_kmer_table_info(awry_index_t *idx, int slot, uint64_t *info);
 /* lines of k-mer count tables built afterwards (process-wide; rounded down to a power of two; 0, the default: the policy).
  * For tests: a table far too small overflows in most lines.  Results do not depend on it. */
 int awry_debug_set_kmer_table_lines(uint64_t lines);
+/* the k-mer count table resident on replica `slot`, for tests that audit it: *L_out its length and *bits_out the log2 of its
+ * number of lines (both 0: none resident).  With host_out non-null and capacity_words >= 16 << *bits_out, the table's
+ * 16 << bits words (entry: tag << 21 | overflow << 20 | count, 16 entries per line) are copied to host_out.  A copy, not a
+ * device pointer: any launch of another length may free the table, so it is read under the lock that keeps it resident. */
+int awry_debug_kmer_table(awry_index_t *idx, int slot, uint64_t *host_out, uint64_t capacity_words, int *L_out, uint32_t *bits_out);
 int awry_num_devices(const awry_index_t *idx);
 
 /* ---- batch queries --------------------------------------------------------------------------------- */
