@@ -70,11 +70,11 @@ void build_seed_table(Replica& r, bool nt, int k, DevBuf<Entry>& out) {
 }
 
 // The table for nucleotide k-mers of L < seed_k letters, built on first use and kept.  nullptr: not available (it does not
-// fit the HBM budget, or AWRY_SEED_RUNGS=0) -- the caller falls back to LF steps from the last letter.
-constexpr int SEED_RUNG_MIN = 6;  // shorter k-mers: a handful of LF steps over blocks that live in L2
+// fit the HBM budget, or AWRY_SEED_RUNGS=0) -- the caller falls back to LF steps from the last letter.  Which launches ask
+// for one is the count plan's rule (count_plan.h, plan_kmers); the guard here keeps the table's size bounded whoever asks.
 const SeedEntry* seed_rung(Replica& r, int L) {
   static const bool off = getenv("AWRY_SEED_RUNGS") && !strcmp(getenv("AWRY_SEED_RUNGS"), "0");
-  if (off || r.wide || r.dev.alphabet != NUCLEOTIDE || L < SEED_RUNG_MIN || L > 16) return nullptr;
+  if (off || r.wide || r.dev.alphabet != NUCLEOTIDE || L < SEED_RUNG_MIN || L > SEED_RUNG_MAX) return nullptr;
   std::lock_guard<std::mutex> lock(r.rung_mu);
   auto it = r.rungs.find(L);
   if (it != r.rungs.end()) return it->second.p;

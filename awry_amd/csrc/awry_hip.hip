@@ -278,26 +278,11 @@ int awry_debug_set_max_blocks(int blocks) {
 int awry_debug_max_blocks(void) { return g_max_blocks.load(); }
 
 const char* awry_count_schedule(const awry_index_t* idx, int L) {
-  static const char* names[] = {"count_nt2_quad_kernel", "count_nt2_chunk_kernel", "count_nt2_quad4_kernel",
-                                "count_nt2_probe_resume_kernel", "count_nt2_probe_kernel+count_nt2_resume_kernel",
-                                "count_nt2_probe_kernel+count_nt2_resume_kernel"};
   if (!idx || idx->reps.empty()) return "";
-  const Replica& r = *idx->reps[0];
-  if (r.wide) return wide_two_phase(1) && r.seed_k > 0 && r.seed_k <= L ? "count_nt2_wide_probe_kernel+count_nt2_wide_kernel" : "count_nt2_wide_kernel";
-  const bool seeded = r.seed_k > 0 && r.seed_k <= L;
-  if (L > 32) {  // launch_count_nt2_long
-    const int om = count_kernel_override();
-    const bool two = r.dev.text4 && r.dev.dense_ratio == 1 && seeded && L - r.seed_k >= 3 && L <= 512 && (om < 0 || (om >= 3 && om <= 5));
-    return two ? "count_nt2_reads_probe_kernel+count_nt2_reads_kernel" : "count_nt2_reads_kernel";
-  }
-  static const bool rungs_off = getenv("AWRY_SEED_RUNGS") && !strcmp(getenv("AWRY_SEED_RUNGS"), "0");
-  if (!seeded && r.seed_k > L && L >= SEED_RUNG_MIN && !rungs_off && count_kernel_override() < 0)
-    return "count_nt2_probe_resume_kernel (table of its own for this length; batches of 4096 queries and more)";
-  int m = count_kernel_mode(r.dev.bwt_len, r.seed_k, seeded);
-  if (m >= 3 && m <= 5 && !seeded) m = 2;
-  if (m == 3 && L > r.seed_k && r.dev.lcx_key && r.dev.text4 && r.dev.dense_ratio == 1 && (r.kt_mode == 1 || (r.kt_mode < 0 && count_kernel_override() < 0)))
-    return "count_nt2_probe_resume_kernel (k-mer count table of this length: on first use with awry_set_kmer_table(1), else for batches of 65536 queries and more)";
-  return names[m >= 0 && m <= 5 ? m : 0];  // (other modes launch the strided quads)
+  // the plan of a seeded launch without census whose batch is at or above every batch-size threshold (rung, count table)
+  const CountFacts f = count_facts(*idx->reps[0]);
+  const uint64_t n = 1u << 20;
+  return plan_name(L > 32 ? plan_reads(f, n, L, true, false) : plan_kmers(f, n, L, true, false));
 }
 
 int awry_seed_kmer_len(const awry_index_t* idx) { return idx && !idx->reps.empty() ? idx->reps[0]->seed_k : 0; }

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "alphabet.h"
+#include "count_plan.h"
 #include "host_index.h"
 #include "host_pack.h"
 #include "kernels.hip.h"

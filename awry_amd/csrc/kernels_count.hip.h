@@ -36,7 +36,6 @@ struct QueryList {
                                     //   lists are then worked through as ONE pool by whatever grid this pass is launched
                                     //   with (0: block b takes list b)
 };
-constexpr int LIST_MAX_LISTS = 4096;
 __device__ __forceinline__ void tally_add(unsigned long long* tally, int slot, unsigned long long v) {
   if (tally && v) atomicAdd(&tally[slot], v);
 }

@@ -1,12 +1,11 @@
-// launchers.h -- count-kernel mode policy and every kernel launch helper (all asynchronous on the stream they are given)
+// launchers.h -- every kernel launch helper (all asynchronous on the stream they are given); the packed count launchers run
+// the schedule count_plan.h chooses
 // A part of awry_hip.hip (one translation unit): included there, in order, and not on its own.
 #pragma once
 
 namespace {
 
-// which instantiation serves awry_dev_count_nt2: 0 strided quads, 1 LDS-staged chunks, 2 groups of four, 3 two-phase,
-// 4 two-phase with the k-mer probe and resume passes as two launches on num_cus * 8 blocks (the schedule before the one
-// launch), 5 the same two launches on the one launch's grid (for A/B of fusion and grid size; other paths treat 4, 5 as 3)
+// the schedule forced on the packed count launchers (CountFacts::forced in count_plan.h has the numbers)
 std::atomic<int> g_count_kernel{-1};
 // -1: no explicit choice (env / policy)
 int count_kernel_override() {
@@ -19,24 +18,37 @@ int count_kernel_override() {
   if (e && !strcmp(e, "twophase")) return 3;
   return -1;
 }
-// Policy, from measurements on MI355X, GRCh38-scale, 10 M random 31-mers per launch (tools/ab_count.py, G queries/s):
-//   seed k   strided  quad4  chunk  twophase
-//     14      10.1    10.3    9.9     8.2
-//     16      19.4    21.8   14.4    21.3
-//     17      25.3    28.1     -     29.9
-// quad4 is the general default; once the table is so sparse that most queries are decided by their entry alone
-// (4^k >= 3 bwt_len) the per-lane probe pass of the two-phase schedule wins.
-int count_kernel_mode(uint64_t bwt_len, int seed_k, bool seeded) {
-  const int m = count_kernel_override();
-  if (m >= 0) return m;
-  if (seeded && seed_k >= 1 && seed_k <= 31 && (1ull << (2 * seed_k)) / 3 >= bwt_len) return 3;
-  return 2;
+
+// what plan_kmers / plan_reads (count_plan.h) read of a replica
+CountFacts count_facts(const Replica& r) {
+  static const bool rungs_off = getenv("AWRY_SEED_RUNGS") && !strcmp(getenv("AWRY_SEED_RUNGS"), "0");
+  static const bool table_off = getenv("AWRY_KMER_TABLE") && !strcmp(getenv("AWRY_KMER_TABLE"), "0");
+  CountFacts f;
+  f.alphabet = r.dev.alphabet;
+  f.wide = r.wide;
+  f.bwt_len = r.dev.bwt_len;
+  f.seed_k = r.seed_k;
+  f.seed = r.seed.p != nullptr;
+  f.seed64 = r.dev.seed64 != nullptr;
+  f.text4 = r.dev.text4 != nullptr;
+  f.dense_ratio = r.dev.dense_ratio;
+  f.lcx_key = r.dev.lcx_key != nullptr;
+  f.kt_mode = r.kt_mode;
+  f.verify_kmers = r.verify_kmers;
+  f.num_cus = r.num_cus;
+  for (int i = 0; i < 4; i++) f.probe_resume_per_cu[i] = r.probe_resume_per_cu[i];
+  for (int i = 0; i < 2; i++) f.lcx_reads_grid[i] = r.lcx_reads_grid[i];
+  f.forced = count_kernel_override();
+  f.rungs_off = rungs_off;
+  f.table_off = table_off;
+  return f;
+}
+// the grid of a plan's launches (the lane pass has p.lcx_grid): its block count, or sized from the batch
+dim3 plan_grid(const Replica& r, const CountPlan& p, uint64_t n) {
+  return dim3(p.blocks ? p.blocks : (unsigned)grid_for(r, n * p.items_per_query, 256));
 }
 
 // ---- kernel launch helpers (all asynchronous on `s`) ------------------------------------------------
-
-// slots of one survivor list of a two-phase launch over n queries on nblk blocks: the queries a block sees, ceil(n / (nblk * 256)) * 256
-uint64_t list_slots_per_block(uint64_t n, unsigned nblk) { return ((n + (uint64_t)nblk * 256 - 1) / ((uint64_t)nblk * 256)) * 256; }
 
 // ASCII -> packed 2-bit words.  d_off == nullptr: n queries of L bytes each; else query q = bytes [d_off[q] - base, d_off[q+1] - base)
 // of d_ascii (total_bytes in all), W words per query (stride), lengths to d_lens.
@@ -151,29 +163,6 @@ void launch_locate(Replica& r, const uint64_t* d_range_start, int rs_stride, con
   HIP_CHECK(hipGetLastError());
 }
 
-// reads: phase 2 as a pooled search pass (lcx_quad_reads_kernel) + LF pass whenever the left-context index is resident;
-// else count_nt2_reads_kernel<.., LIST> (block b works through block b's list)
-bool lcx_lanes(const Replica& r) {
-  return r.dev.lcx_key != nullptr && r.dev.text4 != nullptr && r.dev.dense_ratio == 1;
-}
-// wide-row replicas: the two-phase schedule (count_nt2_wide_probe_kernel + the listed quad pass) is an alternative, not the
-// policy -- on a GRCh38-scale index forced onto 64-bit rows (k = 16, 69 GB of 16-byte entries) it runs random 31-mers at 16.7
-// against 16.5 G/s and reads from the text 10 % slower than the single strided quad kernel: without the 32-bit accelerators
-// (dense SA, text, position seeds) the entry settles too few queries for a second launch to pay.  Selected with
-// AWRY_COUNT_KERNEL=twophase / awry_debug_set_count_kernel(3).
-bool wide_two_phase(uint64_t n) { const int m = count_kernel_override(); return m >= 3 && m <= 5 && n < (1ull << 32); }
-// The LF list lcx_quad_reads_kernel appends to on a grid of `grid` blocks (4 waves each), for `total` list slots of survivors.
-// A wave reserves LCX_LF_CHUNK slots at a time with one atomic and fills them in order.  One append is one item per quad
-// (16 per wave at most), and the wave reserves its next chunk only when an append does not fit in what is left, so every
-// chunk it leaves behind holds more than LCX_LF_CHUNK - 16 items; the chunk a wave holds at its end may be almost empty.
-// A wave that reserves c chunks thus appends at least (c - 1) (LCX_LF_CHUNK - 15) items, and the waves append at most
-// `total` items in all (each survivor at most once):
-//   sum_w (c_w - 1) <= floor(total / (LCX_LF_CHUNK - 15)),   chunks <= that + nwaves,
-//   slots = LCX_LF_CHUNK * chunks <= total + 15 * ceil(total / (LCX_LF_CHUNK - 15)) + nwaves * LCX_LF_CHUNK.
-uint64_t lcx_lf_list_bound(uint64_t total, unsigned grid) {
-  const uint64_t per = (uint64_t)LCX_LF_CHUNK - 15, nwaves = 4ull * grid;
-  return total + (total + per - 1) / per * 15 + nwaves * (uint64_t)LCX_LF_CHUNK;
-}
 // the survivor lists of a two-phase launch over n queries on a grid of nblk <= num_cus * 8 blocks (one list per block):
 // `in` (all three arrays) and, with lcx_grid != 0, the LF list `out` of lcx_quad_reads_kernel on a grid of lcx_grid blocks.
 // The caller holds the stream's ScratchLock until it has queued the kernels that take these pointers.
@@ -211,26 +200,24 @@ unsigned resident_grid(const Replica& r, K kernel) {
 
 // Packed queries on a wide-row replica (64-bit rows), for both packed launchers: k-mers (one word, d_tally optional) and reads
 // (d_lens, d_range_start optional).  The census is the k-mer path's: d_tally goes with equal lengths only.  The caller holds
-// the stream's ScratchLock.
-void launch_count_nt2_wide(Replica& r, const uint64_t* d_words, uint64_t n, int L, uint64_t* d_counts, uint64_t* d_range_start, bool use_seed,
+// the stream's ScratchLock and has planned a wide schedule.
+void launch_count_nt2_wide(Replica& r, const CountPlan& p, const uint64_t* d_words, uint64_t n, int L, uint64_t* d_counts, uint64_t* d_range_start,
                            hipStream_t s, const uint32_t* d_lens, unsigned long long* d_tally) {
   require(!(d_lens && d_tally), "internal: no census for reads of unequal lengths");
-  const bool sdw = use_seed && r.seed_k > 0 && r.dev.seed64 && (d_lens || r.seed_k <= L);  // ragged reads decide per read
-  const dim3 bw(256);
-  if (sdw && wide_two_phase(n)) {  // per-lane probe pass, then the quads on what has to be stepped
+  const dim3 gw(plan_grid(r, p, n)), bw(256);
+  if (p.schedule == CountSchedule::WIDE_TWO_PHASE) {
     Nt2Survivors sv, fb;
-    const unsigned nblk = (unsigned)r.num_cus * 8;
-    two_phase_lists(r, s, n, nblk, 0u, &sv, &fb);
-    if (d_lens) hipLaunchKernelGGL((count_nt2_wide_probe_kernel<true, false>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens, d_tally);
+    two_phase_lists(r, s, n, p.blocks, 0u, &sv, &fb);
+    if (d_lens) hipLaunchKernelGGL((count_nt2_wide_probe_kernel<true, false>), gw, bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens, d_tally);
     else with_flags(d_tally != nullptr, [&](auto T) {
-      hipLaunchKernelGGL((count_nt2_wide_probe_kernel<false, T()>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens, d_tally);
+      hipLaunchKernelGGL((count_nt2_wide_probe_kernel<false, T()>), gw, bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens, d_tally);
     });
     with_flags(d_lens != nullptr, [&](auto R) {
-      hipLaunchKernelGGL((count_nt2_wide_kernel<true, R(), true>), dim3(nblk), bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, d_lens, d_tally, sv);
+      hipLaunchKernelGGL((count_nt2_wide_kernel<true, R(), true>), gw, bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, d_lens, d_tally, sv);
     });
   } else {
-    const dim3 gw(grid_for(r, n * 4, 256));
-    with_flags(sdw, d_lens != nullptr, [&](auto S, auto R) {
+    require(p.schedule == CountSchedule::WIDE_SINGLE, "internal: not a wide-row schedule");
+    with_flags(p.seeded, d_lens != nullptr, [&](auto S, auto R) {
       hipLaunchKernelGGL((count_nt2_wide_kernel<S(), R()>), gw, bw, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, d_lens, d_tally);
     });
   }
@@ -244,52 +231,38 @@ void launch_count_nt2_long(Replica& r, const uint64_t* d_words, uint64_t n, int 
   require(L >= 1 && L <= 1 << 20, "packed read length out of range");
   if (n == 0) return;
   const ScratchLock scratch_lock(r, s);
-  if (r.wide) {
-    launch_count_nt2_wide(r, d_words, n, L, d_counts, d_range_start, use_seed, s, d_lens, nullptr);
-    return;
+  const CountPlan p = plan_reads(count_facts(r), n, L, use_seed, d_lens != nullptr);
+  const dim3 g(plan_grid(r, p, n)), b(256);
+  switch (p.schedule) {
+    case CountSchedule::WIDE_SINGLE:
+    case CountSchedule::WIDE_TWO_PHASE:
+      launch_count_nt2_wide(r, p, d_words, n, L, d_counts, d_range_start, s, d_lens, nullptr);
+      return;
+    case CountSchedule::READS_LISTS:
+    case CountSchedule::READS_LANES: {
+      const bool lanes = p.schedule == CountSchedule::READS_LANES;
+      Nt2Survivors sv, fb;
+      two_phase_lists(r, s, n, p.blocks, p.lcx_grid, &sv, &fb);
+      if (!lanes) sv.w = sv.range = nullptr;  // (the probe pass then lists the reads only)
+      with_flags(d_lens != nullptr, [&](auto R) {
+        hipLaunchKernelGGL(count_nt2_reads_probe_kernel<R()>, g, b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens);
+        if (lanes) {
+          hipLaunchKernelGGL(lcx_quad_reads_kernel<R()>, dim3(p.lcx_grid), b, 0, s, r.dev, d_words, L, d_counts, d_range_start, sv, fb, p.blocks, d_lens);
+          hipLaunchKernelGGL(count_nt2_reads_pool_kernel<R()>, g, b, 0, s, r.dev, d_words, L, d_counts, d_range_start, fb, d_lens);  // the quad code over what the lanes left
+        } else hipLaunchKernelGGL((count_nt2_reads_kernel<true, true, true, R()>), g, b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens);
+      });
+      break;
+    }
+    case CountSchedule::READS_SINGLE: {
+      const Nt2Survivors none{};
+      with_flags(p.seeded, p.verify, d_lens != nullptr, [&](auto S, auto V, auto R) {
+        hipLaunchKernelGGL((count_nt2_reads_kernel<S(), V(), false, R()>), g, b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, none, d_lens);
+      });
+      break;
+    }
+    default: require(false, "internal: not a schedule for reads");
   }
-  const bool sd = use_seed && r.seed_k > 0 && (d_lens || r.seed_k <= L);  // ragged reads decide per read
-  const bool vfy = r.dev.text4 && r.dev.dense_ratio == 1;
-  const dim3 g(grid_for(r, n * 4, 256)), b(256);
-  const int om = count_kernel_override();
-  if (vfy && sd && L - r.seed_k >= 3 && L <= 512 && n < (1ull << 32) && (om < 0 || (om >= 3 && om <= 5))) {
-    // two-phase: a per-lane pass settles the reads their seed entry (plus one SA read and one text window) decides,
-    // the quad kernel works through the rest
-    const unsigned nblk = (unsigned)r.num_cus * 8;  // both phases of the quad schedule use this grid
-    // the pooled pass (lcx_quad_reads_kernel + count_nt2_reads_pool_kernel) holds the prefix sums of the nblk lists in LDS
-    // and numbers the slots of its LF list with u32: it is taken only while both fit
-    const unsigned gl = r.lcx_reads_grid[d_lens != nullptr];
-    const bool lanes = lcx_lanes(r) && gl > 0 && nblk <= (unsigned)LIST_MAX_LISTS && lcx_lf_list_bound(list_slots_per_block(n, nblk) * nblk, gl) <= 0xFFFFFFFFull;
-    Nt2Survivors sv, fb;
-    two_phase_lists(r, s, n, nblk, lanes ? gl : 0u, &sv, &fb);
-    if (!lanes) sv.w = sv.range = nullptr;  // (the probe pass then lists the reads only)
-    const dim3 gq((unsigned)r.num_cus * 8);  // the quad code over what the lanes left
-    with_flags(d_lens != nullptr, [&](auto R) {
-      hipLaunchKernelGGL(count_nt2_reads_probe_kernel<R()>, dim3(nblk), b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens);
-      if (lanes) {
-        hipLaunchKernelGGL(lcx_quad_reads_kernel<R()>, dim3(gl), b, 0, s, r.dev, d_words, L, d_counts, d_range_start, sv, fb, nblk, d_lens);
-        hipLaunchKernelGGL(count_nt2_reads_pool_kernel<R()>, gq, b, 0, s, r.dev, d_words, L, d_counts, d_range_start, fb, d_lens);
-      } else hipLaunchKernelGGL((count_nt2_reads_kernel<true, true, true, R()>), dim3(nblk), b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, sv, d_lens);
-    });
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-  const Nt2Survivors none{};
-  with_flags(sd, vfy, d_lens != nullptr, [&](auto S, auto V, auto R) {
-    hipLaunchKernelGGL((count_nt2_reads_kernel<S(), V(), false, R()>), g, b, 0, s, r.dev, d_words, n, L, d_counts, d_range_start, none, d_lens);
-  });
   HIP_CHECK(hipGetLastError());
-}
-
-// Does a launch of n packed k-mers take the k-mer count table (and build it when its length has none)?  The policy: batches of
-// KMER_TABLE_MIN_BATCH queries and more, with no schedule forced by awry_debug_set_count_kernel / AWRY_COUNT_KERNEL -- small
-// batches and forced schedules keep the searches whose census the tests of those schedules read.  awry_set_kmer_table(1):
-// whatever the batch; (0): never.
-constexpr uint64_t KMER_TABLE_MIN_BATCH = 65536;
-bool kmer_table_wanted(const Replica& r, uint64_t n) {
-  static const bool off = getenv("AWRY_KMER_TABLE") && !strcmp(getenv("AWRY_KMER_TABLE"), "0");
-  if (off || r.kt_mode == 0) return false;
-  return r.kt_mode == 1 || (n >= KMER_TABLE_MIN_BATCH && count_kernel_override() < 0);
 }
 
 void launch_count_nt2(Replica& r, const uint64_t* d_words, uint64_t n, int L, uint64_t* d_counts, bool use_seed, hipStream_t s,
@@ -298,69 +271,57 @@ void launch_count_nt2(Replica& r, const uint64_t* d_words, uint64_t n, int L, ui
   require(L >= 1 && L <= 32, "packed k-mer length must be in 1..32");
   if (n == 0) return;
   const ScratchLock scratch_lock(r, s);
-  if (r.wide) {  // one word per k-mer is the W = 1 case of the wide kernel
-    launch_count_nt2_wide(r, d_words, n, L, d_counts, nullptr, use_seed, s, nullptr, d_tally);
-    return;
-  }
-  // k-mers shorter than the seed table's k: their own complete table ("rung", built on first use) -- the entry IS the
-  // answer, where LF steps from the last letter cost L dependent block reads (GRCh38 scale: 12-mers 5.6 -> 30+ G/s)
+  CountFacts f = count_facts(r);
+  CountPlan p = plan_kmers(f, n, L, use_seed, d_tally != nullptr);
+  // a wanted rung or count table of this length: resident, or built now (the table in place of another length's); where
+  // that fails the launch is planned again without it.  The launch gets either in its own copy of the index.
   DevIndex dv = r.dev;
-  bool rung = false;
-  if (use_seed && r.seed_k > L && r.seed.p && n >= 4096 && n < (1ull << 32) && count_kernel_override() < 0)
-    if (const SeedEntry* t = seed_rung(r, L)) { dv.seed = t; dv.seed_k = L; dv.seed_pos = 0; dv.ctx_extra = 0; rung = true; }
-  const bool seeded = rung || (use_seed && r.seed_k > 0 && r.seed_k <= L);
-  const dim3 g(grid_for(r, n * 4, 256)), b(256);
-  // AWRY_COUNT_KERNEL=chunk selects the LDS-staged variant (count_nt2_chunk_kernel).  Measured on MI355X it is
-  // equal at seed k=14 and 23% slower at k=16 (GRCh38-scale): the strided kernel's query words already arrive
-  // as L2 hits, so staging only removes the partial-line result writes and pays chunk drain + refill for it.
-  const int kmode = rung ? 3 : count_kernel_mode(r.dev.bwt_len, r.seed_k, seeded);
-  const bool use_chunk = kmode == 1;
-  if (use_chunk) {
-    unsigned long long* ctr = next_counter(r, s);
-    with_flags(seeded, d_tally != nullptr, [&](auto S, auto T) {
-      hipLaunchKernelGGL((count_nt2_chunk_kernel<S(), T()>), g, b, 0, s, r.dev, d_words, n, L, d_counts, ctr, d_tally);
-    });
-    HIP_CHECK(hipGetLastError());
-    return;
+  std::shared_lock<std::shared_mutex> kt_lock;  // held until the kernel that takes the table is queued
+  if (p.rung) {
+    if (const SeedEntry* t = seed_rung(r, L)) { dv.seed = t; dv.seed_k = L; dv.seed_pos = 0; dv.ctx_extra = 0; }
+    else { f.rung_failed = true; p = plan_kmers(f, n, L, use_seed, d_tally != nullptr); }
   }
-  if (kmode >= 3 && kmode <= 5 && seeded && n < (1ull << 32)) {
-    // two-phase: per-lane seed probes decide most queries, the quad machinery resumes the survivors -- in one launch on
-    // the resident grid, or (modes 4 and 5, for A/B) as the probe and resume kernels on num_cus * 8 blocks / that grid.
-    // The one launch takes the survivor count from LDS and leaves sv.count untouched.
-    // survivors of phase 1 use seed-and-verify whenever its accelerators are resident (cheap: random batches barely
-    // reach phase 2); the single-kernel schedules use it only on request (awry_set_verify_kmers)
-    const bool vfy = r.dev.text4 != nullptr && r.dev.dense_ratio == 1;
-    const bool pair = kmode != 3;
-    const unsigned nblk = (unsigned)r.num_cus * (kmode == 4 ? 8u : (unsigned)r.probe_resume_per_cu[2 * (d_tally != nullptr) + vfy]);
-    Nt2Survivors sv, fb;
-    two_phase_lists(r, s, n, nblk, 0u, &sv, &fb);
-    // survivors with a bucket of the left-context index: the count table of this length answers them from one line
-    // (kmer_table_wanted: built on the first large batch of a length, replacing the table of another length)
-    std::shared_lock<std::shared_mutex> kt_lock;
-    if (!pair && vfy && !rung && dv.lcx_key && L > r.seed_k && kmer_table_wanted(r, n))
-      if (const Replica::KmerTable* kt = kmer_table(r, L, true, kt_lock)) { dv.kmer_tab = kt->tab.p; dv.kmer_tab_bits = kt->bits; }
-    const dim3 gp(nblk);
-    with_flags(d_tally != nullptr, vfy, [&](auto T, auto V) {
-      if (pair) {
-        hipLaunchKernelGGL((count_nt2_probe_kernel<T(), V()>), gp, b, 0, s, dv, d_words, n, L, d_counts, sv, d_tally);
-        hipLaunchKernelGGL((count_nt2_resume_kernel<T(), V()>), gp, b, 0, s, dv, sv, L, d_counts, d_tally);
-      } else hipLaunchKernelGGL((count_nt2_probe_resume_kernel<T(), V()>), gp, b, 0, s, dv, d_words, n, L, d_counts, sv, d_tally);
-    });
-    HIP_CHECK(hipGetLastError());
-    return;
+  if (p.table) {
+    if (const Replica::KmerTable* kt = kmer_table(r, L, true, kt_lock)) { dv.kmer_tab = kt->tab.p; dv.kmer_tab_bits = kt->bits; }
+    else { f.table_failed = true; p = plan_kmers(f, n, L, use_seed, d_tally != nullptr); }
   }
-  if (kmode >= 2 && kmode <= 5) {  // groups of 4 consecutive queries per quad: whole-sector result writes
-    const dim3 g4(grid_for(r, n, 256));
-    const bool verify = r.verify_kmers && r.dev.text4 != nullptr && r.dev.dense_ratio == 1;
-    with_flags(seeded, d_tally != nullptr, verify, [&](auto S, auto T, auto V) {
-      hipLaunchKernelGGL((count_nt2_quad4_kernel<S(), T(), V()>), g4, b, 0, s, r.dev, d_words, n, L, d_counts, d_tally);
-    });
-    HIP_CHECK(hipGetLastError());
-    return;
+  const dim3 g(plan_grid(r, p, n)), b(256);
+  switch (p.schedule) {
+    case CountSchedule::WIDE_SINGLE:
+    case CountSchedule::WIDE_TWO_PHASE:
+      launch_count_nt2_wide(r, p, d_words, n, L, d_counts, nullptr, s, nullptr, d_tally);
+      return;
+    case CountSchedule::LDS_CHUNKS: {
+      unsigned long long* ctr = next_counter(r, s);
+      with_flags(p.seeded, d_tally != nullptr, [&](auto S, auto T) {
+        hipLaunchKernelGGL((count_nt2_chunk_kernel<S(), T()>), g, b, 0, s, r.dev, d_words, n, L, d_counts, ctr, d_tally);
+      });
+      break;
+    }
+    case CountSchedule::PROBE_RESUME:
+    case CountSchedule::PROBE_THEN_RESUME: {  // (the one launch takes the survivor count from LDS and leaves sv.count untouched)
+      Nt2Survivors sv, fb;
+      two_phase_lists(r, s, n, p.blocks, 0u, &sv, &fb);
+      with_flags(d_tally != nullptr, p.verify, [&](auto T, auto V) {
+        if (p.schedule == CountSchedule::PROBE_THEN_RESUME) {
+          hipLaunchKernelGGL((count_nt2_probe_kernel<T(), V()>), g, b, 0, s, dv, d_words, n, L, d_counts, sv, d_tally);
+          hipLaunchKernelGGL((count_nt2_resume_kernel<T(), V()>), g, b, 0, s, dv, sv, L, d_counts, d_tally);
+        } else hipLaunchKernelGGL((count_nt2_probe_resume_kernel<T(), V()>), g, b, 0, s, dv, d_words, n, L, d_counts, sv, d_tally);
+      });
+      break;
+    }
+    case CountSchedule::QUAD4:
+      with_flags(p.seeded, d_tally != nullptr, p.verify, [&](auto S, auto T, auto V) {
+        hipLaunchKernelGGL((count_nt2_quad4_kernel<S(), T(), V()>), g, b, 0, s, r.dev, d_words, n, L, d_counts, d_tally);
+      });
+      break;
+    case CountSchedule::STRIDED_QUADS:
+      with_flags(p.seeded, d_tally != nullptr, [&](auto S, auto T) {
+        hipLaunchKernelGGL((count_nt2_quad_kernel<S(), T()>), g, b, 0, s, r.dev, d_words, n, L, d_counts, d_tally);
+      });
+      break;
+    default: require(false, "internal: not a schedule for k-mers");
   }
-  with_flags(seeded, d_tally != nullptr, [&](auto S, auto T) {
-    hipLaunchKernelGGL((count_nt2_quad_kernel<S(), T()>), g, b, 0, s, r.dev, d_words, n, L, d_counts, d_tally);
-  });
   HIP_CHECK(hipGetLastError());
 }
 

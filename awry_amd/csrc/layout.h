@@ -210,4 +210,8 @@ constexpr uint64_t RS_LCX = 3;     // matches found through the left-context ind
                                    //   of mask = entry j matched; bits 0..31 base, 32..47 letters left of the seed (i), 48..55
                                    //   mask.  The locate pass emits them in ascending BWT row (lcx_rowpos holds each entry's row).
 
+// limits the kernels of the two-phase count schedules share with the host's choice of schedule and grid (count_plan.h)
+constexpr int LIST_MAX_LISTS = 4096;  // per-block lists a pass can work through as one pool (QueryList::nlists): their prefix sums live in LDS
+constexpr int LCX_LF_CHUNK = 256;     // slots of the LF list a wave reserves at a time (16 quads x 2 slots append at most 32 per step)
+
 }  // namespace awry

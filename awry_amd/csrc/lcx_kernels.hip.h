@@ -24,7 +24,6 @@
 namespace awry {
 
 enum : int { LQ_IDLE = 0, LQ_FETCH, LQ_FETCH2, LQ_TAILCNT, LQ_SEARCH, LQ_POS, LQ_TXT, LQ_DONE };
-constexpr int LCX_LF_CHUNK = 256;  // slots of the LF list a wave reserves at a time (16 quads x 2 slots append at most 32 per step)
 
 // READS: survivors of count_nt2_reads_probe_kernel (in.w = the <= 32 letters left of the seed window, in.range = the probed
 // entry or ~0, in.q = the read); else survivors of count_nt2_probe_kernel (in.w = the k-mer).  out: the device-wide list of

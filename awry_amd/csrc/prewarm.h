@@ -38,12 +38,14 @@ void prewarm_host_paths(Replica& r) {
       if (ln.gpos.n < hits_cap) ln.gpos.alloc(hits_cap);
       if (ln.pos.n < 2 * hits_cap) ln.pos.alloc(2 * hits_cap);
     }
-    // scratch of the two-phase schedules on the lane streams (survivor lists of a full chunk)
+    // scratch of the two-phase schedules on the lane streams (survivor lists of a full chunk): for the grids the count plan
+    // gives a chunk of 31-mers and a chunk of 101-bp reads (no lists where neither is two-phase on this replica)
+    const CountFacts facts = count_facts(r);
     for (int li = 0; li < Replica::NLANES; li++) {
       Replica::SurvScratch* sc = surv_scratch(r, r.lane_stream[li]);
-      uint64_t total = 0;  // for the grid of the one-launch k-mer schedule and for num_cus * 8 blocks
-      for (const unsigned nblk : {(unsigned)r.num_cus * (unsigned)r.probe_resume_per_cu[1], (unsigned)r.num_cus * 8})
-        total = std::max<uint64_t>(total, list_slots_per_block(cap, nblk) * nblk);
+      uint64_t total = 0;
+      for (const unsigned nblk : {plan_kmers(facts, cap, 31, true, false).blocks, plan_reads(facts, cap, 101, true, false).blocks})
+        if (nblk) total = std::max<uint64_t>(total, list_slots_per_block(cap, nblk) * nblk);
       if (sc->cap < total) { sc->w.alloc(total); sc->range.alloc(total); sc->q.alloc(total); sc->cap = sc->cap_q = total; }
       if (!sc->count.p) sc->count.alloc((size_t)r.num_cus * 8);
       if (!sc->counters.p) sc->counters.alloc(8);

@@ -37,7 +37,7 @@ def test_every_included_header_is_watched():
         assert os.path.isfile(os.path.join(build.CSRC, f)), f
 
 
-@pytest.mark.parametrize("name", ["lcx.hip.h", "lcx_kernels.hip.h", "kernels.hip.h", "kernels_nt2_kmer.hip.h", os.path.join("..", "..", "include", "awry_hip.h")])
+@pytest.mark.parametrize("name", ["lcx.hip.h", "lcx_kernels.hip.h", "kernels.hip.h", "kernels_nt2_kmer.hip.h", "count_plan.h", os.path.join("..", "..", "include", "awry_hip.h")])
 def test_stale_sees_an_edited_header(monkeypatch, name):
     """stale() itself: with only `name` newer than the library, the library is stale; with nothing newer, it is not"""
     target = os.path.normpath(os.path.join(build.CSRC, name))
