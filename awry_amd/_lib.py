@@ -52,6 +52,13 @@ class MapClip(C.Structure):  # awry_map_clip_t
     _fields_ = Map._fields_ + [("score", C.c_int32), ("clip_left", C.c_uint16), ("clip_right", C.c_uint16)]
 
 
+class DebugAccel(C.Structure):  # awry_debug_accel_t
+    _fields_ = [("seed", C.c_void_p), ("seed_k", C.c_int32), ("seed_entry_bytes", C.c_int32), ("seed_pos", C.c_int32), ("ctx_extra", C.c_int32),
+                ("dense_sa", C.c_void_p), ("dense_ratio", C.c_uint64), ("text4", C.c_void_p), ("text4_words", C.c_uint64), ("text8", C.c_void_p),
+                ("sa_nblock", C.c_void_p), ("nblock_lo", C.c_uint64), ("nblock_hi", C.c_uint64), ("lcx_inner", C.c_void_p),
+                ("lcx_inner_words", C.c_uint64), ("lcx_off", C.c_uint32 * 8)]
+
+
 class BuildArgs(C.Structure):
     _fields_ = [("input_path", C.c_char_p), ("sa_tmp_path", C.c_char_p), ("sa_ratio", C.c_uint64),
                 ("kmer_len", C.c_uint8), ("alphabet", C.c_uint8), ("max_query_len", C.c_uint64),
@@ -111,6 +118,10 @@ def load_library():
     sig("awry_debug_force_wide_rows", i32, i32)
     sig("awry_debug_set_max_blocks", i32, i32)
     sig("awry_debug_max_blocks", i32)
+    sig("awry_debug_dense_sa", vp, vp, i32)
+    sig("awry_debug_accelerators", i32, vp, i32, C.POINTER(DebugAccel))
+    sig("awry_debug_seed_rung", vp, vp, i32, i32)
+    sig("awry_debug_set_ctx_extra_cap", i32, i32)
     sig("awry_count_schedule", cp, vp, i32)
     sig("awry_num_devices", i32, vp)
     sig("awry_replica_device", i32, vp, i32)

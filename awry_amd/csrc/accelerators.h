@@ -433,6 +433,10 @@ bool build_lcx(awry_index* ix, Replica& r) {
 // sparse enough for the two-phase schedules (the kernels of those schedules settle a singleton from the text and never
 // need its row; the other schedules and the generic kernel would have to start such queries over without the table).
 // Called after anything that changes the table or the accelerators.  AWRY_SEED_POS=0 keeps rows.
+// awry_debug_set_ctx_extra_cap: an upper bound on the extra context letters of tables converted afterwards; -1 (the
+// default): none.  For tests: the E = 0 and E = 2 of GRCh38- and chr1-scale indexes at a text of a few thousand letters.
+std::atomic<int> g_ctx_extra_cap{-1};
+
 void sync_seed_mode(awry_index* ix, Replica& r) {
   const HostIndex& h = ix->host;
   static const bool off = getenv("AWRY_SEED_POS") && !strcmp(getenv("AWRY_SEED_POS"), "0");
@@ -457,7 +461,8 @@ void sync_seed_mode(awry_index* ix, Replica& r) {
   uint64_t nfinal = 1;
   for (int j = 0; j < r.seed_k; j++) nfinal *= nt ? 4 : AA_SEED_SIGMA;
   // context letters beyond the 14 of the count field ride in the top bits of sp that positions of this text never use
-  const int extra = nt ? (int)std::min<uint64_t>(15, (32 - std::min<uint64_t>(32, h.sa_bits)) / 2) : 0;
+  int extra = nt ? (int)std::min<uint64_t>(15, (32 - std::min<uint64_t>(32, h.sa_bits)) / 2) : 0;
+  if (const int cap = g_ctx_extra_cap.load(); cap >= 0) extra = std::min(extra, cap);
   hipLaunchKernelGGL(seed_rows_to_positions_kernel, dim3(grid_for(r, nfinal, 256)), dim3(256), 0, r.stream, r.seed.p, nfinal, r.dense_sa.p,
                      nt ? SEED_CNT_SAT : AA_SEED_CNT_SAT, nt ? r.dev.text4 : nullptr, extra, nt ? nullptr : r.dev.text8);
   r.dev.ctx_extra = (uint32_t)extra;

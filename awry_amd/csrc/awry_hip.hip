@@ -926,6 +926,40 @@ int awry_debug_lcx(const awry_index_t* idx, int slot, const void** d_keys, const
 const void* awry_debug_dense_sa(const awry_index_t* idx, int slot) {
   return idx && slot >= 0 && slot < (int)idx->reps.size() ? (const void*)idx->reps[slot]->dense_sa.p : nullptr;
 }
+int awry_debug_accelerators(const awry_index_t* idx, int slot, awry_debug_accel_t* out) {
+  if (!idx || slot < 0 || slot >= (int)idx->reps.size() || !out) return AWRY_ERR_ARG;
+  const Replica& r = *idx->reps[slot];
+  *out = awry_debug_accel_t{};
+  out->seed = r.wide ? (const void*)r.seed64.p : (const void*)r.seed.p;
+  out->seed_k = out->seed ? r.seed_k : 0;
+  out->seed_entry_bytes = r.wide ? (int32_t)sizeof(SeedEntry64) : (int32_t)sizeof(SeedEntry);
+  out->seed_pos = (int32_t)r.dev.seed_pos;
+  out->ctx_extra = (int32_t)r.dev.ctx_extra;
+  out->dense_sa = r.dense_sa.p;
+  out->dense_ratio = r.dense_ratio;
+  out->text4 = r.text4.p;
+  out->text4_words = r.text4.p ? r.text4.n : 0;
+  out->text8 = r.text8.p;
+  out->sa_nblock = r.sa_nblock.p;
+  if (r.sa_nblock.p) {
+    out->nblock_lo = idx->host.prefix_sums[4];
+    out->nblock_hi = idx->host.prefix_sums[5];
+  }
+  out->lcx_inner = r.lcx_inner.p;
+  out->lcx_inner_words = r.lcx_inner.p ? r.lcx_inner.n : 0;
+  for (int t = 0; t < 8; t++) out->lcx_off[t] = r.dev.lcx_off[t];
+  return AWRY_OK;
+}
+const void* awry_debug_seed_rung(awry_index_t* idx, int slot, int L) {
+  const void* p = nullptr;
+  (void)guarded([&] { p = seed_rung(replica(idx, slot), L); });
+  return p;
+}
+int awry_debug_set_ctx_extra_cap(int cap) {
+  if (cap < -1) { g_last_error = "awry_debug_set_ctx_extra_cap: a cap below -1"; return AWRY_ERR_ARG; }
+  g_ctx_extra_cap.store(cap);
+  return AWRY_OK;
+}
 int awry_verify_enabled(const awry_index_t* idx) {
   return idx && !idx->reps.empty() && (idx->reps[0]->dev.text4 != nullptr || idx->reps[0]->dev.text8 != nullptr);
 }

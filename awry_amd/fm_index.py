@@ -1183,6 +1183,42 @@ class FmIndex:
         _check(self._L.awry_dev_memcpy_d2h(self._h, slot, rowpos.ctypes.data, rp, n * 8))
         return keys, rowpos
 
+    def debug_accelerators(self, slot=0) -> dict:
+        """replica `slot`'s device-only accelerators: device pointers (None: not resident) and sizes, the fields of
+        awry_debug_accel_t by name; valid until the next call that rebuilds accelerators"""
+        a = _lib.DebugAccel()
+        _check(self._L.awry_debug_accelerators(self._h, slot, C.byref(a)))
+        out = {n: getattr(a, n) for n, _ in _lib.DebugAccel._fields_}
+        out["lcx_off"] = [int(x) for x in a.lcx_off]
+        return out
+
+    def debug_seed_table(self, slot=0):
+        """-> the seed table of replica `slot`, copied: a structured array with fields sp and cnt (uint32, or uint64 for
+        16-byte wide-row entries) of sigma^seed_k entries, or None when there is none"""
+        a = self.debug_accelerators(slot)
+        if not a["seed"]:
+            return None
+        word = np.uint64 if a["seed_entry_bytes"] == 16 else np.uint32
+        n = (4 if self.alphabet() == NUCLEOTIDE else 21) ** a["seed_k"]
+        return self.dev_download(a["seed"], (n,), np.dtype([("sp", word), ("cnt", word)]), slot)
+
+    def debug_seed_rung(self, L: int, slot=0):
+        """-> the table for nucleotide k-mers of L < seed k letters (built if absent) as debug_seed_table's array, or None
+        where a launch would get none"""
+        p = self._L.awry_debug_seed_rung(self._h, slot, int(L))
+        if not p:
+            return None
+        return self.dev_download(p, (4 ** int(L),), np.dtype([("sp", np.uint32), ("cnt", np.uint32)]), slot)
+
+    def debug_dense_sa(self, slot=0):
+        """-> (uint32 SA[j * ratio] copied from replica `slot`, ratio), or None when no dense SA is resident"""
+        p = self._L.awry_debug_dense_sa(self._h, slot)
+        a = self.debug_accelerators(slot)
+        if not p:
+            return None
+        ratio = int(a["dense_ratio"])
+        return self.dev_download(p, ((self.bwt_len() + ratio - 1) // ratio,), np.uint32, slot), ratio
+
     def dev_stream_copy(self, d_dst, d_src, nbytes, stream=None, slot=0):
         _check(self._L.awry_dev_stream_copy(self._h, slot, d_dst, d_src, nbytes, stream))
 

@@ -108,6 +108,40 @@ int awry_debug_set_max_blocks(int blocks);
 int awry_debug_max_blocks(void);
 /* device pointer of replica `slot`'s dense SA (u32 SA[j * ratio]) or NULL -- for tests that dump it */
 const void *awry_debug_dense_sa(const awry_index_t *idx, int slot);
+/* The device-only accelerators of replica `slot`, for tests that audit them against the text.  Every pointer is read-only
+ * device memory (NULL: the structure is not resident) and stays valid until the next call that rebuilds accelerators
+ * (awry_set_devices, awry_set_seed_kmer_len, awry_set_verify, awry_set_locate_sa_ratio, awry_set_lcx); copy out with
+ * awry_dev_memcpy_d2h.
+ *   seed: sigma^seed_k entries of seed_entry_bytes bytes (8: u32 sp, u32 cnt; 16, wide rows: u64 sp, u64 cnt; sigma = 4
+ *         nucleotide, 21 amino); seed_pos != 0: singleton entries hold text positions, with 14 + ctx_extra context letters
+ *   dense_sa: u32 SA[j * dense_ratio], j < ceil(bwt_len / dense_ratio)
+ *   text4: text4_words u32 of eight 4-bit codes (A0 C1 G2 T3, else 8), zero past the text;  text8: bwt_len symbol indices
+ *   sa_nblock: u32 SA of the rows [nblock_lo, nblock_hi), those whose suffix starts with N
+ *   lcx_inner: lcx_inner_words u64, the sampled levels of the left-context index, level t = 1..7 at word lcx_off[t] */
+typedef struct {
+  const void *seed;
+  int32_t seed_k, seed_entry_bytes, seed_pos, ctx_extra;
+  const void *dense_sa;
+  uint64_t dense_ratio;
+  const void *text4;
+  uint64_t text4_words;
+  const void *text8;
+  const void *sa_nblock;
+  uint64_t nblock_lo, nblock_hi;
+  const void *lcx_inner;
+  uint64_t lcx_inner_words;
+  uint32_t lcx_off[8];
+} awry_debug_accel_t;
+int awry_debug_accelerators(const awry_index_t *idx, int slot, awry_debug_accel_t *out);
+/* device pointer of replica `slot`'s table for nucleotide k-mers of L < seed k letters (4^L entries of 8 bytes, rows, the BWT
+ * symbol of singletons), built if it is not resident; NULL where a launch would get none (length outside the rungs' range,
+ * wide rows, amino, no room, AWRY_SEED_RUNGS=0).  Valid as long as the replica. */
+const void *awry_debug_seed_rung(awry_index_t *idx, int slot, int L);
+/* An upper bound on E, the context letters a position seed keeps beyond 14 (process-wide; -1, the default: none; below -1:
+ * AWRY_ERR_ARG).  Seed tables converted to position seeds AFTERWARDS keep min(E, cap) extra letters.  For tests: E is
+ * min(15, (32 - sa bits) / 2), so that a text of test size never has the E = 0 of a GRCh38-scale index or the E = 2 of a
+ * chr1-scale one.  Results do not depend on it. */
+int awry_debug_set_ctx_extra_cap(int cap);
 /* name(s) of the kernel(s) awry_dev_count_nt2 launches for k-mers of length L on replica 0 (for profiling reports) */
 const char *awry_count_schedule(const awry_index_t *idx, int L);
 /* device-side SA sampling used by locate (performance knob only; locations do not depend on it): 0 = walk to the
