@@ -15,5 +15,6 @@ from .fm_index import (  # noqa: F401
     SymbolAlphabet,
     cigar_string,
     pattern_class,
+    sa_tags,
 )
 from ._lib import lib_path, load_library  # noqa: F401

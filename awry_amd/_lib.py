@@ -52,6 +52,10 @@ class MapClip(C.Structure):  # awry_map_clip_t
     _fields_ = Map._fields_ + [("score", C.c_int32), ("clip_left", C.c_uint16), ("clip_right", C.c_uint16)]
 
 
+class MapSplit(C.Structure):  # awry_map_split_t
+    _fields_ = MapClip._fields_ + [("q_begin", C.c_uint16), ("q_end", C.c_uint16), ("parent", C.c_uint16), ("reserved", C.c_uint16)]
+
+
 class DebugAccel(C.Structure):  # awry_debug_accel_t
     _fields_ = [("seed", C.c_void_p), ("seed_k", C.c_int32), ("seed_entry_bytes", C.c_int32), ("seed_pos", C.c_int32), ("ctx_extra", C.c_int32),
                 ("dense_sa", C.c_void_p), ("dense_ratio", C.c_uint64), ("text4", C.c_void_p), ("text4_words", C.c_uint64), ("text8", C.c_void_p),
@@ -170,6 +174,9 @@ def load_library():
     sig("awry_map_clip_batch", i32, vp, vp, u64p, u64, u32, u64, u32, u32, u32, u32, u32, u64, u64, u32, u32, u32, u32, u32, u32, C.POINTER(u64p),
         C.POINTER(C.POINTER(MapClip)), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)), C.POINTER(u8p))
     sig("awry_dev_map_select_clip", i32, vp, i32, vp, vp, vp, vp, u64, u32, u32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp)
+    sig("awry_map_split_batch", i32, vp, vp, u64p, u64, u32, u64, u32, u32, u32, u32, u32, u64, u64, u64, u32, u32, u32, u32, u32, u32, u32, C.POINTER(u64p),
+        C.POINTER(C.POINTER(MapSplit)), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)), C.POINTER(u8p))
+    sig("awry_dev_map_select_split", i32, vp, i32, vp, vp, vp, vp, vp, u64, u32, u32, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp)
     sig("awry_map_pairs_batch", i32, vp, vp, u64p, u64, u32, u64, u32, u32, u32, u32, u32, u64, u32, u64, u64, u32, u32, i32, C.POINTER(u64p),
         C.POINTER(C.POINTER(Map)), C.POINTER(C.POINTER(Pos)), C.POINTER(u64p), C.POINTER(C.POINTER(u32)), C.POINTER(u8p), C.POINTER(C.POINTER(u32)))
     sig("awry_dev_pair_windows", i32, vp, i32, vp, vp, vp, u64, u64, u64, u32, i32, vp, vp, vp, vp)

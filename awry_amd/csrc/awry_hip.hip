@@ -13,6 +13,7 @@
 #include "edit_host.h"
 #include "chain_align_host.h"
 #include "map_host.h"
+#include "split_host.h"
 #include "pair_host.h"
 #include "prewarm.h"
 
@@ -519,6 +520,25 @@ int awry_map_clip_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t
     require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
     map_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, (uint32_t)max_report, band, md, clip_map_mode(md, min_aln_score),
               map_off_out, maps_out, pos_out, cigar_off_out, cigar_out, status_out);
+  });
+}
+
+int awry_map_split_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits, uint32_t max_seeds,
+                         uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score, uint64_t chains_per_strand, uint64_t max_segments,
+                         uint64_t max_secondary, uint32_t max_overlap, uint32_t band, uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus,
+                         uint32_t min_aln_score, uint64_t** map_off_out, awry_map_split_t** maps_out, awry_pos_t** pos_out, uint64_t** cigar_off_out,
+                         uint32_t** cigar_out, uint8_t** status_out) {
+  return guarded([&] {
+    require(idx && qoff && map_off_out, "null argument");
+    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    require_smem_args(min_len);
+    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
+    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    const SplitParams sp = split_params(chains_per_strand, max_segments, max_secondary, max_overlap, band);
+    const AlignMode md = clip_mode(match, mismatch, gap, end_bonus);
+    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
+    split_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, sp, band, md, clip_map_mode(md, min_aln_score), map_off_out, maps_out,
+                pos_out, cigar_off_out, cigar_out, status_out);
   });
 }
 
@@ -1232,6 +1252,21 @@ int awry_dev_map_select_clip(awry_index_t* idx, int slot, const uint64_t* d_aln_
     require(n == 0 || (d_aln_off && d_alns && d_chains && (d_map_off ? d_maps != nullptr : d_n_maps != nullptr)), "null device pointer");
     launch_map_select(r, d_aln_off, d_alns, reinterpret_cast<const Chain*>(d_chains), d_chain_status, n, chains_per_strand, max_report, mm, d_n_maps,
                       d_read_status, d_map_off, d_maps, d_sel, reinterpret_cast<uint64_t*>(d_pos), (hipStream_t)stream);
+  });
+}
+
+int awry_dev_map_select_split(awry_index_t* idx, int slot, const uint64_t* d_aln_off, const awry_aln_clip_t* d_alns, const awry_chain_t* d_chains,
+                              const uint8_t* d_chain_status, const uint64_t* d_qoff, uint64_t n, uint32_t chains_per_strand, uint32_t max_segments,
+                              uint32_t max_secondary, uint32_t max_overlap, uint32_t match, uint32_t mismatch, uint32_t min_aln_score, uint64_t* d_n_maps,
+                              uint8_t* d_read_status, const uint64_t* d_map_off, awry_map_split_t* d_maps, uint32_t* d_sel, awry_pos_t* d_pos, void* stream) {
+  return guarded([&] {
+    const SplitParams sp = split_params(chains_per_strand, max_segments, max_secondary, max_overlap, 0);
+    const MapMode mm = clip_map_mode(clip_mode(match, mismatch, 0, 0), min_aln_score);
+    Replica& r = replica(idx, slot);
+    require(n == 0 || (d_aln_off && d_alns && d_chains && d_qoff && (d_map_off ? d_maps != nullptr : d_n_maps != nullptr)), "null device pointer");
+    launch_map_split_select(r, d_aln_off, reinterpret_cast<const AlnClip*>(d_alns), reinterpret_cast<const Chain*>(d_chains), d_chain_status, d_qoff, 1, n,
+                            chains_per_strand, sp, mm, d_n_maps, d_read_status, d_map_off, reinterpret_cast<MapSplitRec*>(d_maps), d_sel,
+                            reinterpret_cast<uint64_t*>(d_pos), (hipStream_t)stream);
   });
 }
 

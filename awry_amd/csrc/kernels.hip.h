@@ -53,6 +53,9 @@
 //                         + MAP_SELECT_KERNEL<FILL>          one read per lane: rank the aligned chains of both strands by selection, drop
 //                                                            redundant spans, MAPQ; count pass, scan, fill pass [kernels_map]
 //                         + MAP_GATHER_KERNEL                the reported alignments as a chain list for the CIGAR fill pass [kernels_map]
+//   split reads           MAP_SPLIT_SELECT_KERNEL<FILL>      one read per lane: the clipped candidates walked in rank order by query interval --
+//                                                            segments (primary, supplementaries), their secondaries, a MAPQ per segment;
+//                                                            classify, then emit; count pass, scan, fill pass [kernels_split]
 //   map read pairs        PAIR_WINDOWS_KERNEL<Rec>           one candidate slot per lane: is it an anchor, and the window of starts in which it
 //                                                            expects the other mate [kernels_pair]
 //                         + pair_sub_windows / PAIR_BEST_HIT / PAIR_RESCUED<Rec> kernels: windows cut for the edit scan, the smallest (distance,
@@ -584,4 +587,5 @@ __global__ __launch_bounds__(256) void locate_walk_nt_lane_kernel(DevIndex ix, u
 #include "kernels_chain.hip.h"     // localise, tally_add, Anchor
 #include "kernels_chain_align.hip.h"  // Seed, Chain, ByteStream, edit_symbols, align_bam_op
 #include "kernels_map.hip.h"       // Aln, Chain, Seed, localise
+#include "kernels_split.hip.h"     // AlnClip, Chain, MapMode, map_key, localise
 #include "kernels_pair.hip.h"      // MapRec, localise, EDIT_MAX_LEN

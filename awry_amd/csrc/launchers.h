@@ -643,6 +643,22 @@ void launch_map_select(Replica& r, const uint64_t* d_aln_off, const void* d_alns
   HIP_CHECK(hipGetLastError());
 }
 
+// The split selection over the clipped alignment records of a doubled batch of n reads (kernels_split.hip.h): launch_map_select's
+// protocol and outputs with MapSplitRec records.  qstride: 1 when d_qoff holds the reads' own n + 1 offsets, 2 when it holds the
+// doubled batch's 2 n + 1; only the lengths are read.
+void launch_map_split_select(Replica& r, const uint64_t* d_aln_off, const AlnClip* d_alns, const Chain* d_chains, const uint8_t* d_chain_status,
+                             const uint64_t* d_qoff, uint32_t qstride, uint64_t n, uint32_t chains_per_strand, const SplitParams& sp, const MapMode& md,
+                             uint64_t* d_n_maps, uint8_t* d_read_status, const uint64_t* d_map_off, MapSplitRec* d_maps, uint32_t* d_sel, uint64_t* d_pos,
+                             hipStream_t s) {
+  if (n == 0) return;
+  require(md.clip, "internal: the split selection reads clipped records");
+  with_flags(d_map_off != nullptr, [&](auto F) {
+    hipLaunchKernelGGL((map_split_select_kernel<F()>), dim3(grid_for(r, n, 256)), dim3(256), 0, s, r.dev, d_aln_off, d_alns, d_chains, d_chain_status, d_qoff,
+                       qstride, n, chains_per_strand, sp, d_n_maps, d_read_status, d_map_off, d_maps, d_sel, d_pos, md);
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
 // The rescue windows of P pairs (kernels_pair.hip.h): 2 P rescue_anchors slots at a fixed stride.  qstride: 1 when d_qoff holds the
 // reads' own 2 P + 1 offsets, 2 when it holds the doubled batch's.  Rec: MapRec end to end, MapClipRec in the clipped mode.
 template <class Rec>

@@ -67,12 +67,13 @@ void fill_reported_cigars(Replica& r, const uint8_t* text8, const ChainOnDevice&
 // One chunk, from where chain_chunk's fill pass leaves the doubled batch: the first min(n_chains, A) chains of each of the 2 n
 // queries, the alignment count pass over all of them in sub-batches (before anything else: the selection needs every record),
 // the selection per read, and the CIGAR fill over the reported alignments, appended to `out`.  MapT is the record of the mode (md
-// for the alignment, mm for the selection).
-template <class MapT>
-void map_chunk(Replica& r, const uint8_t* text8, const ChainOnDevice& v, uint32_t A, uint32_t R, int band, const AlignMode& md, const MapMode& mm, bool want_pos,
-               bool want_cigar, MapHitsOf<MapT>& out) {
-  constexpr bool CLIP = std::is_same_v<MapT, awry_map_clip_t>;
-  require(md.clip == CLIP && mm.clip == CLIP, "internal: the map records are not the mode's");
+// for the alignment).  The selection is the caller's: select(S, alns, n_maps, read_status, map_off, maps, sel, pos) queues its count
+// pass (map_off == nullptr) or its fill pass on the replica's stream; map_chunk below and split_chunk (split_host.h) each pass theirs.
+template <class MapT, class Select>
+void select_chunk(Replica& r, const uint8_t* text8, const ChainOnDevice& v, uint32_t A, int band, const AlignMode& md, bool want_pos, bool want_cigar,
+                  MapHitsOf<MapT>& out, const Select& select) {
+  constexpr bool CLIP = !std::is_same_v<MapT, awry_map_t>;
+  require(md.clip == CLIP, "internal: the map records are not the mode's");
   const hipStream_t s = r.stream;
   const uint64_t n = v.c.hi - v.c.lo, n2 = 2 * n;
   uint64_t Lmax = 1;
@@ -93,7 +94,7 @@ void map_chunk(Replica& r, const uint8_t* text8, const ChainOnDevice& v, uint32_
   // the selection: records per read, a scan, the records
   DevBuf<uint64_t> nmaps(n), moff(n + 1);
   DevBuf<uint8_t> rstatus(n);
-  launch_map_select(r, S.aoff.p, alns.p, S.chains.p, v.status, n, A, R, mm, nmaps.p, rstatus.p, nullptr, nullptr, nullptr, nullptr, s);
+  select(S, alns.p, nmaps.p, rstatus.p, nullptr, nullptr, nullptr, nullptr);
   launch_scan(r, nmaps.p, n, moff.p, S.scratch.p, s);
   uint64_t nwin = 0;
   const size_t at_q = out.n_maps.size(), at_m = out.maps.size();
@@ -105,10 +106,10 @@ void map_chunk(Replica& r, const uint8_t* text8, const ChainOnDevice& v, uint32_
   HIP_CHECK(hipStreamSynchronize(s));
   require(nwin <= total, "internal: more records than candidates");
   if (!nwin) return;
-  DevBuf<MapRecOf<CLIP>> maps(nwin);
+  DevBuf<MapT> maps(nwin);  // (the kernels' records are the header's: the static_asserts)
   DevBuf<uint32_t> win(nwin);
   DevBuf<uint64_t> pos(want_pos ? 2 * nwin : 0);
-  launch_map_select(r, S.aoff.p, alns.p, S.chains.p, v.status, n, A, R, mm, nullptr, nullptr, moff.p, maps.p, win.p, want_pos ? pos.p : nullptr, s);
+  select(S, alns.p, nullptr, nullptr, moff.p, maps.p, win.p, want_pos ? pos.p : nullptr);
   out.maps.resize(at_m + nwin);
   HIP_CHECK(hipMemcpyAsync(out.maps.data() + at_m, maps.p, nwin * sizeof(MapT), hipMemcpyDeviceToHost, s));
   if (want_pos) {
@@ -123,13 +124,26 @@ void map_chunk(Replica& r, const uint8_t* text8, const ChainOnDevice& v, uint32_
   fill_reported_cigars(r, text8, v, S, nops.p, win.p, nwin, band, md, (uint32_t)Lmax, out.n_ops.data() + at_m, out.cigar);
 }
 
+// select_chunk with the selection of awry_map_batch (mm: end to end or clipped, as md)
+template <class MapT>
+void map_chunk(Replica& r, const uint8_t* text8, const ChainOnDevice& v, uint32_t A, uint32_t R, int band, const AlignMode& md, const MapMode& mm, bool want_pos,
+               bool want_cigar, MapHitsOf<MapT>& out) {
+  require(mm.clip == md.clip, "internal: the map records are not the mode's");
+  const uint64_t n = v.c.hi - v.c.lo;
+  select_chunk(r, text8, v, A, band, md, want_pos, want_cigar, out,
+               [&](const SelectedChains& S, const void* alns, uint64_t* n_maps, uint8_t* read_status, const uint64_t* map_off, void* maps, uint32_t* sel, uint64_t* pos) {
+                 launch_map_select(r, S.aoff.p, alns, S.chains.p, v.status, n, A, R, mm, n_maps, read_status, map_off, maps, sel, pos, r.stream);
+               });
+}
+
 // awry_map_batch: shards over the replicas, results stitched in read order into pinned-pool arrays.  The out-pointers are written
 // only when everything has succeeded.  awry_map_clip_batch is the same with the clipped modes and MapT = awry_map_clip_t.
-template <class MapT>
-void map_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits, const ChainParams& P,
-               uint32_t chains_per_strand, uint32_t max_report, uint32_t band, const AlignMode& md, const MapMode& mm, uint64_t** map_off_out, MapT** maps_out,
-               awry_pos_t** pos_out,
-               uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out) {
+// The chunk's work is the caller's: chunk(replica, text8, chain view, want_pos, want_cigar, the shard's hits) is map_chunk for
+// map_batch below and split_chunk for split_batch (split_host.h).
+template <class MapT, class Chunk>
+void map_batch_over(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits, const ChainParams& P,
+                    uint64_t** map_off_out, MapT** maps_out, awry_pos_t** pos_out, uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out,
+                    const Chunk& chunk) {
   if (idx->host.alphabet != NUCLEOTIDE) throw ArgError("mapping on both strands needs a nucleotide index");
   require_chain_index(idx->host.bwt_len);
   require_chain_align_lengths(qoff, n);
@@ -139,9 +153,7 @@ void map_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uin
   for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
     HIP_CHECK(hipSetDevice(r.device));
     const uint8_t* text8 = edit_text(r);
-    const auto sink = [&, g, text8](Replica& rr, const ChainOnDevice& v) {
-      map_chunk(rr, text8, v, chains_per_strand, max_report, (int)band, md, mm, want_pos, want_cigar, res[g]);
-    };
+    const auto sink = [&, g, text8](Replica& rr, const ChainOnDevice& v) { chunk(rr, text8, v, want_pos, want_cigar, res[g]); };
     for (Shard c : chunk_queries(qoff, sh.lo, sh.hi, 2))  // halves between reads, never between a read's strands
       halve_until_fits(c, [&](Shard h) { return chain_chunk(r, qbytes, qoff, h, min_len, max_hits, P, true, sink); });
   });
@@ -163,6 +175,17 @@ void map_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uin
   if (want_pos) *pos_out = pos.release();
   if (want_cigar) { *cigar_off_out = coff.release(); *cigar_out = cg.release(); }
   if (status_out) *status_out = st.release();
+}
+
+template <class MapT>
+void map_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits, const ChainParams& P,
+               uint32_t chains_per_strand, uint32_t max_report, uint32_t band, const AlignMode& md, const MapMode& mm, uint64_t** map_off_out, MapT** maps_out,
+               awry_pos_t** pos_out,
+               uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out) {
+  map_batch_over(idx, qbytes, qoff, n, min_len, max_hits, P, map_off_out, maps_out, pos_out, cigar_off_out, cigar_out, status_out,
+                 [&](Replica& r, const uint8_t* text8, const ChainOnDevice& v, bool want_pos, bool want_cigar, MapHitsOf<MapT>& out) {
+                   map_chunk(r, text8, v, chains_per_strand, max_report, (int)band, md, mm, want_pos, want_cigar, out);
+                 });
 }
 
 }  // namespace

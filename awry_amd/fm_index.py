@@ -34,6 +34,7 @@ CHAIN_MAX_SEEDS, CHAIN_MAX_LOOKBACK, Q_SEED_CAP = 4096, 64, 8  # AWRY_CHAIN_MAX_
 CHAIN_ALIGN_MAX_BAND, CHAIN_ALIGN_MAX_SKEW, CHAIN_ALIGN_MAX_LEN = 8, 16, 1024  # AWRY_CHAIN_ALIGN_MAX_BAND, _MAX_SKEW, _MAX_LEN
 ALN_OK, ALN_SKEW, ALN_BAD_CHAIN = 0, 1, 2  # AWRY_ALN_OK, AWRY_ALN_SKEW, AWRY_ALN_BAD_CHAIN
 MAP_MAX_CHAINS, MAP_SECONDARY = 8, 1  # AWRY_MAP_MAX_CHAINS, AWRY_MAP_SECONDARY
+MAP_SUPPLEMENTARY, SPLIT_MAX_SEGMENTS = 16, 4  # AWRY_MAP_SUPPLEMENTARY, AWRY_SPLIT_MAX_SEGMENTS
 MAP_PROPER_PAIR, MAP_RESCUED, MAP_MATE_UNMAPPED = 2, 4, 8  # AWRY_MAP_PROPER_PAIR, AWRY_MAP_RESCUED, AWRY_MAP_MATE_UNMAPPED
 PAIR_MAX_INSERT, PAIR_MAX_ANCHORS, PAIR_NO_CHAIN = 1 << 20, 4, 0xFFFFFFFF  # AWRY_PAIR_MAX_INSERT, AWRY_PAIR_MAX_ANCHORS, AWRY_PAIR_NO_CHAIN
 CLIP_MAX_MATCH, CLIP_MAX_PENALTY, CLIP_MAX_END_BONUS = 16, 64, 1024  # AWRY_CLIP_MAX_MATCH, AWRY_CLIP_MAX_PENALTY, AWRY_CLIP_MAX_END_BONUS
@@ -43,6 +44,15 @@ CIGAR_OPS = {1: "I", 2: "D", 4: "S", 7: "=", 8: "X"}  # the BAM op codes the ali
 def cigar_string(ops) -> str:
     """runs (len << 4 | BAM op) -> the CIGAR string, "57=1X43=" """
     return "".join("%d%s" % (int(v) >> 4, CIGAR_OPS[int(v) & 15]) for v in ops)
+
+
+def sa_tags(records, headers):
+    """the SA:Z values of one read's records as parallel_map_split returns them, headers[r] the name of record r: per record, for a
+    segment the entries "rname,pos1,+/-,CIGAR,mapq,edits;" of its sibling segments in their order (pos1 is 1-based; "" for a read of one
+    segment), for a secondary None"""
+    segs = [r for r in records if not r[6] & MAP_SECONDARY]
+    entry = lambda r: "%s,%d,%s,%s,%d,%d;" % (headers[r[0]], r[1] + 1, "-" if r[2] else "+", r[5], r[3], r[4])
+    return [None if r[6] & MAP_SECONDARY else "".join(entry(g) for g in segs if g is not r) for r in records]
 
 
 @dataclass
@@ -117,6 +127,8 @@ MAP_DTYPE = np.dtype([("t_begin", np.uint64), ("t_end", np.uint64), ("edits", np
 _CLIP_FIELDS = [("score", np.int32), ("clip_left", np.uint16), ("clip_right", np.uint16)]
 ALN_CLIP_DTYPE = np.dtype(ALN_DTYPE.descr + _CLIP_FIELDS)  # awry_aln_clip_t, 32 bytes
 MAP_CLIP_DTYPE = np.dtype(MAP_DTYPE.descr + _CLIP_FIELDS)  # awry_map_clip_t, 40 bytes
+MAP_SPLIT_DTYPE = np.dtype(MAP_CLIP_DTYPE.descr + [("q_begin", np.uint16), ("q_end", np.uint16), ("parent", np.uint16),
+                                                   ("reserved", np.uint16)])  # awry_map_split_t, 48 bytes
 
 
 class _Owned:
@@ -832,15 +844,19 @@ class FmIndex:
                              want_pos, want_cigar)
 
     def _map_csr(self, clip, qbytes, qoff, min_len, max_hits, chains_per_strand, max_report, band, max_seeds, lookback, max_gap, max_skew, min_score,
-                 want_pos, want_cigar):
-        """awry_map_batch (clip None), or awry_map_clip_batch with clip = (match, mismatch, gap, end_bonus, min_aln_score)"""
+                 want_pos, want_cigar, split=None):
+        """awry_map_batch (clip None), or awry_map_clip_batch with clip = (match, mismatch, gap, end_bonus, min_aln_score), or
+        awry_map_split_batch with that and split = (max_segments, max_secondary, max_overlap) in the place of max_report"""
         qb = np.ascontiguousarray(qbytes, dtype=np.uint8)
         qo = np.ascontiguousarray(qoff, dtype=np.uint64)
         n = len(qo) - 1
         fn, rec, dt = (self._L.awry_map_batch, _lib.Map, MAP_DTYPE) if clip is None else (self._L.awry_map_clip_batch, _lib.MapClip, MAP_CLIP_DTYPE)
+        if split is not None:
+            fn, rec, dt = self._L.awry_map_split_batch, _lib.MapSplit, MAP_SPLIT_DTYPE
+        report = [int(max_report)] if split is None else [int(x) for x in split]
         off, mp, ps, coff, cg, st = _u64p(), C.POINTER(rec)(), C.POINTER(_lib.Pos)(), _u64p(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint8)()
         _check(fn(self._h, qb.ctypes.data, qo.ctypes.data_as(_u64p), n, int(min_len), int(max_hits), int(max_seeds), int(lookback), int(max_gap),
-                  int(max_skew), int(min_score), int(chains_per_strand), int(max_report), int(band), *(() if clip is None else [int(x) for x in clip]),
+                  int(max_skew), int(min_score), int(chains_per_strand), *report, int(band), *(() if clip is None else [int(x) for x in clip]),
                   C.byref(off), C.byref(mp), C.byref(ps) if want_pos else None, C.byref(coff) if want_cigar else None,
                   C.byref(cg) if want_cigar else None, C.byref(st)))
         offs = _adopt(self._L, off, n + 1, np.uint64)
@@ -913,6 +929,46 @@ class FmIndex:
         _check(self._L.awry_dev_map_select_clip(self._h, slot, d_aln_off, d_alns, d_chains, d_chain_status, n, int(chains_per_strand), int(max_report),
                                                 int(match), int(mismatch), int(gap), int(end_bonus), int(min_aln_score), d_n_maps, d_read_status,
                                                 d_map_off, d_maps, d_sel, d_pos, stream))
+
+    # ------------------------------------------------------------------ split reads: supplementary alignments by query overlap
+    def parallel_map_split_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4,
+                               max_segments: int = 2, max_secondary: int = 0, max_overlap: int = 50, band: int = 4, match: int = 1, mismatch: int = 4,
+                               gap: int = 6, end_bonus: int = 5, min_aln_score: int = 0, max_seeds: int = 1024, lookback: int = 32, max_gap: int = 1000,
+                               max_skew: int = 100, min_score: int = 20, want_pos: bool = True, want_cigar: bool = True):
+        """parallel_map_clip_csr with the selection by query interval (include/awry_hip.h, "split reads"): maps is MAP_SPLIT_DTYPE.  Per
+        read first its segments -- up to max_segments clipped alignments that explain different letters [q_begin, q_end) of the read, the
+        primary and then the supplementaries (MAP_SUPPLEMENTARY in flags), each with a mapq of its own -- then up to max_secondary
+        secondaries (MAP_SECONDARY, mapq 0), each overlapping its segment `parent` (an index among the read's records) by at least
+        max_overlap percent of the shorter of the two intervals"""
+        return self._map_csr((match, mismatch, gap, end_bonus, min_aln_score), qbytes, qoff, min_len, max_hits, chains_per_strand, None, band, max_seeds,
+                             lookback, max_gap, max_skew, min_score, want_pos, want_cigar, split=(max_segments, max_secondary, max_overlap))
+
+    def parallel_map_split(self, queries: Iterable, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4, max_segments: int = 2,
+                           max_secondary: int = 0, max_overlap: int = 50, band: int = 4, match: int = 1, mismatch: int = 4, gap: int = 6,
+                           end_bonus: int = 5, min_aln_score: int = 0, **chain_params):
+        """-> per read, [(record, offset, strand, mapq, edits, "60=41S", flags, score, q_begin, q_end, parent)] of its segments and then its
+        secondaries; chain_params: max_seeds, lookback, max_gap, max_skew, min_score"""
+        off, mp, pos, coff, cg, _ = self.parallel_map_split_csr(*pack_queries(queries), min_len, max_hits, chains_per_strand, max_segments, max_secondary,
+                                                                max_overlap, band, match, mismatch, gap, end_bonus, min_aln_score, **chain_params)
+        return [[(int(pos[c][0]), int(pos[c][1]), int(mp[c]["strand"]), int(mp[c]["mapq"]), int(mp[c]["edits"]), cigar_string(cg[coff[c]:coff[c + 1]]),
+                  int(mp[c]["flags"]), int(mp[c]["score"]), int(mp[c]["q_begin"]), int(mp[c]["q_end"]), int(mp[c]["parent"]))
+                 for c in range(int(off[i]), int(off[i + 1]))] for i in range(len(off) - 1)]
+
+    def map_split_string(self, query, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4, max_segments: int = 2, max_secondary: int = 0,
+                         max_overlap: int = 50, band: int = 4, match: int = 1, mismatch: int = 4, gap: int = 6, end_bonus: int = 5, min_aln_score: int = 0,
+                         **chain_params):
+        """segments and secondaries of one read over both strands"""
+        return self.parallel_map_split([query], min_len, max_hits, chains_per_strand, max_segments, max_secondary, max_overlap, band, match, mismatch, gap,
+                                       end_bonus, min_aln_score, **chain_params)[0]
+
+    def dev_map_select_split(self, d_aln_off, d_alns, d_chains, d_chain_status, d_qoff, n, chains_per_strand, max_segments, max_secondary, max_overlap,
+                             match, mismatch, min_aln_score, d_n_maps, d_read_status=None, d_map_off=None, d_maps=None, d_sel=None, d_pos=None, stream=None,
+                             slot=0):
+        """dev_map_select_clip with the split selection: 32-byte ALN_CLIP_DTYPE records in, 48-byte MAP_SPLIT_DTYPE records out; d_qoff
+        holds the reads' own n + 1 offsets (u64), of which only the lengths are read"""
+        _check(self._L.awry_dev_map_select_split(self._h, slot, d_aln_off, d_alns, d_chains, d_chain_status, d_qoff, n, int(chains_per_strand),
+                                                 int(max_segments), int(max_secondary), int(max_overlap), int(match), int(mismatch), int(min_aln_score),
+                                                 d_n_maps, d_read_status, d_map_off, d_maps, d_sel, d_pos, stream))
 
     # ------------------------------------------------------------------ map read pairs: insert-size pairing, mate rescue, proper-pair flag
     def parallel_map_pairs_csr(self, qbytes: np.ndarray, qoff: np.ndarray, min_len: int = 12, max_hits: int = 50, chains_per_strand: int = 4,

@@ -482,6 +482,47 @@ class FmIndex {
                                               uint64_t max_report = 1, uint32_t band = 4, ClipParams c = ClipParams(), ChainParams p = ChainParams()) {
     return parallel_map_clip(std::vector<std::string_view>{std::string_view(query)}, min_len, max_hits, chains_per_strand, max_report, band, c, p)[0];
   }
+  // Split reads (no counterpart in the reference; the definition is in awry_hip.h, "split reads"): parallel_map_clip with the kept
+  // candidates sorted by the part of the read they explain.  Per read first its segments -- up to max_segments clipped alignments over
+  // different letters [q_begin, q_end) of the read, the primary and then the supplementaries (AWRY_MAP_SUPPLEMENTARY), each with a
+  // mapping quality of its own -- then up to max_secondary secondaries, each overlapping the segment map.parent (an index among the
+  // read's records) by at least max_overlap percent of the shorter interval.
+  struct SplitParams {
+    uint64_t max_segments = 2, max_secondary = 0;
+    uint32_t max_overlap = 50;
+  };
+  struct SplitMapping {
+    awry_pos_t pos;
+    awry_map_split_t map;
+    std::vector<uint32_t> cigar;
+    std::string cigar_string() const { return cigar_text(cigar); }
+    bool secondary() const { return (map.flags & AWRY_MAP_SECONDARY) != 0; }
+    bool supplementary() const { return (map.flags & AWRY_MAP_SUPPLEMENTARY) != 0; }
+  };
+  template <class StrRange>
+  std::vector<std::vector<SplitMapping>> parallel_map_split(const StrRange& queries, uint32_t min_len = 12, uint64_t max_hits = 50,
+                                                            uint64_t chains_per_strand = 4, SplitParams sp = SplitParams(), uint32_t band = 4,
+                                                            ClipParams c = ClipParams(), ChainParams p = ChainParams(),
+                                                            std::vector<uint8_t>* status = nullptr) {
+    std::vector<uint8_t> bytes; std::vector<uint64_t> off;
+    pack(queries, bytes, off);
+    const uint64_t n = off.size() - 1;
+    uint64_t* moff = nullptr; awry_map_split_t* mp = nullptr; awry_pos_t* ps = nullptr; uint64_t* coff = nullptr; uint32_t* cg = nullptr; uint8_t* st = nullptr;
+    check(awry_map_split_batch(h_, bytes.data(), off.data(), n, min_len, max_hits, p.max_seeds, p.lookback, p.max_gap, p.max_skew, p.min_score,
+                               chains_per_strand, sp.max_segments, sp.max_secondary, sp.max_overlap, band, c.match, c.mismatch, c.gap, c.end_bonus,
+                               c.min_aln_score, &moff, &mp, &ps, &coff, &cg, &st));
+    std::vector<std::vector<SplitMapping>> out(n);
+    for (uint64_t i = 0; i < n; i++)
+      for (uint64_t j = moff[i]; j < moff[i + 1]; j++) out[i].push_back({ps[j], mp[j], std::vector<uint32_t>(cg + coff[j], cg + coff[j + 1])});
+    if (status) status->assign(st, st + n);
+    awry_free_buffer(moff); awry_free_buffer(mp); awry_free_buffer(ps); awry_free_buffer(coff); awry_free_buffer(cg); awry_free_buffer(st);
+    return out;
+  }
+  template <class Str>
+  std::vector<SplitMapping> map_split_string(const Str& query, uint32_t min_len = 12, uint64_t max_hits = 50, uint64_t chains_per_strand = 4,
+                                             SplitParams sp = SplitParams(), uint32_t band = 4, ClipParams c = ClipParams(), ChainParams p = ChainParams()) {
+    return parallel_map_split(std::vector<std::string_view>{std::string_view(query)}, min_len, max_hits, chains_per_strand, sp, band, c, p)[0];
+  }
   // read pairs mapped together (no counterpart in the reference; the definition is in awry_hip.h, "map read pairs"): reads1[p] and
   // reads2[p] are the mates of pair p.  Per pair at most one Mapping per mate -- the placements of the best pair, with the pair's
   // mapping quality, AWRY_MAP_PROPER_PAIR when they face each other within [min_insert, max_insert] on one record, AWRY_MAP_RESCUED

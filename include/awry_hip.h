@@ -727,6 +727,58 @@ int awry_map_pairs_clip_batch(awry_index_t *idx, const uint8_t *qbytes, const ui
                               uint64_t **map_off_out, awry_map_clip_t **maps_out, awry_pos_t **pos_out, uint64_t **cigar_off_out,
                               uint32_t **cigar_out, uint8_t **status_out, uint32_t **insert_out);
 
+/* ---- split reads: supplementary alignments by query overlap (no counterpart in the reference) --------------------------
+ * A read can come from two places: a chimeric read, a read over a breakpoint, a read that runs across the join of two records.
+ * awry_map_clip_batch reports its second half as a secondary with MAPQ 0, and computes the primary's MAPQ against it although it
+ * explains other letters.  Here the kept candidates are sorted by the part of the read they explain: SEGMENTS cover different letters
+ * (the first is the primary, the later ones are supplementary), SECONDARIES are other places for the letters of a segment, and every
+ * segment has a MAPQ of its own against the best competitor for its letters.  No other entry point changes its output.  Everything
+ * is integer arithmetic and every tie is broken explicitly.
+ * Parameters.  Those of awry_map_clip_batch without max_report, plus max_segments = P, 1 <= P <= AWRY_SPLIT_MAX_SEGMENTS = 4;
+ *   max_secondary = R2, 0 <= R2 <= 2 A; max_overlap = O, a percentage, 1 <= O <= 100.  Out of range => AWRY_ERR_ARG.
+ * Candidates, threshold and rank are exactly the clipped map level's ("soft-clip read ends"): status AWRY_ALN_OK and score >= T,
+ *   among the first A chains of each strand, ordered ascending by (-score, edits, strand, t_begin, j).
+ * Query interval, in the read's own orientation, L the read's length: (lo, hi) = (clip_left, clip_right) on strand 0 and
+ *   (clip_right, clip_left) on strand 1; q_begin = min(lo, L); q_end = max(q_begin, L - min(hi, L)).  Real alignments never saturate;
+ *   the device primitive accepts any records, so the saturation is part of the definition (and a length above 65535 counts as 65535
+ *   there: the interval is two 16-bit fields).  A candidate with q_end == q_begin is dropped: it is not kept and plays no part in
+ *   redundancy.
+ * The walk.  The ranked list is walked once, and for each candidate c: (1) c is dropped if a better-ranked KEPT candidate (segment or
+ *   secondary) of the same strand has an intersecting text span -- the redundancy test of awry_map_batch, unchanged.  (2) Otherwise,
+ *   with the segments so far g_0, g_1, .. in the order they were accepted, c OVERLAPS g when ov = min(c.q_end, g.q_end) -
+ *   max(c.q_begin, g.q_begin) > 0 and 100 ov >= O min(c.q_end - c.q_begin, g.q_end - g.q_begin).  If c overlaps some segment, with g_x
+ *   the first such, c is kept as a secondary of g_x, and if g_x has no sub yet, sub(g_x) = c.score: the list is ranked, so this is the
+ *   best competitor for those letters.  (3) Otherwise, if fewer than P segments exist, c is kept as a new segment; if P segments
+ *   exist already, c is dropped and not kept.
+ * Report.  The segments first, in acceptance order: segment 0 is the primary, with flags 0; each later segment carries
+ *   AWRY_MAP_SUPPLEMENTARY = 16.  Then the first min(R2, #secondaries) secondaries in rank order, each with AWRY_MAP_SECONDARY.
+ *   parent is the index, among this read's records, of the record's segment; a segment's parent is its own index.  The walk always
+ *   runs to the end of the list, because a late candidate can be a late segment's sub; only the report is cut.
+ * Status and MAPQ.  Status as in awry_map_batch.  Every segment has MAPQ 0 under AWRY_Q_SEED_CAP; otherwise a segment with no sub has
+ *   MAPQ 60, and one with a sub has min(60, 10 (score - sub) / (a + b)) with floor division.  Secondaries have MAPQ 0.
+ * Record.  awry_map_split_t, 48 bytes: awry_map_clip_t's eleven fields at the same offsets, then uint16_t q_begin, q_end, parent,
+ *   reserved (= 0).  Spans, clips and CIGARs of strand-1 records stay those of rc(read) against the forward text.  Soft clips stay
+ *   soft: the 'S' letters of a supplementary are the letters the other segments explain.
+ * Properties.  (1) q_end - q_begin equals the query letters of the record's CIGAR, and q_begin / q_end follow from strand, clips and
+ *   L.  (2) A read whose walk yields one segment with P >= 2 is reported exactly as awry_map_clip_batch reports it at max_report = 1 +
+ *   R2: the same records, fields, MAPQ and runs.  (3) No two segments of a read overlap in the sense above.  (4) Every secondary
+ *   overlaps its parent, and overlaps no segment accepted before its parent.  (5) At P = 1 the primary's MAPQ never falls below
+ *   awry_map_clip_batch's for the same read: the competitor set shrinks and the primary is the same.
+ * Not done.  The uncovered part of a read is not seeded again: a split whose second half is not among the first A chains of either
+ *   strand is not found (raise A).  awry_map_pairs_clip_batch is untouched.  No hard clips.
+ *
+ * awry_map_split_batch: awry_map_clip_batch's arguments with max_segments, max_secondary, max_overlap in the place of max_report, the
+ * same CSR output with awry_map_split_t records, the same nullability, errors, index restrictions and invariances. */
+enum { AWRY_SPLIT_MAX_SEGMENTS = 4 };
+enum { AWRY_MAP_SUPPLEMENTARY = 16 };
+typedef struct { uint64_t t_begin, t_end; uint32_t edits, chain_score, chain_index; uint8_t strand, mapq; uint16_t flags; int32_t score; uint16_t clip_left, clip_right; uint16_t q_begin, q_end, parent, reserved; } awry_map_split_t;
+int awry_map_split_batch(awry_index_t *idx, const uint8_t *qbytes, const uint64_t *qoff, uint64_t n, uint32_t min_len,
+                         uint64_t max_hits, uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew,
+                         uint32_t min_score, uint64_t chains_per_strand, uint64_t max_segments, uint64_t max_secondary,
+                         uint32_t max_overlap, uint32_t band, uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus,
+                         uint32_t min_aln_score, uint64_t **map_off_out, awry_map_split_t **maps_out, awry_pos_t **pos_out,
+                         uint64_t **cigar_off_out, uint32_t **cigar_out, uint8_t **status_out);
+
 /* releases an array one of the calls above (or awry_locate / awry_read_query_file) returned.  Result arrays are pinned
  * host memory recycled through a process-wide pool (the device writes results straight into them); never pass them to
  * free().  AWRY_PINNED_CACHE_GB (default 4) bounds what the pool keeps between calls. */
@@ -1002,6 +1054,18 @@ int awry_dev_map_select_clip(awry_index_t *idx, int slot, const uint64_t *d_aln_
                              uint32_t max_report, uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus,
                              uint32_t min_aln_score, uint64_t *d_n_maps, uint8_t *d_read_status, const uint64_t *d_map_off,
                              awry_map_clip_t *d_maps, uint32_t *d_sel, awry_pos_t *d_pos, void *stream);
+/* The walk, report and MAPQ of awry_map_split_batch ("split reads") over a caller's clipped alignment records: the arguments and the
+ * two-call protocol of awry_dev_map_select_clip, with d_qoff -- the reads' own n + 1 offsets, of which only the lengths are read --
+ * after d_chain_status, max_segments, max_secondary, max_overlap in the place of max_report, and of the scalars match, mismatch (MAPQ
+ * divides by their sum) and min_aln_score (the threshold); all are checked.  It writes awry_map_split_t records.  One read per lane:
+ * a first pass classifies the kept candidates (the kept slots in rank order and their segments are two 64-bit words of sixteen
+ * 4-bit entries), a second emits, so that the secondaries land behind however many segments there are.  Queued on `stream`, no
+ * synchronisation. */
+int awry_dev_map_select_split(awry_index_t *idx, int slot, const uint64_t *d_aln_off, const awry_aln_clip_t *d_alns,
+                              const awry_chain_t *d_chains, const uint8_t *d_chain_status, const uint64_t *d_qoff, uint64_t n,
+                              uint32_t chains_per_strand, uint32_t max_segments, uint32_t max_secondary, uint32_t max_overlap,
+                              uint32_t match, uint32_t mismatch, uint32_t min_aln_score, uint64_t *d_n_maps, uint8_t *d_read_status,
+                              const uint64_t *d_map_off, awry_map_split_t *d_maps, uint32_t *d_sel, awry_pos_t *d_pos, void *stream);
 /* The rescue windows of awry_map_pairs_batch over a caller's kept lists: the candidates of read i (mate i & 1 of pair i >> 1) are
  * d_cands[d_cand_off[i] .. d_cand_off[i+1]) in rank order, d_cand_off and d_qoff (the reads' own offsets: only the lengths are read)
  * have 2 n_pairs + 1 entries.  Output at a fixed stride: slot w = (2p + m) G + a, G = rescue_anchors, is candidate a of mate m.  An

@@ -15,7 +15,7 @@ use std::os::raw::c_char;
 use std::path::{Path, PathBuf};
 use std::sync::Arc;
 
-use awry_hip_sys::{self as sys, awry_aln_t as RawAln, awry_anchor_t as RawAnchor, awry_chain_t as RawChain, awry_map_clip_t as RawMapClip, awry_map_t as RawMap, awry_pos_t as RawPos,
+use awry_hip_sys::{self as sys, awry_aln_t as RawAln, awry_anchor_t as RawAnchor, awry_chain_t as RawChain, awry_map_clip_t as RawMapClip, awry_map_split_t as RawMapSplit, awry_map_t as RawMap, awry_pos_t as RawPos,
                    awry_seed_t as RawSeed};
 use rayon::iter::{IndexedParallelIterator, IntoParallelIterator, IntoParallelRefIterator, ParallelIterator};
 
@@ -301,6 +301,33 @@ pub struct ClippedMapping {
     pub score: i32,
     pub clip_left: u16,
     pub clip_right: u16,
+}
+
+/// The three scalars of the split selection (include/awry_hip.h, "split reads"): at most `max_segments` (1..=4) segments per read, at
+/// most `max_secondary` (0..=2 x chains_per_strand) reported secondaries, and `max_overlap` (1..=100), the percentage of the shorter
+/// query interval two alignments may share before one counts as another place for the same letters.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct SplitParams {
+    pub max_segments: u64,
+    pub max_secondary: u64,
+    pub max_overlap: u32,
+}
+
+impl Default for SplitParams {
+    fn default() -> Self {
+        SplitParams { max_segments: 2, max_secondary: 0, max_overlap: 50 }
+    }
+}
+
+/// One record of [`FmIndex::parallel_map_split`]: a [`ClippedMapping`] with the letters `[q_begin, q_end)` of the read (as given) it
+/// explains and `parent`, the index among the read's records of its segment (its own for a segment).  The first record is the
+/// primary, later segments carry `AWRY_MAP_SUPPLEMENTARY`, secondaries `AWRY_MAP_SECONDARY`.
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub struct SplitMapping {
+    pub clipped: ClippedMapping,
+    pub q_begin: u16,
+    pub q_end: u16,
+    pub parent: u16,
 }
 
 /// The CIGAR string of the runs [`FmIndex::parallel_align_edit`] returns (`len << 4 | op`, BAM's op codes): `"57=1X43="`.
@@ -967,6 +994,79 @@ impl FmIndex {
             sys::awry_free_buffer(cigar as *mut std::os::raw::c_void);
             sys::awry_free_buffer(st as *mut std::os::raw::c_void);
             sys::awry_free_buffer(ins as *mut std::os::raw::c_void);
+        }
+        Ok(out)
+    }
+
+    /// Split reads (no counterpart in the reference; include/awry_hip.h, "split reads"): per read its segments -- clipped alignments
+    /// over different letters of the read, the primary and then the supplementaries, each with a mapping quality of its own -- and then
+    /// its reported secondaries; and per read whether one of its strands was abandoned at `params.max_seeds`.
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn parallel_map_split<'a>(
+        &self,
+        queries: impl ParallelIterator<Item = &'a str>,
+        min_len: u32,
+        max_hits: u64,
+        chains_per_strand: u64,
+        split: SplitParams,
+        band: u32,
+        clip: ClipParams,
+        params: ChainParams,
+    ) -> Result<(Vec<Vec<SplitMapping>>, Vec<bool>), AwryError> {
+        let csr = to_csr(queries);
+        let n = csr.offsets.len() - 1;
+        let mut map_off: *mut u64 = std::ptr::null_mut();
+        let mut maps: *mut RawMapSplit = std::ptr::null_mut();
+        let mut pos: *mut RawPos = std::ptr::null_mut();
+        let mut cigar_off: *mut u64 = std::ptr::null_mut();
+        let mut cigar: *mut u32 = std::ptr::null_mut();
+        let mut st: *mut u8 = std::ptr::null_mut();
+        check(unsafe {
+            sys::awry_map_split_batch(self.raw(), csr.bytes.as_ptr(), csr.offsets.as_ptr(), n as u64, min_len, max_hits, params.max_seeds, params.lookback,
+                                      params.max_gap, params.max_skew, params.min_score, chains_per_strand, split.max_segments, split.max_secondary,
+                                      split.max_overlap, band, clip.match_score, clip.mismatch, clip.gap, clip.end_bonus, clip.min_aln_score, &mut map_off,
+                                      &mut maps, &mut pos, &mut cigar_off, &mut cigar, &mut st)
+        })?;
+        let out = unsafe {
+            let off = std::slice::from_raw_parts(map_off, n + 1);
+            let total = off[n] as usize;
+            let mp: &[RawMapSplit] = if total == 0 { &[] } else { std::slice::from_raw_parts(maps, total) };
+            let ps: &[RawPos] = if total == 0 { &[] } else { std::slice::from_raw_parts(pos, total) };
+            let coff = std::slice::from_raw_parts(cigar_off, total + 1);
+            let runs: &[u32] = if coff[total] == 0 { &[] } else { std::slice::from_raw_parts(cigar, coff[total] as usize) };
+            let status: &[u8] = if n == 0 { &[] } else { std::slice::from_raw_parts(st, n) };
+            let record = |j: usize| SplitMapping {
+                clipped: ClippedMapping {
+                    mapping: Mapping {
+                        position: LocalizedSequencePosition::new(ps[j].seq_idx as usize, ps[j].local_pos as usize),
+                        t_begin: mp[j].t_begin,
+                        t_end: mp[j].t_end,
+                        edits: mp[j].edits,
+                        chain_score: mp[j].chain_score,
+                        chain_index: mp[j].chain_index,
+                        strand: mp[j].strand,
+                        mapq: mp[j].mapq,
+                        flags: mp[j].flags,
+                        cigar: runs[coff[j] as usize..coff[j + 1] as usize].to_vec(),
+                    },
+                    score: mp[j].score,
+                    clip_left: mp[j].clip_left,
+                    clip_right: mp[j].clip_right,
+                },
+                q_begin: mp[j].q_begin,
+                q_end: mp[j].q_end,
+                parent: mp[j].parent,
+            };
+            let per = (0..n).map(|i| (off[i] as usize..off[i + 1] as usize).map(record).collect::<Vec<_>>()).collect::<Vec<_>>();
+            (per, status.iter().map(|&s| s == 8).collect::<Vec<_>>())  // AWRY_Q_SEED_CAP
+        };
+        unsafe {
+            sys::awry_free_buffer(map_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(maps as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(pos as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(cigar_off as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(cigar as *mut std::os::raw::c_void);
+            sys::awry_free_buffer(st as *mut std::os::raw::c_void);
         }
         Ok(out)
     }
