@@ -89,8 +89,7 @@ bool find_records(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard
   }
   L.n_rec.alloc(n); L.rec_off.alloc(n + 1); L.scratch.alloc(scan_tiles(n) + 1);
   find(r, cb.q.p, cb.off.p, n, L.n_rec.p, nullptr, nullptr, cb.status.p, s);
-  launch_scan(r, L.n_rec.p, n, L.rec_off.p, L.scratch.p, s);
-  HIP_CHECK(hipMemcpyAsync(&L.total, L.rec_off.p + n, 8, hipMemcpyDeviceToHost, s));
+  scan_with_total(r, L.n_rec.p, n, L.rec_off.p, L.scratch.p, &L.total, s);
   HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   for (uint64_t i = 0; i < n; i++)
@@ -103,8 +102,7 @@ bool find_records(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard
   find(r, cb.q.p, cb.off.p, n, nullptr, L.rec_off.p, L.rec.p, nullptr, s);
   if (!max_hits) return true;
   launch_anchor_ranges(r, L.rec.p, total, max_hits, L.ranges.p, L.located.p, s);
-  launch_scan(r, L.located.p, total, L.hit_off.p, L.lscratch.p, s);
-  HIP_CHECK(hipMemcpyAsync(&L.nhits, L.hit_off.p + total, 8, hipMemcpyDeviceToHost, s));
+  scan_with_total(r, L.located.p, total, L.hit_off.p, L.lscratch.p, &L.nhits, s);
   HIP_CHECK(hipStreamSynchronize(s));
   return !(L.nhits > anchor_hit_cap() && nreads > unit);
 }

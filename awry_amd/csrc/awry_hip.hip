@@ -444,13 +444,10 @@ int awry_chain_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* q
                      uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score, uint64_t** chain_off_out, awry_chain_t** chains_out,
                      uint64_t** seed_off_out, awry_seed_t** seeds_out, uint8_t** status_out) {
   return guarded([&] {
-    require(idx && qoff && chain_off_out, "null argument");
-    require(qbytes || qoff[n] == qoff[0], "null query bytes");
-    require_smem_args(min_len);
-    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
-    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    const Reads q = checked_reads(idx, qbytes, qoff, n, chain_off_out);
+    const Seeding sc(min_len, max_hits, max_seeds, lookback, max_gap, max_skew, min_score);
     require((seed_off_out == nullptr) == (seeds_out == nullptr), "seed_off_out and seeds_out are given or omitted together");
-    chain_batch(idx, qbytes, qoff, n, min_len, max_hits, P, chain_off_out, chains_out, seed_off_out, seeds_out, status_out);
+    chain_batch(idx, q, sc, chain_off_out, chains_out, seed_off_out, seeds_out, status_out);
   });
 }
 
@@ -459,15 +456,11 @@ int awry_align_chains_batch(awry_index_t* idx, const uint8_t* qbytes, const uint
                             uint32_t band, uint64_t** aln_off_out, awry_chain_t** chains_out, awry_aln_t** alns_out, uint64_t** cigar_off_out,
                             uint32_t** cigar_out, uint8_t** status_out) {
   return guarded([&] {
-    require(idx && qoff && aln_off_out, "null argument");
-    require(qbytes || qoff[n] == qoff[0], "null query bytes");
-    require_smem_args(min_len);
-    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
-    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    const Reads q = checked_reads(idx, qbytes, qoff, n, aln_off_out);
+    const Seeding sc(min_len, max_hits, max_seeds, lookback, max_gap, max_skew, min_score);
     require_chain_align_args(max_alignments, band);
-    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
-    align_chains_batch(idx, qbytes, qoff, n, min_len, max_hits, P, max_alignments, band, AlignMode{}, aln_off_out, chains_out, alns_out, cigar_off_out,
-                       cigar_out, status_out);
+    require_cigar_pair(cigar_off_out, cigar_out);
+    align_chains_batch(idx, q, sc, max_alignments, band, AlignMode{}, AlnOut<awry_aln_t>{aln_off_out, chains_out, alns_out, cigar_off_out, cigar_out, status_out});
   });
 }
 
@@ -476,16 +469,12 @@ int awry_align_chains_clip_batch(awry_index_t* idx, const uint8_t* qbytes, const
                                  uint32_t band, uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus, uint64_t** aln_off_out,
                                  awry_chain_t** chains_out, awry_aln_clip_t** alns_out, uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out) {
   return guarded([&] {
-    require(idx && qoff && aln_off_out, "null argument");
-    require(qbytes || qoff[n] == qoff[0], "null query bytes");
-    require_smem_args(min_len);
-    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
-    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    const Reads q = checked_reads(idx, qbytes, qoff, n, aln_off_out);
+    const Seeding sc(min_len, max_hits, max_seeds, lookback, max_gap, max_skew, min_score);
     require_chain_align_args(max_alignments, band);
     const AlignMode md = clip_mode(match, mismatch, gap, end_bonus);
-    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
-    align_chains_batch(idx, qbytes, qoff, n, min_len, max_hits, P, max_alignments, band, md, aln_off_out, chains_out, alns_out, cigar_off_out, cigar_out,
-                       status_out);
+    require_cigar_pair(cigar_off_out, cigar_out);
+    align_chains_batch(idx, q, sc, max_alignments, band, md, AlnOut<awry_aln_clip_t>{aln_off_out, chains_out, alns_out, cigar_off_out, cigar_out, status_out});
   });
 }
 
@@ -493,15 +482,12 @@ int awry_map_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qof
                    uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score, uint64_t chains_per_strand, uint64_t max_report, uint32_t band,
                    uint64_t** map_off_out, awry_map_t** maps_out, awry_pos_t** pos_out, uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out) {
   return guarded([&] {
-    require(idx && qoff && map_off_out, "null argument");
-    require(qbytes || qoff[n] == qoff[0], "null query bytes");
-    require_smem_args(min_len);
-    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
-    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    const Reads q = checked_reads(idx, qbytes, qoff, n, map_off_out);
+    const Seeding sc(min_len, max_hits, max_seeds, lookback, max_gap, max_skew, min_score);
     require_map_args(chains_per_strand, max_report, band);
-    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
-    map_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, (uint32_t)max_report, band, AlignMode{}, MapMode{}, map_off_out,
-              maps_out, pos_out, cigar_off_out, cigar_out, status_out);
+    require_cigar_pair(cigar_off_out, cigar_out);
+    map_batch(idx, q, sc, (uint32_t)chains_per_strand, (uint32_t)max_report, band, AlignMode{}, MapMode{},
+              MapOut<awry_map_t>{map_off_out, maps_out, pos_out, cigar_off_out, cigar_out, status_out});
   });
 }
 
@@ -510,16 +496,13 @@ int awry_map_clip_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t
                         uint32_t band, uint32_t match, uint32_t mismatch, uint32_t gap, uint32_t end_bonus, uint32_t min_aln_score, uint64_t** map_off_out,
                         awry_map_clip_t** maps_out, awry_pos_t** pos_out, uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out) {
   return guarded([&] {
-    require(idx && qoff && map_off_out, "null argument");
-    require(qbytes || qoff[n] == qoff[0], "null query bytes");
-    require_smem_args(min_len);
-    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
-    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    const Reads q = checked_reads(idx, qbytes, qoff, n, map_off_out);
+    const Seeding sc(min_len, max_hits, max_seeds, lookback, max_gap, max_skew, min_score);
     require_map_args(chains_per_strand, max_report, band);
     const AlignMode md = clip_mode(match, mismatch, gap, end_bonus);
-    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
-    map_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, (uint32_t)max_report, band, md, clip_map_mode(md, min_aln_score),
-              map_off_out, maps_out, pos_out, cigar_off_out, cigar_out, status_out);
+    require_cigar_pair(cigar_off_out, cigar_out);
+    map_batch(idx, q, sc, (uint32_t)chains_per_strand, (uint32_t)max_report, band, md, clip_map_mode(md, min_aln_score),
+              MapOut<awry_map_clip_t>{map_off_out, maps_out, pos_out, cigar_off_out, cigar_out, status_out});
   });
 }
 
@@ -529,16 +512,13 @@ int awry_map_split_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_
                          uint32_t min_aln_score, uint64_t** map_off_out, awry_map_split_t** maps_out, awry_pos_t** pos_out, uint64_t** cigar_off_out,
                          uint32_t** cigar_out, uint8_t** status_out) {
   return guarded([&] {
-    require(idx && qoff && map_off_out, "null argument");
-    require(qbytes || qoff[n] == qoff[0], "null query bytes");
-    require_smem_args(min_len);
-    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
-    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    const Reads q = checked_reads(idx, qbytes, qoff, n, map_off_out);
+    const Seeding sc(min_len, max_hits, max_seeds, lookback, max_gap, max_skew, min_score);
     const SplitParams sp = split_params(chains_per_strand, max_segments, max_secondary, max_overlap, band);
     const AlignMode md = clip_mode(match, mismatch, gap, end_bonus);
-    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
-    split_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, sp, band, md, clip_map_mode(md, min_aln_score), map_off_out, maps_out,
-                pos_out, cigar_off_out, cigar_out, status_out);
+    require_cigar_pair(cigar_off_out, cigar_out);
+    split_batch(idx, q, sc, (uint32_t)chains_per_strand, sp, band, md, clip_map_mode(md, min_aln_score),
+                MapOut<awry_map_split_t>{map_off_out, maps_out, pos_out, cigar_off_out, cigar_out, status_out});
   });
 }
 
@@ -548,16 +528,13 @@ int awry_map_pairs_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_
                          uint64_t** map_off_out, awry_map_t** maps_out, awry_pos_t** pos_out, uint64_t** cigar_off_out, uint32_t** cigar_out,
                          uint8_t** status_out, uint32_t** insert_out) {
   return guarded([&] {
-    require(idx && qoff && map_off_out, "null argument");
-    require(qbytes || qoff[n] == qoff[0], "null query bytes");
-    require_smem_args(min_len);
-    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
-    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    const Reads q = checked_reads(idx, qbytes, qoff, n, map_off_out);
+    const Seeding sc(min_len, max_hits, max_seeds, lookback, max_gap, max_skew, min_score);
     require_map_args(chains_per_strand, 1, band);
     const PairParams pp = pair_params(min_insert, max_insert, unpaired_penalty, rescue_anchors, rescue_edits);
-    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
-    map_pairs_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, band, AlignMode{}, MapMode{}, PairMode{}, pp, map_off_out,
-                    maps_out, pos_out, cigar_off_out, cigar_out, status_out, insert_out);
+    require_cigar_pair(cigar_off_out, cigar_out);
+    map_pairs_batch(idx, q, sc, (uint32_t)chains_per_strand, band, AlignMode{}, MapMode{}, PairMode{}, pp,
+                    MapOut<awry_map_t>{map_off_out, maps_out, pos_out, cigar_off_out, cigar_out, status_out, insert_out});
   });
 }
 
@@ -568,26 +545,22 @@ int awry_map_pairs_clip_batch(awry_index_t* idx, const uint8_t* qbytes, const ui
                               awry_map_clip_t** maps_out, awry_pos_t** pos_out, uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out,
                               uint32_t** insert_out) {
   return guarded([&] {
-    require(idx && qoff && map_off_out, "null argument");
-    require(qbytes || qoff[n] == qoff[0], "null query bytes");
-    require_smem_args(min_len);
-    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
-    const ChainParams P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+    const Reads q = checked_reads(idx, qbytes, qoff, n, map_off_out);
+    const Seeding sc(min_len, max_hits, max_seeds, lookback, max_gap, max_skew, min_score);
     require_map_args(chains_per_strand, 1, band);
     const PairParams pp = pair_params(min_insert, max_insert, unpaired_penalty, rescue_anchors, rescue_edits, true);
     const AlignMode md = clip_mode(match, mismatch, gap, end_bonus);
     const MapMode mm = clip_map_mode(md, min_aln_score);
-    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
-    map_pairs_batch(idx, qbytes, qoff, n, min_len, max_hits, P, (uint32_t)chains_per_strand, band, md, mm, clip_pair_mode(md, mm), pp, map_off_out, maps_out,
-                    pos_out, cigar_off_out, cigar_out, status_out, insert_out);
+    require_cigar_pair(cigar_off_out, cigar_out);
+    map_pairs_batch(idx, q, sc, (uint32_t)chains_per_strand, band, md, mm, clip_pair_mode(md, mm), pp,
+                    MapOut<awry_map_clip_t>{map_off_out, maps_out, pos_out, cigar_off_out, cigar_out, status_out, insert_out});
   });
 }
 
 int awry_locate_edit_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, int max_edits, uint64_t max_candidates,
                            uint64_t** hit_off_out, awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** edits_out, uint8_t** status_out) {
   return guarded([&] {
-    require(idx && qoff && hit_off_out, "null argument");
-    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    checked_reads(idx, qbytes, qoff, n, hit_off_out);
     require_edits(max_edits);
     require(max_candidates != 0, "max_candidates must be at least 1 (a cap is mandatory: the pieces of a read from a repeat family occur everywhere)");
     locate_edit_batch(idx, qbytes, qoff, n, max_edits, max_candidates, hit_off_out, hits_out, global_pos_out, edits_out, status_out);
@@ -598,11 +571,10 @@ int awry_align_edit_batch(awry_index_t* idx, const uint8_t* qbytes, const uint64
                           uint64_t** hit_off_out, awry_pos_t** hits_out, uint64_t** global_pos_out, uint8_t** edits_out, uint8_t** status_out,
                           uint32_t** text_len_out, uint64_t** cigar_off_out, uint32_t** cigar_out) {
   return guarded([&] {
-    require(idx && qoff && hit_off_out, "null argument");
-    require(qbytes || qoff[n] == qoff[0], "null query bytes");
+    checked_reads(idx, qbytes, qoff, n, hit_off_out);
     require_edits(max_edits);
     require(max_candidates != 0, "max_candidates must be at least 1 (a cap is mandatory: the pieces of a read from a repeat family occur everywhere)");
-    require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
+    require_cigar_pair(cigar_off_out, cigar_out);
     locate_edit_batch(idx, qbytes, qoff, n, max_edits, max_candidates, hit_off_out, hits_out, global_pos_out, edits_out, status_out, text_len_out,
                       cigar_off_out, cigar_out);
   });

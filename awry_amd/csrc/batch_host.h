@@ -1,10 +1,24 @@
 // batch_host.h -- what the batch drivers of the read pipelines share (mismatch_host.h, anchor_host.h, chain_host.h, edit_host.h,
-// chain_align_host.h, map_host.h): the reader of the capacity variables, the flat launch, the chunk upload, the halving fallback
-// and the stitching of the shards' results into the pinned result arrays.  Each driver still reads top to bottom in its own file.
+// chain_align_host.h, map_host.h, split_host.h, pair_host.h): the reads of a call and their two checks, the reader of the capacity
+// variables, the flat launch, the scan that reads its total back, the chunk upload, the halving fallback and the stitching of the
+// shards' results into the pinned result arrays.  Plain functions and structs: each driver still reads top to bottom in its own file.
 // A part of awry_hip.hip (one translation unit): included there, in order, before the drivers, and not on its own.
 #pragma once
 
 namespace {
+
+struct Reads { const uint8_t* bytes; const uint64_t* off; uint64_t n; };  // of a batch call: read i is bytes[off[i] .. off[i + 1])
+
+// the first two checks of the entry points; first_out is the result array a call always writes (its offsets)
+Reads checked_reads(const void* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, const void* first_out) {
+  require(idx && qoff && first_out, "null argument");
+  require(qbytes || qoff[n] == qoff[0], "null query bytes");
+  return Reads{qbytes, qoff, n};
+}
+
+void require_cigar_pair(const void* cigar_off_out, const void* cigar_out) {
+  require((cigar_off_out == nullptr) == (cigar_out == nullptr), "cigar_off_out and cigar_out are given or omitted together");
+}
 
 // A capacity a test may shrink: the value of the environment variable `name` up to `max`, `dflt` when it is unset or 0.  Read per call.
 uint64_t env_cap(const char* name, uint64_t dflt, uint64_t max) {
@@ -18,6 +32,13 @@ template <class K, class... Args>
 void flat_launch(Replica& r, hipStream_t s, uint64_t items, K kernel, Args... args) {
   hipLaunchKernelGGL(kernel, dim3(grid_for(r, items, 256)), dim3(256), 0, s, args...);
   HIP_CHECK(hipGetLastError());
+}
+
+// The scan of a two-pass stage (count pass, scan, fill pass) and the copy of its total, d_off[n], into *total, both queued on s: the
+// caller places the wait, so that what it queues before it rides on it.
+void scan_with_total(Replica& r, const uint64_t* d_counts, uint64_t n, uint64_t* d_off, uint64_t* d_scratch, uint64_t* total, hipStream_t s) {
+  launch_scan(r, d_counts, n, d_off, d_scratch, s);
+  HIP_CHECK(hipMemcpyAsync(total, d_off + n, 8, hipMemcpyDeviceToHost, s));
 }
 
 // upload one chunk's query bytes and chunk-relative offsets (the generic count path's layout)

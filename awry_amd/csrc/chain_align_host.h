@@ -47,7 +47,9 @@ struct ChainAlnHitsOf {  // one shard's result, in query order
   std::vector<uint64_t> n_ops;  // per alignment
   std::vector<uint32_t> cigar;  // the runs, back to back
 };
-using ChainAlnHits = ChainAlnHitsOf<awry_aln_t>;
+
+template <class AlnT>  // the result arrays of the call: `off` always, the others where the caller wants them (the two cigar arrays together)
+struct AlnOut { uint64_t** off; awry_chain_t** chains; AlnT** alns; uint64_t** cigar_off; uint32_t** cigar; uint8_t** status; };
 
 // ---- the two stages shared with map_chunk (map_host.h) ----------------------------------------------------------------------------
 
@@ -68,16 +70,14 @@ void select_chains(Replica& r, const ChainOnDevice& v, uint64_t nq, uint64_t tak
   const hipStream_t s = r.stream;
   S.taken.alloc(nq); S.aoff.alloc(nq + 1); S.scratch.alloc(scan_tiles(nq) + 1);
   flat_launch(r, s, nq, chain_align_take_kernel, v.n_chains, nq, take, S.taken.p);
-  launch_scan(r, S.taken.p, nq, S.aoff.p, S.scratch.p, s);
-  HIP_CHECK(hipMemcpyAsync(&S.total, S.aoff.p + nq, 8, hipMemcpyDeviceToHost, s));
+  scan_with_total(r, S.taken.p, nq, S.aoff.p, S.scratch.p, &S.total, s);
   HIP_CHECK(hipStreamSynchronize(s));
   const uint64_t total = S.total;
   require(total <= v.nchains && total < (1ull << 32), "internal: more chains selected than the chunk has");
   if (!total) return;
   S.query.alloc(total); S.chains.alloc(total); S.mcnt.alloc(total); S.moff.alloc(total + 1); S.mscratch.alloc(scan_tiles(total) + 1);
   flat_launch(r, s, nq, chain_align_select_kernel, v.chain_off, v.chains, S.aoff.p, nq, S.query.p, S.chains.p, S.mcnt.p);
-  launch_scan(r, S.mcnt.p, total, S.moff.p, S.mscratch.p, s);
-  HIP_CHECK(hipMemcpyAsync(&S.nsel, S.moff.p + total, 8, hipMemcpyDeviceToHost, s));
+  scan_with_total(r, S.mcnt.p, total, S.moff.p, S.mscratch.p, &S.nsel, s);
   HIP_CHECK(hipStreamSynchronize(s));
   require(S.nsel <= v.nmembers, "internal: the selected chains have more members than the chunk");
   S.members.alloc(std::max<uint64_t>(S.nsel, 1));
@@ -92,8 +92,7 @@ void fill_cigar(Replica& r, const uint8_t* text8, const ChunkBuffers& cb, const 
                 int band, const AlignMode& md, uint32_t Lmax, const uint64_t* d_nops, uint64_t* d_coff, uint64_t* d_cscratch, std::vector<uint32_t>& cigar) {
   const hipStream_t s = r.stream;
   uint64_t runs = 0;
-  launch_scan(r, d_nops, c, d_coff, d_cscratch, s);
-  HIP_CHECK(hipMemcpyAsync(&runs, d_coff + c, 8, hipMemcpyDeviceToHost, s));
+  scan_with_total(r, d_nops, c, d_coff, d_cscratch, &runs, s);
   HIP_CHECK(hipStreamSynchronize(s));
   if (!runs) return;
   DevBuf<uint32_t> d_cigar(runs);
@@ -148,38 +147,36 @@ void align_chunk_chains(Replica& r, const uint8_t* text8, const ChainOnDevice& v
 // awry_align_chains_batch: shards over the replicas, results stitched in query order into pinned-pool arrays.  The out-pointers
 // are written only when everything has succeeded.  awry_align_chains_clip_batch is the same with md's mode and AlnT = awry_aln_clip_t.
 template <class AlnT>
-void align_chains_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits, const ChainParams& P,
-                        uint64_t max_alignments, uint32_t band, const AlignMode& md, uint64_t** aln_off_out, awry_chain_t** chains_out, AlnT** alns_out,
-                        uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out) {
+void align_chains_batch(awry_index* idx, const Reads& q, const Seeding& sc, uint64_t max_alignments, uint32_t band, const AlignMode& md, const AlnOut<AlnT>& out) {
   require_chain_index(idx->host.bwt_len);
-  require_chain_align_lengths(qoff, n);
-  const bool want_cigar = cigar_out != nullptr;
+  require_chain_align_lengths(q.off, q.n);
+  const bool want_cigar = out.cigar != nullptr;
   using Hits = ChainAlnHitsOf<AlnT>;
   std::vector<Hits> res(std::max<size_t>(1, idx->reps.size()));
-  for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
+  for_each_replica(idx, q.n, [&](Replica& r, Shard sh, int g) {
     HIP_CHECK(hipSetDevice(r.device));
     const uint8_t* text8 = edit_text(r);
     const auto sink = [&, g, text8](Replica& rr, const ChainOnDevice& v) { align_chunk_chains(rr, text8, v, max_alignments, (int)band, md, want_cigar, res[g]); };
-    for (Shard c : chunk_queries(qoff, sh.lo, sh.hi))
-      halve_until_fits(c, [&](Shard h) { return chain_chunk(r, qbytes, qoff, h, min_len, max_hits, P, false, sink); });
+    for (Shard c : chunk_queries(q.off, sh.lo, sh.hi))
+      halve_until_fits(c, [&](Shard h) { return chain_chunk(r, q, h, sc, false, sink); });
   });
   MBuf<uint64_t> aoff, coff;
   MBuf<awry_chain_t> chains;
   MBuf<AlnT> alns;
   MBuf<uint32_t> cg;
   MBuf<uint8_t> st;
-  const uint64_t total = stitch_offsets(res, &Hits::n_alns, n, aoff);
+  const uint64_t total = stitch_offsets(res, &Hits::n_alns, q.n, aoff);
   for (auto& x : res) require(x.chains.size() == x.alns.size() && x.alns.size() == x.n_ops.size(), "internal: the alignment passes do not cover the chains");
   require(stitch_size(res, &Hits::alns) == total, "internal: shard results do not cover the alignments");
-  if (status_out) stitch_concat(res, &Hits::status, st);
-  if (chains_out) stitch_concat(res, &Hits::chains, chains);
-  if (alns_out) stitch_concat(res, &Hits::alns, alns);
+  if (out.status) stitch_concat(res, &Hits::status, st);
+  if (out.chains) stitch_concat(res, &Hits::chains, chains);
+  if (out.alns) stitch_concat(res, &Hits::alns, alns);
   if (want_cigar) stitch_run_offsets(res, &Hits::n_ops, total, stitch_concat(res, &Hits::cigar, cg), coff);
-  *aln_off_out = aoff.release();
-  if (chains_out) *chains_out = chains.release();
-  if (alns_out) *alns_out = alns.release();
-  if (want_cigar) { *cigar_off_out = coff.release(); *cigar_out = cg.release(); }
-  if (status_out) *status_out = st.release();
+  *out.off = aoff.release();
+  if (out.chains) *out.chains = chains.release();
+  if (out.alns) *out.alns = alns.release();
+  if (want_cigar) { *out.cigar_off = coff.release(); *out.cigar = cg.release(); }
+  if (out.status) *out.status = st.release();
 }
 
 }  // namespace

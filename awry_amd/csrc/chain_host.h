@@ -23,6 +23,16 @@ ChainParams chain_params(uint32_t max_seeds, uint32_t lookback, uint32_t max_gap
   return ChainParams{max_seeds, lookback, max_gap, max_skew, min_score};
 }
 
+struct Seeding {  // the seeding and chaining parameters of a call, checked in the order the entry points report them
+  uint32_t min_len; uint64_t max_hits; ChainParams P;
+  Seeding(uint32_t min_len, uint64_t max_hits, uint32_t max_seeds, uint32_t lookback, uint32_t max_gap, uint32_t max_skew, uint32_t min_score)
+      : min_len(min_len), max_hits(max_hits) {
+    require_smem_args(min_len);
+    require(max_hits != 0, "max_hits must be at least 1 (a one-letter match has a quarter of the text as hits)");
+    P = chain_params(max_seeds, lookback, max_gap, max_skew, min_score);
+  }
+};
+
 void require_chain_index(uint64_t bwt_len) {
   if (bwt_len >= (1ull << 32)) throw ArgError("chaining needs an index with bwt_len < 2^32");
 }
@@ -51,14 +61,13 @@ struct ChainOnDevice {
 // two queries, itself and its reverse complement (find_records, copies == 2); the sink's view is over the 2 (c.hi - c.lo) queries.
 // unit: find_records' (2 for read pairs, whose chunks are cut between pairs).
 template <class Sink>
-bool chain_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard c, uint32_t min_len, uint64_t max_hits, const ChainParams& P,
-                 bool both_strands, Sink&& sink, uint64_t unit = 1) {
+bool chain_chunk(Replica& r, const Reads& q, Shard c, const Seeding& sc, bool both_strands, Sink&& sink, uint64_t unit = 1) {
   const hipStream_t s = r.stream;
   const uint64_t n = (both_strands ? 2 : 1) * (c.hi - c.lo);
   for (uint64_t i = c.lo; i < c.hi; i++)
-    if (qoff[i + 1] >= qoff[i] && qoff[i + 1] - qoff[i] >= (1ull << 31)) throw ArgError("a query of 2^31 letters or more");
+    if (q.off[i + 1] >= q.off[i] && q.off[i + 1] - q.off[i] >= (1ull << 31)) throw ArgError("a query of 2^31 letters or more");
   LocatedRecords L;
-  if (!find_records(r, qbytes, qoff, c, smem_finder(min_len), max_hits, both_strands ? 2 : 1, "SMEMs", L, unit)) return false;
+  if (!find_records(r, q.bytes, q.off, c, smem_finder(sc.min_len), sc.max_hits, both_strands ? 2 : 1, "SMEMs", L, unit)) return false;
   DevBuf<uint64_t> soff(n + 1);
   DevBuf<Seed> seeds;
   if (L.total) {
@@ -75,16 +84,14 @@ bool chain_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qoff, Shard 
   }
   DevBuf<uint64_t> nch(n), nmem(n), choff(n + 1), moff(n + 1);
   DevBuf<uint8_t> status(n);
-  launch_chain(r, soff.p, seeds.p, n, P, nch.p, nmem.p, nullptr, nullptr, nullptr, nullptr, status.p, s);
-  launch_scan(r, nch.p, n, choff.p, L.scratch.p, s);
+  launch_chain(r, soff.p, seeds.p, n, sc.P, nch.p, nmem.p, nullptr, nullptr, nullptr, nullptr, status.p, s);
   uint64_t nchains = 0, nmembers = 0;
-  HIP_CHECK(hipMemcpyAsync(&nchains, choff.p + n, 8, hipMemcpyDeviceToHost, s));
-  launch_scan(r, nmem.p, n, moff.p, L.scratch.p, s);  // the stage's scratch serves both scans: they are ordered on the stream
-  HIP_CHECK(hipMemcpyAsync(&nmembers, moff.p + n, 8, hipMemcpyDeviceToHost, s));
+  scan_with_total(r, nch.p, n, choff.p, L.scratch.p, &nchains, s);
+  scan_with_total(r, nmem.p, n, moff.p, L.scratch.p, &nmembers, s);  // the stage's scratch serves both scans: they are ordered on the stream
   HIP_CHECK(hipStreamSynchronize(s));
   DevBuf<Chain> d_chains(std::max<uint64_t>(nchains, 1));
   DevBuf<Seed> d_members(std::max<uint64_t>(nmembers, 1));
-  if (nchains) launch_chain(r, soff.p, seeds.p, n, P, nullptr, nullptr, choff.p, moff.p, d_chains.p, d_members.p, nullptr, s);
+  if (nchains) launch_chain(r, soff.p, seeds.p, n, sc.P, nullptr, nullptr, choff.p, moff.p, d_chains.p, d_members.p, nullptr, s);
   sink(r, ChainOnDevice{L.cb, c, nch.p, choff.p, moff.p, d_chains.p, d_members.p, nchains, nmembers, status.p});
   return true;
 }
@@ -109,21 +116,21 @@ void copy_out_chains(Replica& r, const ChainOnDevice& v, bool want_members, Chai
 
 // awry_chain_batch: shards over the replicas, results stitched in query order into pinned-pool arrays.  The out-pointers are
 // written only when everything has succeeded.
-void chain_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits, const ChainParams& P,
-                 uint64_t** chain_off_out, awry_chain_t** chains_out, uint64_t** seed_off_out, awry_seed_t** seeds_out, uint8_t** status_out) {
+void chain_batch(awry_index* idx, const Reads& q, const Seeding& sc, uint64_t** chain_off_out, awry_chain_t** chains_out, uint64_t** seed_off_out,
+                 awry_seed_t** seeds_out, uint8_t** status_out) {
   require_chain_index(idx->host.bwt_len);
   std::vector<ChainHits> res(std::max<size_t>(1, idx->reps.size()));
-  for_each_replica(idx, n, [&](Replica& r, Shard sh, int g) {
+  for_each_replica(idx, q.n, [&](Replica& r, Shard sh, int g) {
     HIP_CHECK(hipSetDevice(r.device));
     const auto sink = [&, g](Replica& rr, const ChainOnDevice& v) { copy_out_chains(rr, v, seeds_out != nullptr, res[g]); };
-    for (Shard c : chunk_queries(qoff, sh.lo, sh.hi))
-      halve_until_fits(c, [&](Shard h) { return chain_chunk(r, qbytes, qoff, h, min_len, max_hits, P, false, sink); });
+    for (Shard c : chunk_queries(q.off, sh.lo, sh.hi))
+      halve_until_fits(c, [&](Shard h) { return chain_chunk(r, q, h, sc, false, sink); });
   });
   MBuf<uint64_t> choff, soff;
   MBuf<awry_chain_t> chains;
   MBuf<awry_seed_t> members;
   MBuf<uint8_t> st;
-  const uint64_t total = stitch_offsets(res, &ChainHits::n_chains, n, choff);
+  const uint64_t total = stitch_offsets(res, &ChainHits::n_chains, q.n, choff);
   require(stitch_size(res, &ChainHits::chains) == total, "internal: shard results do not cover the chains");
   if (status_out) stitch_concat(res, &ChainHits::status, st);
   if (chains_out) stitch_concat(res, &ChainHits::chains, chains);

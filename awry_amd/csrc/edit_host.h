@@ -83,9 +83,8 @@ void align_chunk_hits(Replica& r, const uint8_t* text8, const ChunkBuffers& cb, 
     const uint64_t c = std::min(sub, nhits - at);
     launch_edit_align(r, text8, cb.q.p, cb.off.p, hit_query.p + at, d_gpos + at, d_edits + at, c, k, Lmax, text_len.p, n_ops.p, ops.p, s);
     flat_launch(r, s, c, align_counts_kernel, n_ops.p, c, counts.p);
-    launch_scan(r, counts.p, c, cigar_off.p, scratch.p, s);
     uint64_t runs = 0;
-    HIP_CHECK(hipMemcpyAsync(&runs, cigar_off.p + c, 8, hipMemcpyDeviceToHost, s));
+    scan_with_total(r, counts.p, c, cigar_off.p, scratch.p, &runs, s);
     HIP_CHECK(hipMemcpyAsync(out.text_len.data() + at_h + at, text_len.p, c * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(out.n_ops.data() + at_h + at, n_ops.p, c, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
@@ -129,9 +128,8 @@ bool edit_chunk(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const u
   HIP_CHECK(hipMemcpyAsync(poff.p, h_poff.data(), (np + 1) * 8, hipMemcpyHostToDevice, s));
   launch_count_ascii(r, cb.q.p, poff.p, np, pcounts.p, pranges.p, pstatus.p, s, true);
   flat_launch(r, s, n, edit_cap_kernel, pcounts.p, pstatus.p, n, k, max_candidates, cb.status.p);
-  launch_scan(r, pcounts.p, np, phoff.p, pscratch.p, s);
   uint64_t total = 0;
-  HIP_CHECK(hipMemcpyAsync(&total, phoff.p + np, 8, hipMemcpyDeviceToHost, s));
+  scan_with_total(r, pcounts.p, np, phoff.p, pscratch.p, &total, s);
   HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   for (uint64_t i = 0; i < n; i++)
@@ -153,16 +151,14 @@ bool edit_chunk(Replica& r, const uint8_t* text8, const uint8_t* qbytes, const u
     DevBuf<uint8_t> tmp(std::max<size_t>(tmp_bytes, 8));
     HIP_CHECK(rocprim::segmented_radix_sort_keys(tmp.p, tmp_bytes, key.p, key2.p, (unsigned)total, (unsigned)n, cand_off.p, cand_off.p + 1, 0, end_bit, s));
     flat_launch(r, s, total, edit_run_heads_kernel, key2.p, cand_off.p, n, total, k, heads.p);
-    launch_scan(r, heads.p, total, head_off.p, hscratch.p, s);
-    HIP_CHECK(hipMemcpyAsync(&m, head_off.p + total, 8, hipMemcpyDeviceToHost, s));
+    scan_with_total(r, heads.p, total, head_off.p, hscratch.p, &m, s);
     HIP_CHECK(hipStreamSynchronize(s));
     DevBuf<uint32_t> win_query(m), win_count(m);
     DevBuf<uint64_t> run_lo(m), run_hi(m), win_first(m), win_hits(m), win_hit_off(m + 1), wscratch(scan_tiles(m) + 1), q_hit_off(n + 1);
     flat_launch(r, s, total, edit_run_ends_kernel, key2.p, cand_off.p, n, total, k, head_off.p, win_query.p, run_lo.p, run_hi.p);
     flat_launch(r, s, m, edit_windows_kernel, win_query.p, run_lo.p, run_hi.p, m, cb.off.p, k, n_text, win_first.p, win_count.p);
     launch_edit_windows(r, text8, cb.q.p, cb.off.p, win_query.p, win_first.p, win_count.p, m, k, W, n, win_hits.p, nullptr, nullptr, nullptr, s);
-    launch_scan(r, win_hits.p, m, win_hit_off.p, wscratch.p, s);
-    HIP_CHECK(hipMemcpyAsync(&nhits, win_hit_off.p + m, 8, hipMemcpyDeviceToHost, s));
+    scan_with_total(r, win_hits.p, m, win_hit_off.p, wscratch.p, &nhits, s);
     flat_launch(r, s, n + 1, edit_query_hit_off_kernel, cand_off.p, head_off.p, win_hit_off.p, n, q_hit_off.p);
     HIP_CHECK(hipMemcpyAsync(h_qhoff.data(), q_hit_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));

@@ -55,11 +55,9 @@ bool locate_mismatch_chunk(Replica& r, const uint8_t* qbytes, const uint64_t* qo
   upload_chunk(r, cb, qbytes, qoff, c);
   DevBuf<uint64_t> totals(n), nleaves(n), hit_off(n + 1), leaf_off(n + 1), scratch(scan_tiles(n) + 1);
   launch_count_leaves(r, classes, cb.q.p, cb.off.p, n, k, nullptr, totals.p, nleaves.p, cb.status.p, s, nullptr, nullptr, nullptr, nullptr);
-  launch_scan(r, totals.p, n, hit_off.p, scratch.p, s);
   uint64_t total = 0, nleaf = 0;
-  HIP_CHECK(hipMemcpyAsync(&total, hit_off.p + n, 8, hipMemcpyDeviceToHost, s));
-  launch_scan(r, nleaves.p, n, leaf_off.p, scratch.p, s);
-  HIP_CHECK(hipMemcpyAsync(&nleaf, leaf_off.p + n, 8, hipMemcpyDeviceToHost, s));
+  scan_with_total(r, totals.p, n, hit_off.p, scratch.p, &total, s);
+  scan_with_total(r, nleaves.p, n, leaf_off.p, scratch.p, &nleaf, s);
   HIP_CHECK(hipMemcpyAsync(cb.h_status.data(), cb.status.p, n, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   check_status(cb, c.lo);

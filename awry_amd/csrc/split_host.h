@@ -1,7 +1,8 @@
-// split_host.h -- the driver of awry_map_split_batch: map_host.h's chunk and batch drivers with the split selection
-// (kernels_split.hip.h) in the place of map_select.  split_chunk is a sink of chain_chunk over the doubled batch, like map_chunk:
-// the first chains of every query, the clipped alignment count pass over all of them, the split selection per read (count pass,
-// scan, fill pass), and the CIGAR fill over the reported alignments (fill_reported_cigars).
+// split_host.h -- the driver of awry_map_split_batch: map_host.h's chunk and batch drivers (select_chunk, map_batch_over) with the
+// split selection (kernels_split.hip.h) in the place of map_select.  split_chunk is a sink of chain_chunk over the doubled batch,
+// like map_chunk: the candidates stage in the clipped mode (align_candidates), the split selection per read (count pass, scan, fill
+// pass), and the CIGAR fill over the reported alignments (fill_reported_cigars).  The reads, the seeding parameters and the result
+// arrays arrive in the family's bundles (Reads, Seeding, MapOut).
 // A part of awry_hip.hip (one translation unit): included there, in order, after map_host.h, and not on its own.
 #pragma once
 
@@ -35,24 +36,20 @@ SplitParams split_params(uint64_t chains_per_strand, uint64_t max_segments, uint
 }
 
 // select_chunk (map_host.h) with the split selection; the read lengths are those of the chunk's doubled batch, L_i = off[2i+1] - off[2i]
-void split_chunk(Replica& r, const uint8_t* text8, const ChainOnDevice& v, uint32_t A, const SplitParams& sp, int band, const AlignMode& md, const MapMode& mm,
-                 bool want_pos, bool want_cigar, MapHitsOf<awry_map_split_t>& out) {
+void split_chunk(Replica& r, const ChainOnDevice& v, const ChunkAlign& ca, const SplitParams& sp, const MapMode& mm, MapHitsOf<awry_map_split_t>& out) {
   const uint64_t n = v.c.hi - v.c.lo;
-  select_chunk(r, text8, v, A, band, md, want_pos, want_cigar, out,
+  select_chunk(r, v, ca, out,
                [&](const SelectedChains& S, const void* alns, uint64_t* n_maps, uint8_t* read_status, const uint64_t* map_off, void* maps, uint32_t* sel, uint64_t* pos) {
-                 launch_map_split_select(r, S.aoff.p, static_cast<const AlnClip*>(alns), S.chains.p, v.status, v.cb.off.p, 2, n, A, sp, mm, n_maps, read_status,
+                 launch_map_split_select(r, S.aoff.p, static_cast<const AlnClip*>(alns), S.chains.p, v.status, v.cb.off.p, 2, n, ca.A, sp, mm, n_maps, read_status,
                                          map_off, static_cast<MapSplitRec*>(maps), sel, pos, r.stream);
                });
 }
 
 // awry_map_split_batch: map_batch's shards, halves and stitching (map_batch_over) around split_chunk
-void split_batch(awry_index* idx, const uint8_t* qbytes, const uint64_t* qoff, uint64_t n, uint32_t min_len, uint64_t max_hits, const ChainParams& P,
-                 uint32_t chains_per_strand, const SplitParams& sp, uint32_t band, const AlignMode& md, const MapMode& mm, uint64_t** map_off_out,
-                 awry_map_split_t** maps_out, awry_pos_t** pos_out, uint64_t** cigar_off_out, uint32_t** cigar_out, uint8_t** status_out) {
-  map_batch_over(idx, qbytes, qoff, n, min_len, max_hits, P, map_off_out, maps_out, pos_out, cigar_off_out, cigar_out, status_out,
-                 [&](Replica& r, const uint8_t* text8, const ChainOnDevice& v, bool want_pos, bool want_cigar, MapHitsOf<awry_map_split_t>& out) {
-                   split_chunk(r, text8, v, chains_per_strand, sp, (int)band, md, mm, want_pos, want_cigar, out);
-                 });
+void split_batch(awry_index* idx, const Reads& q, const Seeding& sc, uint32_t chains_per_strand, const SplitParams& sp, uint32_t band, const AlignMode& md,
+                 const MapMode& mm, const MapOut<awry_map_split_t>& out) {
+  map_batch_over(idx, q, sc, chains_per_strand, band, md, out,
+                 [&](Replica& r, const ChainOnDevice& v, const ChunkAlign& ca, MapHitsOf<awry_map_split_t>& hits) { split_chunk(r, v, ca, sp, mm, hits); });
 }
 
 }  // namespace
