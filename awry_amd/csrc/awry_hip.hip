@@ -261,11 +261,7 @@ int awry_set_seed_kmer_len(awry_index_t* idx, int k) {
     require(idx != nullptr, "null index");
     require(k >= -1 && k <= 17, "seed k-mer length must be in -1..17 (amino: ..7)");
     idx->seed_k_request = k;
-    for (size_t s = 0; s < idx->reps.size(); s++) {
-      Replica& r = replica(idx, (int)s);
-      build_seed(idx, r, k < 0 ? default_seed_k(idx->host) : k);
-      sync_seed_mode(idx, r);
-    }
+    change_replicas(idx, [&](Replica& r) { rebuild_seed(idx, r, wanted_seed_k(idx)); });
   });
 }
 
@@ -834,11 +830,7 @@ int awry_set_locate_sa_ratio(awry_index_t* idx, int ratio) {
     require(idx != nullptr, "null index");
     require(ratio >= 0 && ratio <= 1024, "dense SA ratio must be in 0..1024");
     idx->dense_ratio_request = ratio;
-    for (size_t s = 0; s < idx->reps.size(); s++) {
-      build_dense_sa(idx, replica(idx, (int)s), ratio);
-      refresh_nblock(idx, replica(idx, (int)s));
-      sync_seed_mode(idx, replica(idx, (int)s));
-    }
+    change_replicas(idx, [&](Replica& r) { rebuild_dense_sa(idx, r, ratio); });
   });
 }
 int awry_set_verify(awry_index_t* idx, int after_steps) {
@@ -847,11 +839,7 @@ int awry_set_verify(awry_index_t* idx, int after_steps) {
     require(after_steps >= -1 && after_steps <= 1000, "verify threshold out of range");
     idx->verify_request = after_steps;
     if (after_steps >= 0) idx->dense_ratio_request = 1;
-    for (size_t s = 0; s < idx->reps.size(); s++) {
-      build_verify(idx, replica(idx, (int)s), after_steps);
-      refresh_nblock(idx, replica(idx, (int)s));
-      sync_seed_mode(idx, replica(idx, (int)s));
-    }
+    change_replicas(idx, [&](Replica& r) { rebuild_verify(idx, r, after_steps); });
   });
 }
 int awry_set_verify_kmers(awry_index_t* idx, int on) {
@@ -865,10 +853,10 @@ int awry_set_lcx(awry_index_t* idx, int on) {
   return guarded([&] {
     require(idx != nullptr, "null index");
     idx->lcx_request = on ? -1 : 0;
-    for (size_t s = 0; s < idx->reps.size(); s++) sync_seed_mode(idx, replica(idx, (int)s));
+    change_replicas(idx, [](Replica&) {});
   });
 }
-int awry_lcx_enabled(const awry_index_t* idx) { return idx && !idx->reps.empty() && idx->reps[0]->dev.lcx_key != nullptr; }
+int awry_lcx_enabled(const awry_index_t* idx) { return idx && !idx->reps.empty() && idx->reps[0]->lcx_key.p != nullptr; }
 int awry_set_kmer_table(awry_index_t* idx, int mode) {
   return guarded([&] {
     require(idx != nullptr, "null index");
@@ -925,8 +913,8 @@ int awry_debug_accelerators(const awry_index_t* idx, int slot, awry_debug_accel_
   out->seed = r.wide ? (const void*)r.seed64.p : (const void*)r.seed.p;
   out->seed_k = out->seed ? r.seed_k : 0;
   out->seed_entry_bytes = r.wide ? (int32_t)sizeof(SeedEntry64) : (int32_t)sizeof(SeedEntry);
-  out->seed_pos = (int32_t)r.dev.seed_pos;
-  out->ctx_extra = (int32_t)r.dev.ctx_extra;
+  out->seed_pos = r.seed_pos ? 1 : 0;
+  out->ctx_extra = r.ctx_extra;
   out->dense_sa = r.dense_sa.p;
   out->dense_ratio = r.dense_ratio;
   out->text4 = r.text4.p;
@@ -939,7 +927,7 @@ int awry_debug_accelerators(const awry_index_t* idx, int slot, awry_debug_accel_
   }
   out->lcx_inner = r.lcx_inner.p;
   out->lcx_inner_words = r.lcx_inner.p ? r.lcx_inner.n : 0;
-  for (int t = 0; t < 8; t++) out->lcx_off[t] = r.dev.lcx_off[t];
+  for (int t = 0; t < 8; t++) out->lcx_off[t] = r.lcx_off[t];
   return AWRY_OK;
 }
 const void* awry_debug_seed_rung(awry_index_t* idx, int slot, int L) {
@@ -953,7 +941,7 @@ int awry_debug_set_ctx_extra_cap(int cap) {
   return AWRY_OK;
 }
 int awry_verify_enabled(const awry_index_t* idx) {
-  return idx && !idx->reps.empty() && (idx->reps[0]->dev.text4 != nullptr || idx->reps[0]->dev.text8 != nullptr);
+  return idx && !idx->reps.empty() && (idx->reps[0]->text4.p != nullptr || idx->reps[0]->text8.p != nullptr);
 }
 
 int awry_locate_sa_ratio(const awry_index_t* idx) {

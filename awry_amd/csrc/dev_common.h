@@ -32,6 +32,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "accel_plan.h"
 #include "alphabet.h"
 #include "count_plan.h"
 #include "host_index.h"

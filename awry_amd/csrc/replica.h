@@ -123,6 +123,7 @@ struct Replica {
   DevBuf<uint8_t> edit_text8;                 // the edit scan's own copy of the text while text8 is not resident (built on first use, edit_host.h)
   std::mutex edit_mu;
   uint32_t dense_ratio = 0;                   // 0 = use the file's bit-packed samples
+  uint32_t verify_after = 0;                  // seed-and-verify: LF steps before the text comparison (DevIndex::verify_after)
   bool verify_kmers = false;                  // also use seed-and-verify in the k-mer (L <= 32) kernel
   // survivor lists of the two-phase count schedule, one per stream (launches on one stream are ordered, so reuse is safe)
   struct SurvScratch {
@@ -163,6 +164,9 @@ struct Replica {
   std::mutex scratch_mu;  // the map below and the head ring's sequence numbers
   std::map<hipStream_t, std::unique_ptr<SurvScratch>> scratch;
   int seed_k = 0;
+  bool seed_pos = false;        // the seed table's singletons hold text positions (DevIndex::seed_pos) ...
+  int ctx_extra = 0;            // ... with this many context letters beyond 14 (DevIndex::ctx_extra)
+  uint32_t lcx_off[8] = {0};    // the levels of lcx_inner (DevIndex::lcx_off)
   int num_cus = 256;
   // blocks of count_nt2_probe_resume_kernel<TALLY, VERIFY> resident per CU, by [2 * TALLY + VERIFY] (the occupancy query of
   // each instantiation, at replica creation): its grid, and the number of survivor lists two_phase_lists sizes
@@ -170,6 +174,8 @@ struct Replica {
   // blocks of lcx_quad_reads_kernel<RAGGED> resident at once, by [RAGGED] (the occupancy query at replica creation): its
   // grid, and the number of waves whose partly filled chunks two_phase_lists makes room for in the LF list
   unsigned lcx_reads_grid[2] = {0, 0};
+  // The kernels' view.  The index fields are written once (accelerators.h upload_index); every accelerator field is written by
+  // publish() alone, from the buffers and the host-side state above.
   DevIndex dev{};
   ~Replica() {
     if (device >= 0) {
@@ -239,18 +245,17 @@ int grid_for(const Replica& r, uint64_t work_items, int per_block, int blocks_pe
 std::atomic<int> g_force_wide{0};
 bool narrow(const HostIndex& h) { return h.bwt_len < (1ull << 32) - 512 && !g_force_wide.load(); }
 
-// HBM the accelerator policies may plan with on the current device: what is free now, capped by AWRY_HBM_BUDGET_GB (a
-// process that shares the GPU, or wants room for its own buffers, sets it; the seed table is sized to 70 % and the
-// verify accelerators admitted below 50 % of this figure)
-bool hbm_budget(size_t* free_out) {
+// HBM the accelerator policies may plan with on the current device (accel_plan.h HbmFree): what is free now, capped by
+// AWRY_HBM_BUDGET_GB (a process that shares the GPU, or wants room for its own buffers, sets it; the seed table is sized to
+// 70 % and the verify accelerators admitted below 50 % of this figure)
+HbmFree hbm_free() {
   size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return HbmFree{};
   if (const char* e = getenv("AWRY_HBM_BUDGET_GB")) {
     const double gb = atof(e);
     if (gb > 0) free_b = std::min<size_t>(free_b, (size_t)(gb * 1e9));
   }
-  *free_out = free_b;
-  return true;
+  return HbmFree{true, free_b};
 }
 
 // survivor lists of the two-phase schedules, one set per stream

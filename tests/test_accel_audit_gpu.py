@@ -306,6 +306,32 @@ def test_wide_row_tables():
         ix.close()
 
 
+def test_a_knob_refused_on_wide_rows_leaves_what_is_held():
+    """set_locate_sa_ratio and set_verify need 32-bit rows: on a wide-row replica each has dropped its accelerators (none were
+    there) by the time it refuses, and what the kernels see must still be what is held -- no dense SA, no texts, the wide table"""
+    text, st, hd, ref = world("5k")
+    k = DEFAULT_K_E["5k"][0]
+    ix = FmIndex.from_text(text, 0, 8, 0, st, hd)
+    try:
+        with wide_rows():
+            ix.set_devices([0])
+        q2d = synth.sampled_queries(text, 2000, 12, 12)
+        before = ix.count_kmers_nt2(q2d, True)
+        assert (before >= 1).all()
+        audit(ix, ref, "wide rows", k, False, 0, False, 0, False, wide=True)
+        for what, knob in (("set_locate_sa_ratio(2)", lambda: ix.set_locate_sa_ratio(2)), ("set_verify(2)", lambda: ix.set_verify(2))):
+            with pytest.raises(awry_amd.fm_index.AwryError) as err:
+                knob()
+            assert err.value.code == awry_amd.fm_index.ERR_ARG, what
+            a = ix.debug_accelerators()
+            assert not a["dense_sa"] and a["dense_ratio"] == 0 and not a["text4"] and not a["text8"], (what, a)
+            audit(ix, ref, "wide rows after " + what, k, False, 0, False, 0, False, wide=True)
+            assert np.array_equal(ix.count_kmers_nt2(q2d, True), before), what
+    finally:
+        L_.awry_debug_force_wide_rows(0)
+        ix.close()
+
+
 # ---- 6. amino ------------------------------------------------------------------------------------------------------------------------------
 def amino_tables():
     text, st, hd, ref = world("amino")
